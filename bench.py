@@ -11,17 +11,22 @@ step runs --spinup times (default 400 = 0.1 s, untimed, reported as "clock_spinu
 GPU runs its first ~25 steps 10 % slower, and W = 5 steps are 1.3 ms.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W        # starts its N ranks itself (launch.py)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra
-objects: "roofline" (the emission kernel, algorithmic bytes / HIP-event duration
-measured on the kernel's own stream) and "cpu_baseline" (the oracle, i.e. a port of
-the reference's C path, timed on this box's host cores on a bounded sample).  Further keys:
-"ms_per_step_cold" / "value_cold" (the same W + K steps before the clock spin-up), "job_ms" (a
-whole training job: upload + initial model + EM under the reference's stopping rule),
-"ranks" / "allreduce_ms" (N > 1: ranks as the process group sees them, HIP-event time of the
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, spin-up
+and warmup, the K timed steps, and the line ("metric", "value", "unit", "ms_per_step", "dtype",
+..., "loglik_per_frame").  --dump-outputs DIR writes what the last timed step computed (the
+re-estimated model and the E-step's statistics) as DIR/<name>.npy.
+
+--full adds the side measurements, in runs of their own outside the timed steps: "roofline"
+(the emission kernel, algorithmic bytes / HIP-event duration measured on the kernel's own
+stream), "kernel_ms", "cpu_baseline" (the oracle, i.e. a port of the reference's C path, timed
+on the host's cores on a bounded sample), "ms_per_step_cold" / "value_cold" (the same W + K
+steps before the clock spin-up), "extras" and "job_ms" (a whole training job: upload + initial
+model + EM under the reference's stopping rule), "allreduce_ms" (N > 1: HIP-event time of the
 statistics all-reduce per step), extras.config4 at 8 GPUs (BASELINE configs[3]); every extra
 carries "checks_ok" (invariants of its results, evaluated outside the timed regions).
 """
@@ -39,13 +44,19 @@ from _load import load_pkg  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 measured copy rate
 F64_PEAK_TFLOPS = 78.6  # MI355X FP64 vector = matrix peak
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: under 64 MB in all, .npy headers included
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed EM steps")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: cold pass, instrumented pass (kernel_ms, roofline, "
+                         "allreduce_ms), CPU baseline, extras, config4")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the model and statistics of the last timed step as DIR/<name>.npy")
     ap.add_argument("--spinup", type=int, default=400,
                     help="EM steps run (untimed) before the warmup steps so that the GPU is at its operating "
                          "clocks: after idling, the first ~25 steps (6 ms) run 10 %% slower (0 = none)")
@@ -57,16 +68,18 @@ def main():
     ap.add_argument("--kernels", type=int, default=0, help="0 auto, 1 vector-ALU, 2 MFMA")
     ap.add_argument("--fused-scan", type=int, default=0,
                     help="GHMM_OPT_FUSED_SCAN: 0 / 1 the recursions in one launch, 2 in separate launches (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the SURVEY §8(d) side measurements (decode, 64 mixtures, 2 000 states, "
-                         "ragged lengths, EM from the reference's initial model)")
+                    help="--full without the SURVEY §8(d) side measurements (decode, 64 mixtures, 2 000 "
+                         "states, ragged lengths, EM from the reference's initial model)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--config4", choices=("auto", "on", "off"), default="auto",
-                    help="N > 1 only: BASELINE configs[3] (64 mixtures, 12 500 utterances per GPU, fixed 10 "
-                         "iterations) as extras.config4; auto = at 8 GPUs")
+                    help="--full, N > 1 only: BASELINE configs[3] (64 mixtures, 12 500 utterances per GPU, "
+                         "fixed 10 iterations) as extras.config4; auto = at 8 GPUs")
     ap.add_argument("--config4-utts", type=int, default=12500, help="utterances per GPU of --config4")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     pkg = load_pkg()
     if args.gpus > 1 and not pkg.launch.under_launcher():
@@ -138,11 +151,16 @@ def main():
             dt = float(t.item())
         return dt
 
-    # (1) COLD: the contract's W warmup steps and K timed steps on a GPU that has just been
-    # idle (what a reference-style training job of ~10 iterations sees): "ms_per_step_cold".
-    for _ in range(args.warmup):
-        driver.step()
-    elapsed_cold = timed(args.steps)
+    # (1) --full, COLD: the W warmup steps and K timed steps on a GPU that has just been idle
+    # (what a reference-style training job of ~10 iterations sees): "ms_per_step_cold".  The
+    # model then goes back to the start model, so that the headline steps compute what they
+    # compute in a plain run.
+    elapsed_cold = None
+    if args.full:
+        for _ in range(args.warmup):
+            driver.step()
+        elapsed_cold = timed(args.steps)
+        model.set(start)
     # (2) Clock spin-up, then W warmup steps, then the K timed steps: the headline.  Measured on
     # one box (steps 20): warmup 5 alone 0.275 ms per step, warmup 50 0.249, warmup 200 0.246 — an
     # idle MI355X needs some tens of milliseconds of work to reach its operating clocks, and 5
@@ -154,72 +172,53 @@ def main():
         driver.step()
     elapsed = timed(args.steps)
     loglik = backend.loglik()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the re-estimated model and the statistics of the
+        # E-step behind it (log P and the utterance count are its last two entries); the ranks
+        # hold the same model and, after the all-reduce, the same statistics
+        hm = model.get()
+        dump_outputs(args.dump_outputs, {"model_A": hm.A, "model_c": hm.c, "model_mean": hm.mean,
+                                         "model_inv_var": hm.inv_var, "model_det": hm.det,
+                                         "stats": backend.stats.download()})
 
-    # (3) INSTRUMENTED pass of the same K steps: every kernel bracketed by HIP events on the
-    # stream the kernels run on (kept out of the timed region above: two event records per
-    # launch perturb a ~100 us step — this pass runs ~6 % slower, so "kernel_ms" sums to more
-    # than "ms_per_step"), and the all-reduce between two events on that same stream.
-    ctx.set_option(G.OPT_TIMING, 1)
-    ctx.kernel_times_reset()
-    ar_events = []
-    for _ in range(args.steps):
-        backend.estep()
-        if world > 1:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            dist.all_reduce(backend.stats_tensor(), op=dist.ReduceOp.SUM)
-            e1.record(stream)
-            ar_events.append((e0, e1))
-        backend.mstep()
-    kt = ctx.kernel_times()
-    ctx.set_option(G.OPT_TIMING, 0)
-    torch.cuda.synchronize()
-    allreduce_ms = (sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)) if ar_events else None
-    # per EM step: total HIP-event time of each kernel class / steps (a class may hold
-    # several launches per step, e.g. "reduce")
-    kavg = {k: (ms / args.steps if n else None) for k, (ms, n) in kt.items()}
+    if args.full:
+        # (3) INSTRUMENTED pass of the same K steps: every kernel bracketed by HIP events on the
+        # stream the kernels run on (kept out of the timed region above: two event records per
+        # launch perturb a ~100 us step — this pass runs ~6 % slower, so "kernel_ms" sums to more
+        # than "ms_per_step"), and the all-reduce between two events on that same stream.
+        ctx.set_option(G.OPT_TIMING, 1)
+        ctx.kernel_times_reset()
+        ar_events = []
+        for _ in range(args.steps):
+            backend.estep()
+            if world > 1:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                dist.all_reduce(backend.stats_tensor(), op=dist.ReduceOp.SUM)
+                e1.record(stream)
+                ar_events.append((e0, e1))
+            backend.mstep()
+        kt = ctx.kernel_times()
+        ctx.set_option(G.OPT_TIMING, 0)
+        torch.cuda.synchronize()
+        allreduce_ms = (sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)) if ar_events else None
+        # per EM step: total HIP-event time of each kernel class / steps (a class may hold
+        # several launches per step, e.g. "reduce")
+        kavg = {k: (ms / args.steps if n else None) for k, (ms, n) in kt.items()}
 
-    # (4) N > 1: BASELINE configs[3] — 64 mixtures, 12 500 utterances x 300 frames PER GPU (100 000
-    # over 8 GPUs), fixed 10 EM iterations with the statistics all-reduce (every rank takes part)
-    config4 = None
-    want4 = args.config4 == "on" or (args.config4 == "auto" and world == 8)
-    if world > 1 and want4:
-        try:
-            config4 = config4_sharded(G, em, ctx, torch, dist, local, rank, world, stream,
-                                      args.config4_utts, barrier)
-        except Exception as e:   # noqa: BLE001 - the headline line must survive a failing extra
-            config4 = {"error": f"{type(e).__name__}: {e}"[:300], "checks_ok": False}
+        # (4) N > 1: BASELINE configs[3] — 64 mixtures, 12 500 utterances x 300 frames PER GPU (100 000
+        # over 8 GPUs), fixed 10 EM iterations with the statistics all-reduce (every rank takes part)
+        config4 = None
+        want4 = args.config4 == "on" or (args.config4 == "auto" and world == 8)
+        if world > 1 and want4:
+            try:
+                config4 = config4_sharded(G, em, ctx, torch, dist, local, rank, world, stream,
+                                          args.config4_utts, barrier)
+            except Exception as e:   # noqa: BLE001 - the headline line must survive a failing extra
+                config4 = {"error": f"{type(e).__name__}: {e}"[:300], "checks_ok": False}
 
     if rank == 0:
-        Gn = N * M
         value = world * frames_rank * args.steps / elapsed
-        # emission kernel, posteriors materialised (the training path): per frame it reads
-        # the frame (8D) and writes b (8N) and post (8G) — SURVEY.md §8(d) "emission +
-        # posteriors materialised" = 1 032 B at 10x8
-        emis_ms = kavg.get("emission")
-        bytes_per_frame = 8 * (D + N + Gn)
-        flops_per_frame = Gn * (3 * D + 2)
-        roofline = None
-        if emis_ms:
-            ach = bytes_per_frame * frames_rank / (emis_ms * 1e-3) / 1e9
-            roofline = {
-                "kernel": "k_emission", "bound": "hbm", "achieved": round(ach, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                "traffic": emission_traffic(frames_rank, N, M, D),
-                "avg_kernel_ms": round(emis_ms, 5),
-                "bytes_per_frame": bytes_per_frame, "frames_per_launch": frames_rank,
-                "f64_tflops": round(flops_per_frame * frames_rank / (emis_ms * 1e-3) / 1e12, 3),
-                "f64_frac": round(flops_per_frame * frames_rank / (emis_ms * 1e-3) / 1e12
-                                  / F64_PEAK_TFLOPS, 4),
-            }
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(G, start, X, lens, args.cpu_seconds)
-        extras = None
-        if world == 1 and not args.no_extras and (N, M, D, U, T) == (10, 8, 39, 1000, 300):
-            extras = side_measurements(G, em, ctx, torch, local, mean, std, start, corpus, kavg, X)
-        if config4 is not None:
-            extras = dict(extras or {}, config4=config4)
         out = {
             "metric": "frames/sec Baum-Welch (39-d MFCC, 10 states x 8 mix)",
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -232,24 +231,55 @@ def main():
                        "frames_per_step": world * frames_rank,
                        "parallelism": f"utterance-sharded x{world}, 1 all-reduce of "
                                       f"{G.stats_len(N, M, D)} f64 per iteration"},
-            "roofline": roofline, "cpu_baseline": cpu,
-            "kernel_ms": {k: (round(v, 5) if v else None) for k, v in kavg.items()},
-            "kernel_ms_source": "second, instrumented pass of the same K steps (two HIP events per launch; "
-                                "it runs a few % slower than the timed pass, so the sum exceeds ms_per_step); "
-                                "'forward' = k_scan_combine when 'backward' is null: both scans and the gamma / xi "
-                                "pass of the E-step in one launch",
             "clock_spinup_steps": max(0, args.spinup),
-            # the same W + K steps BEFORE the spin-up, on a GPU coming out of idle
-            "ms_per_step_cold": round(1e3 * elapsed_cold / args.steps, 4),
-            "value_cold": round(world * frames_rank * args.steps / elapsed_cold, 1),
             "ranks": dist.get_world_size() if world > 1 else 1,
             "dist_backend": (dist.get_backend() if world > 1 else None),
-            "allreduce_ms": (round(allreduce_ms, 5) if allreduce_ms is not None else None),
-            "extras": extras,
             "loglik_per_frame": round(loglik / (world * frames_rank), 6),
         }
-        if extras and "job" in extras:
-            out["job_ms"] = extras["job"]["job_ms"]
+        if args.full:
+            Gn = N * M
+            # emission kernel, posteriors materialised (the training path): per frame it reads
+            # the frame (8D) and writes b (8N) and post (8G) — SURVEY.md §8(d) "emission +
+            # posteriors materialised" = 1 032 B at 10x8
+            emis_ms = kavg.get("emission")
+            bytes_per_frame = 8 * (D + N + Gn)
+            flops_per_frame = Gn * (3 * D + 2)
+            roofline = None
+            if emis_ms:
+                ach = bytes_per_frame * frames_rank / (emis_ms * 1e-3) / 1e9
+                roofline = {
+                    "kernel": "k_emission", "bound": "hbm", "achieved": round(ach, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                    "traffic": emission_traffic(frames_rank, N, M, D),
+                    "avg_kernel_ms": round(emis_ms, 5),
+                    "bytes_per_frame": bytes_per_frame, "frames_per_launch": frames_rank,
+                    "f64_tflops": round(flops_per_frame * frames_rank / (emis_ms * 1e-3) / 1e12, 3),
+                    "f64_frac": round(flops_per_frame * frames_rank / (emis_ms * 1e-3) / 1e12
+                                      / F64_PEAK_TFLOPS, 4),
+                }
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(G, start, X, lens, args.cpu_seconds)
+            extras = None
+            if world == 1 and not args.no_extras and (N, M, D, U, T) == (10, 8, 39, 1000, 300):
+                extras = side_measurements(G, em, ctx, torch, local, mean, std, start, corpus, kavg, X)
+            if config4 is not None:
+                extras = dict(extras or {}, config4=config4)
+            out.update({
+                "roofline": roofline, "cpu_baseline": cpu,
+                "kernel_ms": {k: (round(v, 5) if v else None) for k, v in kavg.items()},
+                "kernel_ms_source": "second, instrumented pass of the same K steps (two HIP events per launch; "
+                                    "it runs a few % slower than the timed pass, so the sum exceeds ms_per_step); "
+                                    "'forward' = k_scan_combine when 'backward' is null: both scans and the gamma / xi "
+                                    "pass of the E-step in one launch",
+                # the same W + K steps BEFORE the spin-up, on a GPU coming out of idle
+                "ms_per_step_cold": round(1e3 * elapsed_cold / args.steps, 4),
+                "value_cold": round(world * frames_rank * args.steps / elapsed_cold, 1),
+                "allreduce_ms": (round(allreduce_ms, 5) if allreduce_ms is not None else None),
+                "extras": extras,
+            })
+            if extras and "job" in extras:
+                out["job_ms"] = extras["job"]["job_ms"]
         print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:
@@ -528,6 +558,20 @@ def config5_emission(G, ctx, torch, dev, F=1_000_000, N=2000, M=16, D=39):
             "ms": round(ms, 3), "matrix_tflops": round(tf, 2), "f64_peak_tflops": F64_PEAK_TFLOPS,
             "mfma_frac": round(tf / F64_PEAK_TFLOPS, 4), "output_bytes": 8 * F * N,
             "first_4096_frames_finite_positive": ok, "checks_ok": ok}
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays (name -> array) as path/<name>.npy in float64.  Above `limit` bytes in all, each array
+    keeps the same fixed, seeded sample of its flattened entries (a share of the limit by size)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(20260104)
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, a.size * limit // total)
+            a = a.ravel()[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def emission_traffic(frames, N, M, D):

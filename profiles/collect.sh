@@ -13,7 +13,7 @@ stats() { # $1 = name, rest = command after --
   f=$(ls "$OUT/$n"/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/${n}_kernel_stats.csv"
 }
-stats bench python3 bench.py --no-extras --no-cpu-baseline --steps 40 --warmup 3
+stats bench python3 bench.py --full --no-extras --no-cpu-baseline --steps 40 --warmup 3
 echo "bench stats done"
 bash profiles/pmc_passes.sh "$OUT/pmc" > "$OUT/pmc.log" 2>&1
 python3 profiles/pmc_summary.py "$OUT/pmc" k_emission_sched k_mixstats_mfma k_scan_combine k_scan_pair k_combine k_backward_fix k_reduce_all k_mstep_mfma > "$OUT/pmc_summary.txt"
@@ -24,7 +24,7 @@ stats config5 python3 profiles/config5_emission.py
 echo "config5 done"
 stats decode python3 profiles/decode_time.py
 echo "decode done"
-stats m64 python3 bench.py --no-extras --no-cpu-baseline --steps 3 --warmup 1 --mix 64 --utts 12500
+stats m64 python3 bench.py --full --no-extras --no-cpu-baseline --steps 3 --warmup 1 --mix 64 --utts 12500
 echo "m64 done"
 stats refinit python3 profiles/train_trace.py
 echo "refinit done"

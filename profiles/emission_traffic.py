@@ -25,7 +25,7 @@ traffic = int(round((2 * fetch + write) * 1024))
 alg = 1032 * 300000
 out = {
     "source": f"profiles/{tag}_pmc_sq_tcc.txt (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, "
-              "profiles/pmc_passes.sh = bench.py --steps 3 --warmup 1 --no-extras), profiles/emission_traffic.py",
+              "profiles/pmc_passes.sh = bench.py --full --steps 3 --warmup 1 --no-extras), profiles/emission_traffic.py",
     "kernel": name, "frames_per_launch": 300000,
     "FETCH_SIZE_KB": round(fetch, 1), "WRITE_SIZE_KB": round(write, 1),
     "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request of a wide coalesced read "

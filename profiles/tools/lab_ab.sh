@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 for rep in 1 2 3; do
 for b in "$@"; do
   lib="$PWD/speech-recognition-hmm-continuous_amd/build/libghmm_lab$b.so"
-  GHMM_HIP_LIB="$lib" python3 bench.py --no-extras --no-cpu-baseline --steps 100 --warmup 5 2>/dev/null |
+  GHMM_HIP_LIB="$lib" python3 bench.py --full --no-extras --no-cpu-baseline --steps 100 --warmup 5 2>/dev/null |
     python3 -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms']; print('lab $b', 'emission', k['emission'], 'step_ms', d['ms_per_step'])"
 done; done
 for b in "$@"; do

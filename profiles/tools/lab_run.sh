@@ -7,7 +7,7 @@ cd "$HERE"
 for b in "$@"; do
   lib="$HERE/speech-recognition-hmm-continuous_amd/build/libghmm_lab$b.so"
   [ "$b" = "0" ] && lib="$HERE/speech-recognition-hmm-continuous_amd/libghmm_hip.so"
-  GHMM_HIP_LIB="$lib" python3 bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null |
+  GHMM_HIP_LIB="$lib" python3 bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null |
     python3 -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms']; print('lab $b', 'emission', k['emission'], 'mixstats', k['mixstats'], 'fwd', k['forward'], 'bwd', k['backward'], 'step_ms', d['ms_per_step'])"
 done
 for b in $CHECK; do

@@ -6,7 +6,7 @@ for b in "$@"; do
   [ "$b" = "0" ] && lib="$PWD/speech-recognition-hmm-continuous_amd/libghmm_hip.so"
   out=gpurun_out/labstats_$b
   rm -rf "$out"; mkdir -p "$out"
-  GHMM_HIP_LIB="$lib" rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python3 bench.py --no-extras --no-cpu-baseline --steps 40 --warmup 3 > "$out/log.txt" 2>&1
+  GHMM_HIP_LIB="$lib" rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python3 bench.py --full --no-extras --no-cpu-baseline --steps 40 --warmup 3 > "$out/log.txt" 2>&1
   echo "== $b: $(grep -o '"ms_per_step": [0-9.]*' "$out/log.txt")"
   python3 - "$out" <<'PY'
 import csv, glob, sys

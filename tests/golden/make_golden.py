@@ -4,9 +4,10 @@
 Run in the build container only (needs /root/reference):
     sh oracle/build_ref.sh && python tests/golden/make_golden.py
 
-Inputs : the 13 bundled .perfil files (copied here verbatim as data fixtures under
-         perfil/), and synthetic utterances from the product's deterministic
-         generator (ghmm_synth.c, seed 20260104).
+Inputs : the 13 bundled .perfil files and the 13 shipped full-covariance .hmm models
+         (copied here verbatim as data fixtures under perfil/ and full_cov_models/), and
+         synthetic utterances from the product's deterministic generator (ghmm_synth.c,
+         seed 20260104).
 Outputs: *.npz  — function-level dumps of the reference's own functions driven by
                   oracle/ref_harness.c (model before, b, post, alpha^, beta^, c_t,
                   log P per utterance, every accumulator, model after one M-step)
@@ -116,6 +117,12 @@ def main():
     os.makedirs(pdir, exist_ok=True)
     for fn in MEAN_LIST:
         shutil.copyfile(os.path.join(REF, "train/test/perfil_data", fn), os.path.join(pdir, fn))
+    # the full-covariance models the reference ships (the diagonal reader must refuse them)
+    mdir = os.path.join(HERE, "full_cov_models")
+    os.makedirs(mdir, exist_ok=True)
+    for fn in sorted(os.listdir(os.path.join(REF, "test/test/models"))):
+        if fn.endswith(".hmm"):
+            shutil.copyfile(os.path.join(REF, "test/test/models", fn), os.path.join(mdir, fn))
     bundled = [os.path.join(pdir, fn) for fn in MEAN_LIST]
     w186 = os.path.join(pdir, "mean_vc_186_f_03_ap_0225.perfil")
 

@@ -1699,8 +1699,9 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2 ...` exactly as the driver types it, no launcher environment:
     bench.py starts its two ranks itself (launch.py), here both on device 0 with gloo standing in
     for RCCL (a one-GPU box cannot hold a two-rank RCCL communicator), and rank 0 prints the one
-    JSON line with n_gpus = ranks = 2, the all-reduce timed, and BASELINE configs[3]'s shape
-    (64 mixtures, fixed 10 iterations, scaled down to 40 utterances per rank) as extras.config4."""
+    JSON line with n_gpus = ranks = 2, and with --full the all-reduce timed and BASELINE
+    configs[3]'s shape (64 mixtures, fixed 10 iterations, scaled down to 40 utterances per rank)
+    as extras.config4."""
     import json
     import subprocess
     import sys
@@ -1708,7 +1709,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(GHMM_FORCE_DEVICE="0", GHMM_DIST_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "1", "--spinup", "0", "--utts", "64", "--frames", "120",
+                        "--warmup", "1", "--spinup", "0", "--utts", "64", "--frames", "120", "--full",
                         "--config4", "on", "--config4-utts", "40"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -1722,6 +1723,52 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     c4 = rec["extras"]["config4"]
     assert c4["iterations"] == 10 and c4["checks_ok"] is True
     assert np.isfinite(rec["loglik_per_frame"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_output_dump(G, tmp_path):
+    """A plain `bench.py` run prints the headline line without the --full measurements, and
+    --dump-outputs writes what its last timed step computed: the model after spin-up + warmup +
+    timed EM steps from the start model, and the statistics of the E-step behind it, both
+    against the oracle.  With --full the headline steps compute the same."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    N, M, D, U, T = 10, 8, 39, 24, 120
+    spin, warm, steps = 2, 1, 3
+
+    def run(out, *extra):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                            "--steps", str(steps), "--warmup", str(warm), "--spinup", str(spin),
+                            "--utts", str(U), "--frames", str(T), "--dump-outputs", str(out), *extra],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+
+    rec, got = run(tmp_path / "plain")
+    assert rec["steps"] == steps and rec["warmup"] == warm and rec["clock_spinup_steps"] == spin
+    assert rec["ms_per_step"] > 0 and rec["value"] == pytest.approx(U * T / (rec["ms_per_step"] * 1e-3), rel=1e-2)
+    assert not {"roofline", "cpu_baseline", "kernel_ms", "ms_per_step_cold", "allreduce_ms", "extras"} & set(rec)
+    names = ["model_A", "model_c", "model_mean", "model_inv_var", "model_det", "stats"]
+    assert sorted(got) == sorted(names) and all(a.dtype == np.float64 for a in got.values())
+    mean, std = G.synth_truth(N, M, D)
+    lens = np.full(U, T, dtype=np.int32)
+    X = G.synth_utterances(mean, std, lens)
+    before, _, _, _ = O.train(G.synth_start_model(mean, std, 0.05), X, lens,
+                              max_iter=spin + warm + steps - 1, fixed_iter=True)
+    ref_stats, _ = O.estep(before, X, lens, dumps=False)
+    assert_close(got["stats"][-2], ref_stats[-2], rtol=1e-9, what="log P of the last step")
+    assert_close(got["stats"], ref_stats, rtol=1e-7, floor=1e-9, what="statistics")
+    for name, b in zip(names, O.mstep(before, ref_stats).arrays()):
+        assert_close(got[name], b, rtol=1e-6, what=name)
+    rec_full, got_full = run(tmp_path / "full", "--full", "--no-cpu-baseline", "--no-extras")
+    assert rec_full["ms_per_step_cold"] > 0 and rec_full["kernel_ms"]["emission"] > 0
+    assert rec_full["roofline"]["achieved"] > 0
+    for name in names:
+        assert_close(got_full[name], got[name], rtol=1e-10, what="--full " + name)
 
 
 def test_more_models_than_flag_slots(G, ctx):

@@ -26,7 +26,7 @@ def test_abi_library_exports_every_declared_symbol(G):
     assert lib.ghmm_version() == 200
 
 
-def test_no_cpu_fallback(G):
+def test_no_cpu_fallback(G, tmp_path):
     """Without a device the hot path must fail loudly, never compute on the host."""
     import torch
     if torch.cuda.is_available():
@@ -36,7 +36,7 @@ def test_no_cpu_fallback(G):
     assert e.value.code == G.ERR_NODEVICE
     exe = os.path.join(PKG_DIR, "bin", "hmm-continuous-train-fs")
     lst = os.path.join(GOLDEN, "perfil", "mean_vc_186_f_03_ap_0225.perfil")
-    p = subprocess.run([exe, "w", "6", "1", "1", "/dev/stdin", "/tmp/ghmm_nogpu.hmm"],
+    p = subprocess.run([exe, "w", "6", "1", "1", "/dev/stdin", str(tmp_path / "nogpu.hmm")],
                        input=(lst + "\n").encode(), stdout=subprocess.PIPE)
     assert p.returncode == 1 and b"GPU context" in p.stdout
 
@@ -120,10 +120,8 @@ def test_hmm_file_both_header_widths(G, load_case, tmp_path):
 def test_shipped_full_covariance_models_are_refused_not_misread(G):
     """The 13 .hmm files the reference ships were written by its FULL-covariance trainer on
     a 32-bit build: the diagonal reader must say 'bad format', not parse
-    garbage.  (Runs only where /root/reference is mounted.)"""
-    d = "/root/reference/test/test/models"
-    if not os.path.isdir(d):
-        pytest.skip("reference tree not present")
+    garbage.  (tests/golden/full_cov_models/: the reference's test/test/models/*.hmm verbatim.)"""
+    d = os.path.join(GOLDEN, "full_cov_models")
     files = [f for f in sorted(os.listdir(d)) if f.endswith(".hmm")]
     assert len(files) == 13
     for fn in files:
@@ -294,3 +292,28 @@ def test_rendezvous_timeouts_and_stale_files(G, tmp_path):
         with pytest.raises(G.GhmmError) as e:
             G.rendezvous_file(args[0], args[1], args[2], 0.1, ident)
         assert e.value.code == G.ERR_ARG
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: one float64 .npy per array; above the size limit, the same seeded
+    sample of every array in every run, within the limit (under 64 MB by default)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT_BYTES + 16 * 128 <= 64 * 10 ** 6     # the arrays and their .npy headers
+    arrays = {"a": np.arange(1000.0).reshape(10, 100), "b": np.arange(3000, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["a.npy", "b.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    runs = []
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=8000)
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in arrays})
+    assert sum(a.nbytes for a in runs[0].values()) <= 8000
+    for k, v in arrays.items():
+        a = runs[0][k]
+        assert a.size >= 200 and np.array_equal(a, runs[1][k])
+        assert np.isin(a, v).all() and (np.diff(a) > 0).all()   # distinct entries, in storage order
