@@ -287,6 +287,45 @@ int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *co
 int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
                  double *score_host);
 
+/* ------------------------------------------ the full-covariance recogniser */
+
+/* RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c, the reference's
+ * full-covariance recogniser.  A separate opaque model: nothing of the diagonal E-step,
+ * M-step or Viterbi takes it.  One feature stream, 1 <= N <= 64 states, M >= 1 mixtures,
+ * 1 <= D <= 48 coefficients (GHMM_ERR_UNSUPPORTED outside; the reference's caps are 15, 5
+ * and 16).  Per Gaussian: mean[D], det (of the NON-inverted covariance) and the inverse
+ * covariance inv_cov[D][D] row-major as the .hmm file stores it (RC:591-707):
+ *     A[N*N], c[N*M], mean[N*M*D], inv_cov[N*M*D*D], det[N*M]
+ * calc_gaus (RC:902-954) is evaluated in the reference's direct form and order:
+ *     dif = x - mu;  aux = sum_i dif[i] * (sum_j dif[j] * inv_cov[j][i]);
+ *     gaus = exp(-aux/2) / (pow(2 pi, D/2) * sqrt(|det|))
+ * det == 0: the reference leaves gaus uninitialised; here it is what the diagonal emission
+ * gives such a Gaussian: exp(-aux/2) / 0 (inf, or NaN where exp(-aux/2) is 0).
+ * GHMM_OPT_ROBUST is not available: every call below returns GHMM_ERR_UNSUPPORTED with it. */
+typedef struct ghmm_fmodel ghmm_fmodel;
+int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out);
+void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm);
+/* host -> device; also rebuilds the per-Gaussian constant pow(2 pi, D/2) * sqrt(|det|) */
+int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
+                    const double *mean, const double *inv_cov, const double *det);
+/* device -> host (synchronises); any pointer may be NULL */
+int ghmm_fmodel_get(ghmm_ctx *ctx, ghmm_fmodel *fm, double *A, double *c, double *mean,
+                    double *inv_cov, double *det);
+int ghmm_fmodel_dims(const ghmm_fmodel *fm, int *N, int *M, int *D);
+/* calc_symbol_probab + calc_gaus (RC:855-954): b[F][N] into the workspace, readable with
+ * ghmm_fetch(GHMM_BUF_B).  The row API of the diagonal models refuses these densities. */
+int ghmm_emission_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c);
+/* emission + calc_alpha (RC:733-800) + calc_probability (RC:822-836) per utterance:
+ * log P = -sum_t log c_t, WITHOUT the final-state term log alpha^_{N-1}(T-1) that the diagonal
+ * recogniser adds (ghmm_score).  Synchronises, writes loglik[U] on the host. */
+int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host);
+/* The vocabulary loop of RC (RC:326-374) in two launches, like ghmm_score_batch: one emission
+ * launch over the concatenated Gaussians of all words, one forward launch over every (word,
+ * utterance) pair.  All models share M and D.  loglik_host[k*U + u] = log P(utterance u | model k),
+ * bit for bit what ghmm_score_full gives word by word.  Synchronises. */
+int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                          double *loglik_host);
+
 /* -------------------------------------- several GPUs: the one collective */
 
 /* Utterances shard data-parallel over ranks (one rank = one process or host thread with
@@ -366,6 +405,20 @@ int ghmm_hmm_write(const char *path, const ghmm_host_model *hm, int len_bytes);
 #define GHMM_MAX_STREAMS 8
 int ghmm_hmm_read_streams(const char *path, ghmm_host_model *hm, int max_streams, int *n_streams);
 int ghmm_hmm_write_streams(const char *path, const ghmm_host_model *hm, int n_streams, int len_bytes);
+/* The full-covariance .hmm file (reader RC:591-707; what the reference's full-covariance trainer
+ * writes, e.g. its shipped test/test/models): the same header, then per state c[M] and per
+ * mixture mean[D], det, inv_cov[D][D].  One stream: the reader returns GHMM_ERR_UNSUPPORTED for
+ * a file of several streams and GHMM_ERR_FORMAT for anything else that does not fit (a diagonal
+ * .hmm included); 4- or 8-byte length prefix, told apart by the exact file size. */
+typedef struct ghmm_host_fmodel {
+    char word[GHMM_MAX_WORD];
+    int N, M, D;
+    double *A, *c, *mean, *det, *inv_cov;
+} ghmm_host_fmodel;
+int ghmm_host_fmodel_alloc(ghmm_host_fmodel *hfm, int N, int M, int D);
+void ghmm_host_fmodel_free(ghmm_host_fmodel *hfm);
+int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm);
+int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_bytes);
 
 /* creating_initial_model TF:732-1317 (uniform segmentation, LBG splitting with
  * factors 1.005/0.995, three k-means passes, per-cell variance floored at 1e-5)

@@ -21,6 +21,7 @@
 #include "ghmm_mfma.hpp"
 #include "ghmm_pair.hpp"
 #include "ghmm_wide.hpp"
+#include "ghmm_fullcov.hpp"
 
 extern "C" void ghmm_set_error(const char *fmt, ...); // ghmm_io.c
 
@@ -79,6 +80,10 @@ struct ghmm_ctx {
     // ghmm_score_batch: the concatenated vocabulary model and the pass's tables, kept between calls
     ghmm_model *bt_cat = nullptr;
     char *bt_tab = nullptr;
+    // ghmm_score_full_batch: the same for the full-covariance vocabulary (the log P go to bt_ll)
+    ghmm_fmodel *fbt_cat = nullptr;
+    char *fbt_tab = nullptr;
+    size_t cap_fbt_tab = 0;
     double *bt_scale = nullptr, *bt_sinv = nullptr, *bt_ll = nullptr;
     size_t cap_bt_tab = 0, cap_bt_scale = 0, cap_bt_sinv = 0, cap_bt_ll = 0;
     size_t cap_fix_mark = 0, cap_fix_list = 0;
@@ -392,7 +397,11 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
         ghmm_model_destroy(ctx, ctx->bt_cat);
         ctx->bt_cat = nullptr;
     }
-    void *bufs[] = {ctx->bt_tab, ctx->bt_scale, ctx->bt_sinv, ctx->bt_ll, ctx->b_alloc, ctx->post,      ctx->alpha,     ctx->beta,    ctx->gamma,
+    if (ctx->fbt_cat) {
+        ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
+        ctx->fbt_cat = nullptr;
+    }
+    void *bufs[] = {ctx->fbt_tab, ctx->bt_tab, ctx->bt_scale, ctx->bt_sinv, ctx->bt_ll, ctx->b_alloc, ctx->post,      ctx->alpha,     ctx->beta,    ctx->gamma,
                     ctx->scale,   ctx->lognorm,   ctx->loglik,    ctx->part_xi, ctx->part_dena,
                     ctx->part_denc, ctx->part_mu, ctx->part_var,  ctx->psi,     ctx->path,
                     ctx->part_m,  ctx->sinv,      ctx->sink,      ctx->wrow,    ctx->sb,
@@ -2242,13 +2251,293 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
         kscope ks(ctx, GHMM_K_FORWARD);
         GHMM_BY_LANES(L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
                                             ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->bt_scale,
-                                            ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order));
+                                            ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
     }
     if ((rc = launch_ok("k_forward_multi"))) return rc;
     HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
                            ctx->stream));
     HIP_TRY(stream_sync(ctx));
     ctx->b_is_log = true; // the workspace b belongs to the concatenated model: not reusable
+    return GHMM_OK;
+}
+
+// ------------------------------------------------ the full-covariance recogniser (RC)
+
+struct ghmm_fmodel {
+    int N = 0, M = 0, D = 0;
+    double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
+    double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
+};
+
+// any N (the concatenated vocabulary of ghmm_score_full_batch has hundreds of states)
+static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
+{
+    ghmm_fmodel *fm = new (std::nothrow) ghmm_fmodel();
+    if (!fm) return GHMM_ERR_ALLOC;
+    fm->N = N; fm->M = M; fm->D = D;
+    const size_t G = (size_t)N * M;
+    // mean and inv_cov with FC_SLACK doubles behind them: the kernel's padded columns read there
+    const size_t nmean = G * D + FC_SLACK, ncov = G * D * D + FC_SLACK;
+    int rc;
+    if ((rc = dev_alloc(&fm->A, (size_t)N * N)) || (rc = dev_alloc(&fm->c, G)) ||
+        (rc = dev_alloc(&fm->mean, nmean)) || (rc = dev_alloc(&fm->inv_cov, ncov)) ||
+        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G))) {
+        ghmm_fmodel_destroy(ctx, fm);
+        return rc;
+    }
+    if (hipMemsetAsync(fm->mean, 0, nmean * 8, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(fm->inv_cov, 0, ncov * 8, ctx->stream) != hipSuccess) {
+        ghmm_fmodel_destroy(ctx, fm);
+        ghmm_set_error("hipMemsetAsync failed");
+        return GHMM_ERR_HIP;
+    }
+    *out = fm;
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(out, "null output");
+    *out = nullptr;
+    ARG_CHECK(N > 0 && M > 0 && D > 0, "N, M and D must be positive");
+    if (N > 64 || D > FC_DMAX) {
+        ghmm_set_error("full-covariance models take up to 64 states and %d coefficients (asked: %d states, "
+                       "%d coefficients)", FC_DMAX, N, D);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return fmodel_alloc(ctx, N, M, D, out);
+}
+
+extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
+{
+    if (!fm) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    delete fm;
+}
+
+extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
+                               const double *mean, const double *inv_cov, const double *det)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm && A && c && mean && inv_cov && det, "null argument");
+    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
+    // calc_gaus's normaliser as the reference forms it: aux1 = pow(2 pi, D/2.0), aux2 = pow(|det|, 0.5)
+    std::vector<double> den(G);
+    const double aux1 = pow(2.0 * M_PI, fm->D / 2.0);
+    for (size_t g = 0; g < G; g++) den[g] = aux1 * pow(fabs(det[g]), 0.5);
+    HIP_TRY(hipMemcpyAsync(fm->A, A, NN * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->c, c, G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->mean, mean, G * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->inv_cov, inv_cov, G * fm->D * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->det, det, G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->den, den.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(stream_sync(ctx)); // (pageable sources)
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_get(ghmm_ctx *ctx, ghmm_fmodel *fm, double *A, double *c, double *mean,
+                               double *inv_cov, double *det)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
+    if (A) HIP_TRY(hipMemcpyAsync(A, fm->A, NN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c) HIP_TRY(hipMemcpyAsync(c, fm->c, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, fm->mean, G * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (inv_cov)
+        HIP_TRY(hipMemcpyAsync(inv_cov, fm->inv_cov, G * fm->D * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (det) HIP_TRY(hipMemcpyAsync(det, fm->det, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_dims(const ghmm_fmodel *fm, int *N, int *M, int *D)
+{
+    ARG_CHECK(fm, "null model");
+    if (N) *N = fm->N;
+    if (M) *M = fm->M;
+    if (D) *D = fm->D;
+    return GHMM_OK;
+}
+
+static int check_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+{
+    if (!fm || !c) {
+        ghmm_set_error("null model or corpus");
+        return GHMM_ERR_ARG;
+    }
+    if (fm->D != c->D) {
+        ghmm_set_error("model has %d coefficients per frame, corpus has %d", fm->D, c->D);
+        return GHMM_ERR_ARG;
+    }
+    if (ctx->robust) {
+        ghmm_set_error("GHMM_OPT_ROBUST is not available with full-covariance models");
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return GHMM_OK;
+}
+
+// b[F][N] (N = the model's states, or the vocabulary's) plus what the forward launch needs
+static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
+{
+    int rc;
+    const size_t F = (size_t)c->F;
+    if ((rc = grow_b(ctx, F, (size_t)N))) return rc;
+    if ((rc = dev_grow(&ctx->scale, &ctx->cap_scale, F))) return rc;
+    if ((rc = dev_grow(&ctx->sinv, &ctx->cap_sinv, F))) return rc;
+    if (!ctx->sink) {
+        if ((rc = dev_grow(&ctx->sink, &ctx->cap_sink, (size_t)2 * WAVE * SINK_WAVES))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->sink, 0, (size_t)2 * WAVE * SINK_WAVES * sizeof(double), ctx->stream));
+    }
+    if ((rc = dev_grow(&ctx->loglik, &ctx->cap_loglik, (size_t)c->U))) return rc;
+    ctx->F = c->F;
+    ctx->U = c->U;
+    ctx->N = N;
+    ctx->G = N * M;
+    return GHMM_OK;
+}
+
+static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+{
+    // the workspace now holds densities no diagonal model owns: the row API refuses them
+    // (need_emission), and alpha^ / W / log P of an earlier pass no longer go with b
+    ctx->last_m = nullptr;
+    ctx->last_c = nullptr;
+    ctx->em_m = nullptr;
+    ctx->em_c = c;
+    ctx->em_epoch = -1;
+    ctx->b_is_log = false;
+    ctx->own_bwd_done = false;
+    ctx->beta_valid = false;
+    ctx->loglik_pieces = false;
+    if (c->F == 0) return GHMM_OK;
+    const int nch = (fm->N + FC_SC - 1) / FC_SC;
+    const dim3 grid((unsigned)((c->F + WAVE - 1) / WAVE), (unsigned)((nch + FC_WAVES - 1) / FC_WAVES));
+    const size_t lds = (size_t)fc_lds_doubles(fm->D) * sizeof(double);
+    const int DB = (fm->D + 7) / 8 * 8;
+    kscope ks(ctx, GHMM_K_EMISSION);
+#define GHMM_FCK(DBV)                                                                                         \
+    hipLaunchKernelGGL(k_emission_full<DBV>, grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M, fm->D, \
+                       c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b)
+    switch (DB) {
+    case 8: GHMM_FCK(8); break;
+    case 16: GHMM_FCK(16); break;
+    case 24: GHMM_FCK(24); break;
+    case 32: GHMM_FCK(32); break;
+    case 40: GHMM_FCK(40); break;
+    default: GHMM_FCK(48); break;
+    }
+#undef GHMM_FCK
+    return launch_ok("k_emission_full");
+}
+
+extern "C" int ghmm_emission_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
+    return run_emission_full(ctx, fm, c);
+}
+
+extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    // calc_alpha + calc_probability without the final-state term: k_scan_pair's only = 3
+    const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
+    const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+    {
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_scan_pair<LL>, dim3(blocks, 1u), dim3(WAVE), 0, ctx->stream, fm->N, c->U, 3,
+                                            fm->A, ctx->b, c->off, ctx->alpha, ctx->scale, ctx->sinv,
+                                            (const double *)nullptr, ctx->loglik, ctx->wrow, ctx->sb, ctx->sink,
+                                            c->order));
+    }
+    if ((rc = launch_ok("k_scan_pair"))) return rc;
+    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                     double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(models && n_models > 0 && c, "null argument");
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
+    const int M = models[0]->M, D = models[0]->D;
+    int NS = 0;
+    for (int k = 0; k < n_models; k++) {
+        if (models[k]->M != M || models[k]->D != D) {
+            ghmm_set_error("ghmm_score_full_batch: every model must have the same M and D");
+            return GHMM_ERR_UNSUPPORTED;
+        }
+        NS += models[k]->N;
+    }
+    if ((rc = check_full(ctx, models[0], c))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    // the concatenated vocabulary (NS states, transitions unused), kept in the context between calls
+    if (ctx->fbt_cat && (ctx->fbt_cat->N != NS || ctx->fbt_cat->M != M || ctx->fbt_cat->D != D)) {
+        ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
+        ctx->fbt_cat = nullptr;
+    }
+    if (!ctx->fbt_cat && (rc = fmodel_alloc(ctx, NS, M, D, &ctx->fbt_cat))) return rc;
+    ghmm_fmodel *cat = ctx->fbt_cat;
+    std::vector<fwd_model> tab((size_t)n_models);
+    std::vector<fgather_src> src((size_t)n_models);
+    {
+        int go = 0, so = 0;
+        for (int k = 0; k < n_models; k++) {
+            const ghmm_fmodel *m = models[k];
+            tab[k].A = m->A;
+            tab[k].N = m->N;
+            tab[k].bo = so;
+            src[k].c = m->c; src[k].mean = m->mean; src[k].inv_cov = m->inv_cov; src[k].den = m->den;
+            src[k].g0 = go; src[k].ng = m->N * M;
+            go += m->N * M;
+            so += m->N;
+        }
+    }
+    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(fgather_src);
+    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, tab_bytes + src_bytes + 16))) return rc;
+    fwd_model *dtab = (fwd_model *)ctx->fbt_tab;
+    fgather_src *dsrc = (fgather_src *)(ctx->fbt_tab + ((tab_bytes + 15) / 16) * 16);
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_gather_fmodels, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
+                       cat->mean, cat->inv_cov, cat->den);
+    if ((rc = launch_ok("k_gather_fmodels"))) return rc;
+    if ((rc = ws_full(ctx, NS, M, c)) || (rc = run_emission_full(ctx, cat, c))) return rc;
+    int Nmax = 0;
+    for (int k = 0; k < n_models; k++) Nmax = models[k]->N > Nmax ? models[k]->N : Nmax;
+    {
+        const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
+        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                            ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->sink,
+                                            ctx->sink, ctx->bt_ll, ctx->sink, c->order, 0));
+    }
+    if ((rc = launch_ok("k_forward_multi"))) return rc;
+    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
 

@@ -7,7 +7,8 @@
  *   .hmm     size_t len | word[len] | int N | int P | int M[P] | int D[P] |
  *            double A[N][N] | per stream, per state: double c[M], then per
  *            mixture: double mean[D], double det, double inv_var[D]
- *            (writer TF:2043-2146, readers TF:604-711 / RF:595-715)
+ *            (writer TF:2043-2146, readers TF:604-711 / RF:595-715); the full-covariance
+ *            files hold inv_cov[D][D] where the diagonal ones hold inv_var[D] (RC:591-707)
  *
  * The shipped .hmm files were written by a 32-bit build (4-byte size_t), a
  * 64-bit build writes 8 bytes: the reader accepts both by checking which header
@@ -343,4 +344,130 @@ int ghmm_hmm_write_streams(const char *path, const ghmm_host_model *hm, int n_st
 int ghmm_hmm_write(const char *path, const ghmm_host_model *hm, int len_bytes)
 {
     return ghmm_hmm_write_streams(path, hm, 1, len_bytes);
+}
+
+/* ------------------------------------------------- full-covariance .hmm (RC:591-707) */
+
+int ghmm_host_fmodel_alloc(ghmm_host_fmodel *hfm, int N, int M, int D)
+{
+    if (!hfm || N <= 0 || M <= 0 || D <= 0) return GHMM_ERR_ARG;
+    size_t G = (size_t)N * M;
+    hfm->N = N; hfm->M = M; hfm->D = D;
+    hfm->A = (double *)calloc((size_t)N * N, sizeof(double));
+    hfm->c = (double *)calloc(G, sizeof(double));
+    hfm->mean = (double *)calloc(G * D, sizeof(double));
+    hfm->det = (double *)calloc(G, sizeof(double));
+    hfm->inv_cov = (double *)calloc(G * D * D, sizeof(double));
+    if (!hfm->A || !hfm->c || !hfm->mean || !hfm->det || !hfm->inv_cov) {
+        ghmm_host_fmodel_free(hfm);
+        return GHMM_ERR_ALLOC;
+    }
+    return GHMM_OK;
+}
+
+void ghmm_host_fmodel_free(ghmm_host_fmodel *hfm)
+{
+    if (!hfm) return;
+    free(hfm->A); free(hfm->c); free(hfm->mean); free(hfm->det); free(hfm->inv_cov);
+    hfm->A = hfm->c = hfm->mean = hfm->det = hfm->inv_cov = NULL;
+}
+
+/* the full-covariance layout with an `lb`-byte length prefix; 0 = fits the file exactly */
+static int fhmm_try(FILE *f, long size, int lb, ghmm_host_fmodel *hfm, const char *path)
+{
+    unsigned char raw[8] = {0};
+    rewind(f);
+    if (fread(raw, 1, (size_t)lb, f) != (size_t)lb) return GHMM_ERR_FORMAT;
+    uint64_t len = 0;
+    for (int i = lb - 1; i >= 0; i--) len = (len << 8) | raw[i];
+    if (len >= GHMM_MAX_WORD) return GHMM_ERR_FORMAT;
+    char word[GHMM_MAX_WORD] = {0};
+    int32_t N = 0, P = 0, M[GHMM_MAX_STREAMS], D[GHMM_MAX_STREAMS];
+    if (fread(word, 1, (size_t)len, f) != (size_t)len) return GHMM_ERR_FORMAT;
+    if (fread(&N, 4, 1, f) != 1 || fread(&P, 4, 1, f) != 1) return GHMM_ERR_FORMAT;
+    if (N <= 0 || N > 65536 || P <= 0 || P > GHMM_MAX_STREAMS) return GHMM_ERR_FORMAT;
+    if (fread(M, 4, (size_t)P, f) != (size_t)P || fread(D, 4, (size_t)P, f) != (size_t)P) return GHMM_ERR_FORMAT;
+    long expect = lb + (long)len + 8 + 8L * P + 8L * (long)N * N;
+    for (int p = 0; p < P; p++) {
+        if (M[p] <= 0 || M[p] > 65536 || D[p] <= 0 || D[p] > 4096) return GHMM_ERR_FORMAT;
+        expect += 8L * (long)N * ((long)M[p] + (long)M[p] * ((long)D[p] * D[p] + D[p] + 1));
+    }
+    if (expect != size) return GHMM_ERR_FORMAT;
+    if (P > 1) {
+        ghmm_set_error("%s: %d feature streams, the full-covariance reader takes one", path, P);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    int rc = ghmm_host_fmodel_alloc(hfm, N, M[0], D[0]);
+    if (rc) return rc;
+    memcpy(hfm->word, word, GHMM_MAX_WORD);
+    const size_t DD = (size_t)D[0] * D[0];
+    int ok = fread(hfm->A, 8, (size_t)N * N, f) == (size_t)N * N;
+    for (int i = 0; ok && i < N; i++) {
+        ok = fread(hfm->c + (size_t)i * M[0], 8, (size_t)M[0], f) == (size_t)M[0];
+        for (int k = 0; ok && k < M[0]; k++) {
+            size_t g = (size_t)i * M[0] + k;
+            ok = fread(hfm->mean + g * D[0], 8, (size_t)D[0], f) == (size_t)D[0] &&
+                 fread(hfm->det + g, 8, 1, f) == 1 &&
+                 fread(hfm->inv_cov + g * DD, 8, DD, f) == DD;
+        }
+    }
+    if (!ok) {
+        ghmm_host_fmodel_free(hfm);
+        return GHMM_ERR_IO;
+    }
+    return GHMM_OK;
+}
+
+int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm)
+{
+    if (!path || !hfm) return GHMM_ERR_ARG;
+    memset(hfm, 0, sizeof *hfm);
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        ghmm_set_error("file %s not found", path);
+        return GHMM_ERR_IO;
+    }
+    long size = file_size(f);
+    int rc = fhmm_try(f, size, 8, hfm, path);
+    if (rc == GHMM_ERR_FORMAT) rc = fhmm_try(f, size, 4, hfm, path);
+    fclose(f);
+    if (rc == GHMM_ERR_FORMAT)
+        ghmm_set_error("%s: not a full-covariance .hmm file (4- or 8-byte header)", path);
+    else if (rc == GHMM_ERR_IO)
+        ghmm_set_error("reading error on file %s", path);
+    return rc;
+}
+
+int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_bytes)
+{
+    if (!path || !hfm || hfm->N <= 0 || hfm->M <= 0 || hfm->D <= 0 || (len_bytes != 4 && len_bytes != 8))
+        return GHMM_ERR_ARG;
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        ghmm_set_error("can't open file %s", path);
+        return GHMM_ERR_IO;
+    }
+    const int N = hfm->N, M = hfm->M, D = hfm->D;
+    const size_t DD = (size_t)D * D;
+    int32_t hdr[4] = {N, 1, M, D};
+    uint64_t len = strnlen(hfm->word, GHMM_MAX_WORD - 1);
+    int ok = fwrite(&len, 1, (size_t)len_bytes, f) == (size_t)len_bytes; /* little-endian */
+    ok = ok && fwrite(hfm->word, 1, (size_t)len, f) == (size_t)len;
+    ok = ok && fwrite(hdr, 4, 4, f) == 4;
+    ok = ok && fwrite(hfm->A, 8, (size_t)N * N, f) == (size_t)N * N;
+    for (int i = 0; ok && i < N; i++) {
+        ok = fwrite(hfm->c + (size_t)i * M, 8, (size_t)M, f) == (size_t)M;
+        for (int k = 0; ok && k < M; k++) {
+            size_t g = (size_t)i * M + k;
+            ok = fwrite(hfm->mean + g * D, 8, (size_t)D, f) == (size_t)D &&
+                 fwrite(hfm->det + g, 8, 1, f) == 1 &&
+                 fwrite(hfm->inv_cov + g * DD, 8, DD, f) == DD;
+        }
+    }
+    if (fclose(f) != 0) ok = 0;
+    if (!ok) {
+        ghmm_set_error("writing error on file %s", path);
+        return GHMM_ERR_IO;
+    }
+    return GHMM_OK;
 }

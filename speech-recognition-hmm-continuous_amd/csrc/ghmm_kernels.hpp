@@ -362,7 +362,10 @@ struct log_product {
     }
 };
 
-template <int L, bool BANDED> struct fwd_state {
+// EXACT (the full-covariance recogniser, whose log P ends with -log c_{T-1}): the banded step takes
+// recip_select as the dense one does, so that a frame whose densities are all 0 gives c_t = inf
+// like the reference's 1.0/sum (RC:780-795) and a last such frame leaves log P = -inf, not NaN
+template <int L, bool BANDED, bool EXACT = false> struct fwd_state {
     double a, a_self, a_prev, a_next;
     double acol[BANDED ? 1 : L];
     int N;
@@ -377,7 +380,7 @@ template <int L, bool BANDED> struct fwd_state {
     {
         const double v = fma(a, a_self, group_up1<L>(a) * a_prev) * bt;
         const double s = group_sum<L>(v);
-        const double c = recip_fast(s);
+        const double c = EXACT ? recip_select(s) : recip_fast(s);
         a = v * c;
         *pa = a;
         if (STORE_C) *pcs = (SINV && i != 0) ? s : c;
@@ -401,14 +404,14 @@ template <int L, bool BANDED> struct fwd_state {
     }
 };
 
-template <int L, bool BANDED, bool SINV = true, bool STORE_C = true>
+template <int L, bool BANDED, bool SINV = true, bool STORE_C = true, bool EXACT = false>
 __device__ __forceinline__ double forward_run(int N, int T, int i, bool act, const double *__restrict__ A,
                                      const double *__restrict__ bu, double *__restrict__ au,
                                      double *__restrict__ su, double *__restrict__ si,
                                      double *__restrict__ sink, int bstride, log_product *pacc = nullptr)
 {
     log_product acc;
-    fwd_state<L, BANDED> st;
+    fwd_state<L, BANDED, EXACT> st;
     st.N = N;
     st.a_self = act ? A[i * N + i] : 0.0;
     st.a_prev = (act && i > 0) ? A[(i - 1) * N + i] : 0.0;
@@ -488,8 +491,9 @@ __device__ __forceinline__ double forward_run(int N, int T, int i, bool act, con
 
 // calc_alpha + calc_probability for utterance u on the 16/64 lanes of one group
 // SCORE: log P only (ghmm_score) — alpha^ and c_t are not written, the logarithm of their product
-// is taken from its pieces in registers
-template <int L, bool SINV = true, bool SCORE = false>
+// is taken from its pieces in registers.  FINAL = false (SCORE only): the full-covariance
+// recogniser's calc_probability (RC:822-836), -sum_t log c_t without the final-state term
+template <int L, bool SINV = true, bool SCORE = false, bool FINAL = true>
 __device__ inline void forward_utt(int N, int u, int i, const double *__restrict__ A,
                                    const double *__restrict__ b, const long long *__restrict__ off,
                                    double *__restrict__ alpha, double *__restrict__ scale,
@@ -511,6 +515,15 @@ __device__ inline void forward_utt(int N, int u, int i, const double *__restrict
     double *su = scale + f0, *si = sinv + f0;
     double *snk = wave_sink(sink);
     double a;
+    if (SCORE && !FINAL) {
+        log_product pc;
+        if (banded)
+            forward_run<L, true, false, false, true>(N, T, i, act, A, b + f0 * N, nullptr, su, si, snk, N, &pc);
+        else
+            forward_run<L, false, false, false, true>(N, T, i, act, A, b + f0 * N, nullptr, su, si, snk, N, &pc);
+        if (i == 0) loglik[u] = -pc.log_value();
+        return;
+    }
     if (SCORE) {
         log_product pc;
         if (banded)
@@ -563,6 +576,7 @@ k_forward(int N, int U, const double *__restrict__ A, const double *__restrict__
 // The emission densities of ALL models were computed by one launch over the concatenated
 // Gaussians (b[F][NS], model k owns columns bo_k .. bo_k + N_k - 1); every (model,
 // utterance) pair runs calc_alpha + calc_probability here.  alpha^ is not kept.
+// final_term = 0: the full-covariance recogniser's log P (RC:822-836), without log alpha^_{N-1}(T-1).
 struct fwd_model {
     const double *A;
     int N, bo;
@@ -595,7 +609,7 @@ k_forward_multi(int U, int NS, long long F, const fwd_model *__restrict__ tab,
                 const double *__restrict__ b, const long long *__restrict__ off,
                 double *__restrict__ scale, double *__restrict__ sinv,
                 double *__restrict__ loglik, double *__restrict__ sink,
-                const int *__restrict__ order)
+                const int *__restrict__ order, int final_term)
 {
     const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
     const int i = threadIdx.x % L;
@@ -622,6 +636,14 @@ k_forward_multi(int U, int NS, long long F, const fwd_model *__restrict__ tab,
     const double *bu = b + f0 * NS + mk.bo;
     double a;
     log_product pc;
+    if (!final_term) { // (the same operations as forward_utt<L, false, true, false>: bit for bit ghmm_score_full)
+        if (banded)
+            forward_run<L, true, false, false, true>(N, T, i, act, A, bu, nullptr, snk, snk, snk, NS, &pc);
+        else
+            forward_run<L, false, false, false, true>(N, T, i, act, A, bu, nullptr, snk, snk, snk, NS, &pc);
+        if (i == 0) loglik[(size_t)k * U + u] = -pc.log_value();
+        return;
+    }
     if (banded)
         a = forward_run<L, true, false, false>(N, T, i, act, A, bu, nullptr, snk, snk, snk, NS, &pc);
     else

@@ -117,6 +117,8 @@ __device__ __forceinline__ void backward_own_run(int N, int T, int i, bool act, 
 
 // blockIdx.y (or `only` when one direction is wanted): 0 = calc_alpha + calc_probability,
 // 1 = the backward recursion with its own normaliser.  Groups of 16/64 lanes = utterances.
+// only = 2: log P alone (ghmm_score); 3: log P of the full-covariance recogniser, without the
+// final-state term (ghmm_score_full, RC:822-836).
 template <int L>
 __global__ void __launch_bounds__(WAVE)
 k_scan_pair(int N, int U, int only, const double *__restrict__ A, const double *__restrict__ b,
@@ -134,6 +136,10 @@ k_scan_pair(int N, int U, int only, const double *__restrict__ A, const double *
     const int dir = only >= 0 ? only : (int)blockIdx.y;
     if (only == 2) { // log P only (ghmm_score): nothing but loglik[] is written
         forward_utt<L, false, true>(N, u, i, A, b, off, alpha, scale, sinv, lognorm, loglik, sink);
+        return;
+    }
+    if (only == 3) {
+        forward_utt<L, false, true, false>(N, u, i, A, b, off, alpha, scale, sinv, lognorm, loglik, sink);
         return;
     }
     if (dir == 0) {

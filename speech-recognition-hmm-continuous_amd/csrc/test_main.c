@@ -15,6 +15,12 @@
  * A model set may have several feature streams (param_number P > 1): its P feature lists follow
  * each other on the command line (RF:253-262) and the score runs on the product of the streams'
  * emission densities (ghmm_score_streams, RF:349-366).
+ *
+ * Built with -DGHMM_FULL_COV this is recognition-continuous-test-full-fs, the full-covariance
+ * recogniser RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c: the same
+ * argv, lists and bookkeeping (RC:283-412), its usage text and header (RC:1019-1033), models read
+ * with ghmm_hmm_read_full (RC:591-707, one stream) and scored with ghmm_score_full_batch, whose
+ * log P has no final-state term (calc_probability, RC:822-836).
  */
 #include "ghmm.h"
 
@@ -35,7 +41,11 @@ static void die(const char *what, int rc)
 
 static void usage(void)
 {
+#ifdef GHMM_FULL_COV
+    puts("Usage: recognition_continuous_full models_number  model1 ... modelN coef_model1 ... coef_modelN input_file1 ... input_fileM  word_file output_file");
+#else
     puts("Usage: recognition_continuous_fs models_number  model1 ... modelN coef_model1 ... coef_modelN input_file1 ... input_fileM  word_file output_file");
+#endif
     puts("models_number: number of model");
     puts("model1: name of file with the name of model 1");
     puts("modelN: name of file with the name of model N");
@@ -123,7 +133,11 @@ int main(int argc, char **argv)
     int rc;
 
     /* models: one list per set, the same vocabulary in every set */
+#ifdef GHMM_FULL_COV
+    ghmm_host_fmodel *fhm[MAX_SETS]; /* fhm[j][k]: set j, word k (one stream) */
+#else
     ghmm_host_model *hm[MAX_SETS]; /* hm[j][k * GHMM_MAX_STREAMS + p]: set j, word k, stream p */
+#endif
     int Pj[MAX_SETS];              /* feature streams of set j (param_number of its models) */
     int word_number = 0;
     printf("\r\nLoading Models\r\n");
@@ -131,6 +145,20 @@ int main(int argc, char **argv)
         FILE *fl = open_read(argv[2 + j]);
         char name[4096];
         int n = 0, cap = 0;
+#ifdef GHMM_FULL_COV
+        fhm[j] = NULL;
+        Pj[j] = 1;
+        while (fscanf(fl, "%4095s", name) == 1) {
+            printf("Model: %s\r\n", name);
+            if (n == cap) {
+                cap = cap ? 2 * cap : 32;
+                fhm[j] = (ghmm_host_fmodel *)realloc(fhm[j], (size_t)cap * sizeof(ghmm_host_fmodel));
+                if (!fhm[j]) die("memory", GHMM_ERR_ALLOC);
+            }
+            if ((rc = ghmm_hmm_read_full(name, &fhm[j][n]))) die("reading model", rc);
+            n++;
+        }
+#else
         hm[j] = NULL;
         while (fscanf(fl, "%4095s", name) == 1) {
             printf("Model: %s\r\n", name);
@@ -149,6 +177,7 @@ int main(int argc, char **argv)
             }
             n++;
         }
+#endif
         fclose(fl);
         if (j > 0 && n != word_number) {
             printf("model list %s holds %d models, expected %d \n", argv[2 + j], n, word_number);
@@ -161,7 +190,11 @@ int main(int argc, char **argv)
         exit(1);
     }
     char **word = (char **)malloc((size_t)word_number * sizeof(char *));
+#ifdef GHMM_FULL_COV
+    for (int k = 0; k < word_number; k++) word[k] = fhm[K - 1][k].word; /* RC:229 */
+#else
     for (int k = 0; k < word_number; k++) word[k] = hm[K - 1][(size_t)k * GHMM_MAX_STREAMS].word; /* RF:229 */
+#endif
     int n_lists = 0;
     for (int j = 0; j < K; j++) n_lists += Pj[j];
     if (argc != 2 * K + n_lists + 4) usage();
@@ -229,6 +262,16 @@ int main(int argc, char **argv)
         printf("can't open file %s \n", output_file);
         exit(1);
     }
+#ifdef GHMM_FULL_COV
+    /* writing_header, RC:1019-1033 (coef_model is a double there) */
+    fprintf(f_out, "Isolated word recognition using Continuous HMM. It is considered full covariance matrix.\n");
+    fprintf(f_out, "Algorithm used for recognition: Forward \n");
+    fprintf(f_out, "Number of models: %d  \n", K);
+    for (int i = 0; i < K; i++) {
+        fprintf(f_out, "Model name %d: %s\n", i + 1, argv[2 + i]);
+        fprintf(f_out, "Weighting coefficient of model %d:%.2f\n", i + 1, coef_model[i]);
+    }
+#else
     /* writing_header, RF:1014-1031.  The reference declares coef_model as int* there
        and prints it with %.2d: the integer words of the double array are shown. */
     fprintf(f_out, "Isolated word recognition using Continuous HMM (diagonal covariance matrix). It is considered a final state. \n");
@@ -240,6 +283,7 @@ int main(int argc, char **argv)
         fprintf(f_out, "Model name %d: %s\n", i + 1, argv[2 + i]);
         fprintf(f_out, "Weighting coefficient of model %d:%.2d\n", i + 1, as_int);
     }
+#endif
     fprintf(f_out, "Date and time: %s \n\n", date_time);
 
     /* score[k][u] = sum_j w_j log P(utterance u | model k of set j), RF:366 */
@@ -250,6 +294,42 @@ int main(int argc, char **argv)
     if (n_utt > 0) {
         ghmm_ctx *ctx;
         if ((rc = ghmm_ctx_create(0, NULL, &ctx))) die("GPU context", rc);
+#ifdef GHMM_FULL_COV
+        for (int j = 0; j < K; j++) {
+            /* the whole vocabulary in one batched call when the models share M (ghmm_score_full_batch),
+               model by model otherwise (ghmm_score_full) */
+            ghmm_corpus *corpus;
+            if ((rc = ghmm_corpus_create(ctx, X[j][0], len[j], n_utt, D[j][0], &corpus))) die("corpus", rc);
+            ghmm_fmodel **fm = (ghmm_fmodel **)calloc((size_t)word_number, sizeof(ghmm_fmodel *));
+            double *all = (double *)malloc((size_t)word_number * (size_t)n_utt * sizeof(double));
+            if (!fm || !all) die("memory", GHMM_ERR_ALLOC);
+            int same = 1;
+            for (int k = 0; k < word_number; k++) {
+                ghmm_host_fmodel *m = &fhm[j][k];
+                if (m->D != D[j][0]) {
+                    printf("model %s has %d coefficients, data has %d \n", m->word, m->D, D[j][0]);
+                    exit(1);
+                }
+                if (m->M != fhm[j][0].M) same = 0;
+                if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, &fm[k]))) die("model", rc);
+                if ((rc = ghmm_fmodel_set(ctx, fm[k], m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
+            }
+            if (same) {
+                if ((rc = ghmm_score_full_batch(ctx, fm, word_number, corpus, all))) die("scoring", rc);
+            } else {
+                for (int k = 0; k < word_number; k++)
+                    if ((rc = ghmm_score_full(ctx, fm[k], corpus, all + (size_t)k * n_utt))) die("scoring", rc);
+            }
+            for (int k = 0; k < word_number; k++) {
+                for (int u = 0; u < n_utt; u++)
+                    score[(size_t)k * n_utt + u] += coef_model[j] * all[(size_t)k * n_utt + u];
+                ghmm_fmodel_destroy(ctx, fm[k]);
+            }
+            free(fm);
+            free(all);
+            ghmm_corpus_destroy(ctx, corpus);
+        }
+#else
         for (int j = 0; j < K; j++) {
             const int P = Pj[j];
             ghmm_corpus *corpus[GHMM_MAX_STREAMS];
@@ -295,6 +375,7 @@ int main(int argc, char **argv)
             free(all);
             for (int p = 0; p < P; p++) ghmm_corpus_destroy(ctx, corpus[p]);
         }
+#endif
         ghmm_ctx_destroy(ctx);
     }
 
@@ -346,8 +427,12 @@ int main(int argc, char **argv)
     cpu_time = aux - old_aux;
     sum_cpu_time += cpu_time;
     if (n_utt > 0) {
+#ifdef GHMM_FULL_COV
+        report_word(correct, error, second, word_number, last_word, wrong_word, word, cpu_time, word_frames);
+#else
         /* the reference passes models_number where word_number belongs (RF:400) */
         report_word(correct, error, second, K, last_word, wrong_word, word, cpu_time, word_frames);
+#endif
         sum_correct += correct;
         sum_error += error;
         sum_second += second;
@@ -369,9 +454,14 @@ int main(int argc, char **argv)
         exit(1);
     }
     for (int j = 0; j < K; j++) {
+#ifdef GHMM_FULL_COV
+        for (int k = 0; k < word_number; k++) ghmm_host_fmodel_free(&fhm[j][k]);
+        free(fhm[j]);
+#else
         for (int k = 0; k < word_number; k++)
             for (int p = 0; p < Pj[j]; p++) ghmm_host_model_free(&hm[j][(size_t)k * GHMM_MAX_STREAMS + p]);
         free(hm[j]);
+#endif
         for (int p = 0; p < Pj[j]; p++) free(X[j][p]);
         free(len[j]);
     }

@@ -42,6 +42,11 @@ class HostModelStruct(C.Structure):
                 ("A", _dp), ("c", _dp), ("mean", _dp), ("inv_var", _dp), ("det", _dp)]
 
 
+class HostFullModelStruct(C.Structure):
+    _fields_ = [("word", C.c_char * MAX_WORD), ("N", C.c_int), ("M", C.c_int), ("D", C.c_int),
+                ("A", _dp), ("c", _dp), ("mean", _dp), ("det", _dp), ("inv_cov", _dp)]
+
+
 # every exported symbol of include/ghmm.h: name -> (restype, argtypes, needs_hip)
 SYMBOLS = {
     "ghmm_strerror": (C.c_char_p, [C.c_int], False),
@@ -97,6 +102,15 @@ SYMBOLS = {
     "ghmm_estep_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp)], True),
     "ghmm_score_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _dp], True),
     "ghmm_viterbi": (C.c_int, [_vp, _vp, _vp, _ip, _dp], True),
+    "ghmm_fmodel_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
+    "ghmm_fmodel_destroy": (None, [_vp, _vp], True),
+    "ghmm_fmodel_set": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp], True),
+    "ghmm_fmodel_get": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp], True),
+    "ghmm_fmodel_dims": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int)], True),
+    "ghmm_emission_full": (C.c_int, [_vp, _vp, _vp], True),
+    "ghmm_score_full": (C.c_int, [_vp, _vp, _vp, _dp], True),
+    "ghmm_score_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -114,6 +128,11 @@ SYMBOLS = {
                                         C.POINTER(C.c_int)], False),
     "ghmm_hmm_write_streams": (C.c_int, [C.c_char_p, C.POINTER(HostModelStruct), C.c_int, C.c_int],
                                False),
+    "ghmm_host_fmodel_alloc": (C.c_int, [C.POINTER(HostFullModelStruct), C.c_int, C.c_int, C.c_int],
+                               False),
+    "ghmm_host_fmodel_free": (None, [C.POINTER(HostFullModelStruct)], False),
+    "ghmm_hmm_read_full": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct)], False),
+    "ghmm_hmm_write_full": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct), C.c_int], False),
     "ghmm_init_model": (C.c_int, [_dp, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(HostModelStruct)], False),
     "ghmm_synth_truth": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp, _dp], False),
@@ -250,6 +269,53 @@ class HostModel:
         _check(lib.ghmm_init_model(_d(X), lens.ctypes.data_as(_ip), len(lens), N, M, X.shape[1],
                                    C.byref(s)), lib)
         return HostModel._from_struct(s, lib)
+
+
+class HostFullModel:
+    """A full-covariance model in host memory (ghmm_host_fmodel): inv_cov[N, M, D, D] where
+    HostModel has inv_var[N, M, D]; det is that of the non-inverted covariance."""
+
+    def __init__(self, A, c, mean, inv_cov, det, word=""):
+        self.A = _f64(A)
+        self.N = self.A.shape[0]
+        self.c = _f64(c).reshape(self.N, -1)
+        self.M = self.c.shape[1]
+        self.mean = _f64(mean).reshape(self.N, self.M, -1)
+        self.D = self.mean.shape[2]
+        self.inv_cov = _f64(inv_cov).reshape(self.N, self.M, self.D, self.D)
+        self.det = _f64(det).reshape(self.N, self.M)
+        self.word = word
+
+    def arrays(self):
+        """(A, c, mean, inv_cov, det): the argument order of ghmm_fmodel_set"""
+        return self.A, self.c, self.mean, self.inv_cov, self.det
+
+    def _struct(self):
+        s = HostFullModelStruct()
+        s.word = self.word.encode()[:MAX_WORD - 1]
+        s.N, s.M, s.D = self.N, self.M, self.D
+        s.A, s.c, s.mean, s.det, s.inv_cov = (_d(x) for x in (self.A, self.c, self.mean, self.det,
+                                                               self.inv_cov))
+        return s
+
+    @staticmethod
+    def read(path):
+        lib = host_lib()
+        s = HostFullModelStruct()
+        _check(lib.ghmm_hmm_read_full(os.fsencode(path), C.byref(s)), lib)
+        N, M, D = s.N, s.M, s.D
+        hm = HostFullModel(np.ctypeslib.as_array(s.A, (N, N)).copy(),
+                           np.ctypeslib.as_array(s.c, (N, M)).copy(),
+                           np.ctypeslib.as_array(s.mean, (N, M, D)).copy(),
+                           np.ctypeslib.as_array(s.inv_cov, (N, M, D, D)).copy(),
+                           np.ctypeslib.as_array(s.det, (N, M)).copy(), s.word.decode())
+        lib.ghmm_host_fmodel_free(C.byref(s))
+        return hm
+
+    def write(self, path, len_bytes=8):
+        lib = host_lib()
+        s = self._struct()
+        _check(lib.ghmm_hmm_write_full(os.fsencode(path), C.byref(s), len_bytes), lib)
 
 
 def perfil_read(path):
@@ -488,6 +554,28 @@ class Context:
         _check(self.lib.ghmm_score_streams(self.h, pm, pc, P, _d(out)), self.lib)
         return out
 
+    # ---- the full-covariance recogniser
+    def full_model(self, hfm):
+        return FullModel(self, hfm)
+
+    def emission_full(self, fmodel, corpus):
+        """b[F][N] into the workspace (fetch(BUF_B, (frames, N)))"""
+        _check(self.lib.ghmm_emission_full(self.h, fmodel.h, corpus.h), self.lib)
+
+    def score_full(self, fmodel, corpus):
+        """RC's log P per utterance: -sum_t log c_t (no final-state term)"""
+        out = np.empty(corpus.n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_score_full(self.h, fmodel.h, corpus.h, _d(out)), self.lib)
+        return out
+
+    def score_full_batch(self, fmodels, corpus):
+        """RC:326-374 for a whole vocabulary: out[k, u] = log P(utterance u | model k)."""
+        arr = (_vp * len(fmodels))(*[m.h for m in fmodels])
+        out = np.empty((len(fmodels), corpus.n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_score_full_batch(self.h, arr, len(fmodels), corpus.h, _d(out)),
+               self.lib)
+        return out
+
     def viterbi(self, model, corpus):
         path = np.empty(corpus.frames, dtype=np.int32)
         score = np.empty(corpus.n_utt, dtype=np.float64)
@@ -529,6 +617,40 @@ class Model:
     def close(self):
         if self.h:
             self.ctx.lib.ghmm_model_destroy(self.ctx.h, self.h)
+            self.h = None
+
+
+class FullModel:
+    """Device-resident full-covariance model (ghmm_fmodel)."""
+
+    def __init__(self, ctx, hfm):
+        self.ctx, self.N, self.M, self.D = ctx, hfm.N, hfm.M, hfm.D
+        h = _vp()
+        _check(ctx.lib.ghmm_fmodel_create(ctx.h, hfm.N, hfm.M, hfm.D, C.byref(h)), ctx.lib)
+        self.h = h
+        ctx._children.append(self)
+        self.set(hfm)
+
+    def set(self, hfm):
+        _check(self.ctx.lib.ghmm_fmodel_set(self.ctx.h, self.h, *(_d(x) for x in hfm.arrays())),
+               self.ctx.lib)
+
+    def get(self):
+        N, M, D = self.N, self.M, self.D
+        A = np.empty((N, N)); c = np.empty((N, M)); mu = np.empty((N, M, D))
+        ic = np.empty((N, M, D, D)); det = np.empty((N, M))
+        _check(self.ctx.lib.ghmm_fmodel_get(self.ctx.h, self.h, _d(A), _d(c), _d(mu), _d(ic),
+                                            _d(det)), self.ctx.lib)
+        return HostFullModel(A, c, mu, ic, det)
+
+    def dims(self):
+        n, m, d = C.c_int(), C.c_int(), C.c_int()
+        _check(self.ctx.lib.ghmm_fmodel_dims(self.h, C.byref(n), C.byref(m), C.byref(d)), self.ctx.lib)
+        return n.value, m.value, d.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.ghmm_fmodel_destroy(self.ctx.h, self.h)
             self.h = None
 
 
