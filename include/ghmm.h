@@ -326,6 +326,32 @@ int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *logl
 int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                           double *loglik_host);
 
+/* -------------------------------------------- the full-covariance trainer */
+
+/* TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c, the reference's full-covariance trainer
+ * (the one that wrote the models RC reads).  One feature stream, on a ghmm_fmodel, whose caps hold:
+ * 1 <= N <= 64, M >= 1, 1 <= D <= 48.  GHMM_OPT_ROBUST is refused with GHMM_ERR_UNSUPPORTED.
+ * Statistics vector of the full-covariance layout, in doubles (G = N*M, DT = D(D+1)/2):
+ *   num_a[N*N]  den_a[N]  den_c[N]        TFF:1601-1660 (the diagonal trainer's sums)
+ *   num_c[G]  num_mu[G*D]                  TFF:1740-1744
+ *   num_cov[G*DT]                          TFF:1748-1750, upper triangle k <= l, row-major, around
+ *                                          the OLD mean
+ *   loglik  n_utt                          TFF:299-300
+ * Being flat like the diagonal one, ghmm_stats_download / _upload / _loglik / _allreduce take it as
+ * they are; the diagonal calls (ghmm_estep, ghmm_mstep, ...) refuse it. */
+size_t ghmm_stats_len_full(int N, int M, int D);
+int ghmm_stats_create_full(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats **out);
+/* One E-step over the whole corpus (TFF:254-301): calc_symbol_probab + calc_gaus with the mixture
+ * posteriors (TFF:1775-1887: densities of +inf become 1e20, post = c*gaus / b or 0 where b == 0),
+ * the diagonal trainer's recursions on fm's A with the final-state term in log P, then
+ * calc_mix_param (TFF:1714-1753) and an ordered reduction into `stats` (overwritten; bitwise
+ * reproducible).  Afterwards ghmm_fetch(GHMM_BUF_B / _POST / _GAMMA ...) returns the trainer's
+ * arrays.  Asynchronous on the context's stream. */
+int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *stats);
+/* The M-step (TFF:306-341): downloads the statistics and the model, applies ghmm_mstep_full_host
+ * with GHMM_OPT_DELTA, and sets the model again.  Synchronises. */
+int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
+
 /* -------------------------------------- several GPUs: the one collective */
 
 /* Utterances shard data-parallel over ranks (one rank = one process or host thread with
@@ -425,6 +451,27 @@ int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_b
  * on utterances already in host memory.  Host code. */
 int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
                     ghmm_host_model *hm);
+
+/* The full-covariance trainer's host side (TFF, see ghmm_estep_full), in the reference's order of
+ * operations.  The matrix slot inv_cov of a Gaussian is TFF's cov_matrix: normally the inverse covariance. */
+/* creating_initial_model (TFF:731-1134): uniform segmentation, LBG splitting x1.05 / x0.95 (the
+ * split of the cells of largest distortion and the re-seeding of empty cells: x1.005 / x0.995),
+ * five nearest-mean passes, the full covariance of each cell around its mean (diagonal floored at
+ * 1e-5, mirrored), inverse and det by inv_cov_matrix (D = 1: det = var, inverse = 1 / var),
+ * weights floored and renormalised; one-step left-to-right A. */
+int ghmm_init_model_full(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
+                         ghmm_host_fmodel *hfm);
+/* The M-step of main (TFF:306-341) on a full statistics vector: updating_transition_probab
+ * (TFF:1907-1929, inside the band i <= j <= i + delta), updating_mix_param (TFF:1951-2000) with
+ * changing_zero_coef, inv_cov_matrix per Gaussian (TFF:2164-2202) and, for D > 1, treat_zero_det
+ * per state (TFF:2226-2265).  The reference's quirks are kept: a state with den_c == 0 keeps its
+ * matrix slot (an inverse) and has it inverted again; num_c == 0 gives 0/0 means; det == 0 (NaN
+ * det included) leaves the matrix un-inverted; with M = 1 treat_zero_det splits a Gaussian with
+ * itself (mean x0.9975, weight unchanged). */
+int ghmm_mstep_full_host(const double *stats, int delta, ghmm_host_fmodel *hfm);
+/* inv_cov_matrix (TFF:2164-2202) alone: LDL' decomposition, det = prod of the pivots (NaN -> 0),
+ * cov[D*D] replaced by its inverse unless det == 0.  Returns det; 1 <= D <= 64. */
+double ghmm_inv_cov_full(int D, double *cov);
 
 /* -------------------------------------------- host side: synthetic corpora */
 

@@ -201,6 +201,7 @@ struct ghmm_stats {
     long long mbox_expect = 0;
     long long mbox_mark = 0; // ctx->launch_mark when the k_reduce_all that fills it was enqueued
     bool mbox_valid = false;
+    bool full = false; // the full-covariance layout (ghmm_stats_create_full): diagonal calls refuse it
 };
 
 static const char *k_names[GHMM_K_COUNT] = {"emission", "forward", "backward", "mixstats",
@@ -881,7 +882,7 @@ extern "C" size_t ghmm_stats_len(int N, int M, int D)
     return (size_t)N * N + 2 * (size_t)N + (size_t)N * M * (2 * (size_t)D + 1) + 2;
 }
 
-extern "C" int ghmm_stats_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats **out)
+static int stats_make(ghmm_ctx *ctx, int N, int M, int D, bool full, ghmm_stats **out)
 {
     int rc = use(ctx);
     if (rc) return rc;
@@ -889,7 +890,8 @@ extern "C" int ghmm_stats_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats 
     ghmm_stats *s = new (std::nothrow) ghmm_stats();
     if (!s) return GHMM_ERR_ALLOC;
     s->N = N; s->M = M; s->D = D;
-    s->n = ghmm_stats_len(N, M, D);
+    s->full = full;
+    s->n = full ? ghmm_stats_len_full(N, M, D) : ghmm_stats_len(N, M, D);
     s->own = true;
     if ((rc = dev_alloc(&s->v, s->n))) {
         delete s;
@@ -924,6 +926,16 @@ extern "C" int ghmm_stats_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats 
     }
     *out = s;
     return GHMM_OK;
+}
+
+extern "C" int ghmm_stats_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats **out)
+{
+    return stats_make(ctx, N, M, D, false, out);
+}
+
+extern "C" int ghmm_stats_create_full(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats **out)
+{
+    return stats_make(ctx, N, M, D, true, out);
 }
 
 extern "C" int ghmm_stats_wrap(ghmm_ctx *ctx, int N, int M, int D, double *dev_ptr, ghmm_stats **out)
@@ -1695,7 +1707,7 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
 
 static int check_stats(const ghmm_model *m, const ghmm_stats *s)
 {
-    if (!s || s->N != m->N || s->M != m->M || s->D != m->D) {
+    if (!s || s->N != m->N || s->M != m->M || s->D != m->D || s->full) {
         ghmm_set_error("statistics vector does not match the model's shape");
         return GHMM_ERR_ARG;
     }
@@ -2267,6 +2279,10 @@ struct ghmm_fmodel {
     int N = 0, M = 0, D = 0;
     double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
     double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
+    // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
+    // run_scan_combine): N, and A (aliases the A above, owned there) with its band flag.  Nothing
+    // else of it is set; it is never passed to ghmm_model_destroy.
+    ghmm_model rec;
 };
 
 // any N (the concatenated vocabulary of ghmm_score_full_batch has hundreds of states)
@@ -2275,6 +2291,7 @@ static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
     ghmm_fmodel *fm = new (std::nothrow) ghmm_fmodel();
     if (!fm) return GHMM_ERR_ALLOC;
     fm->N = N; fm->M = M; fm->D = D;
+    fm->rec.N = N; fm->rec.M = M; fm->rec.D = D;
     const size_t G = (size_t)N * M;
     // mean and inv_cov with FC_SLACK doubles behind them: the kernel's padded columns read there
     const size_t nmean = G * D + FC_SLACK, ncov = G * D * D + FC_SLACK;
@@ -2285,6 +2302,7 @@ static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
         ghmm_fmodel_destroy(ctx, fm);
         return rc;
     }
+    fm->rec.A = fm->A;
     if (hipMemsetAsync(fm->mean, 0, nmean * 8, ctx->stream) != hipSuccess ||
         hipMemsetAsync(fm->inv_cov, 0, ncov * 8, ctx->stream) != hipSuccess) {
         ghmm_fmodel_destroy(ctx, fm);
@@ -2313,6 +2331,7 @@ extern "C" int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmode
 extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
 {
     if (!fm) return;
+    if (ctx && ctx->last_m == &fm->rec) ctx->last_m = nullptr;
     if (ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
@@ -2327,9 +2346,14 @@ extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, 
                                const double *mean, const double *inv_cov, const double *det)
 {
     int rc = use(ctx);
+    if (ctx && fm && ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
     if (rc) return rc;
     ARG_CHECK(fm && A && c && mean && inv_cov && det, "null argument");
     const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
+    fm->rec.banded = true; // (as ghmm_model_set decides it: the paired scans' band-diagonal forms)
+    for (int i = 0; i < fm->N; i++)
+        for (int j = 0; j < fm->N; j++)
+            if (A[(size_t)i * fm->N + j] != 0.0 && j != i && j != i + 1) fm->rec.banded = false;
     // calc_gaus's normaliser as the reference forms it: aux1 = pow(2 pi, D/2.0), aux2 = pow(|det|, 0.5)
     std::vector<double> den(G);
     const double aux1 = pow(2.0 * M_PI, fm->D / 2.0);
@@ -2407,7 +2431,7 @@ static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
     return GHMM_OK;
 }
 
-static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, bool want_post = false)
 {
     // the workspace now holds densities no diagonal model owns: the row API refuses them
     // (need_emission), and alpha^ / W / log P of an earlier pass no longer go with b
@@ -2427,8 +2451,14 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
     const int DB = (fm->D + 7) / 8 * 8;
     kscope ks(ctx, GHMM_K_EMISSION);
 #define GHMM_FCK(DBV)                                                                                         \
-    hipLaunchKernelGGL(k_emission_full<DBV>, grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M, fm->D, \
-                       c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b)
+    do {                                                                                                      \
+        if (want_post)                                                                                        \
+            hipLaunchKernelGGL((k_emission_full<DBV, true>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, \
+                               fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, ctx->post); \
+        else                                                                                                  \
+            hipLaunchKernelGGL(k_emission_full<DBV>, grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M, \
+                               fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, (double *)nullptr); \
+    } while (0)
     switch (DB) {
     case 8: GHMM_FCK(8); break;
     case 16: GHMM_FCK(16); break;
@@ -2539,6 +2569,109 @@ extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, 
                            ctx->stream));
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
+}
+
+// ------------------------------------------------ the full-covariance trainer (TFF)
+
+static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)
+{
+    if (!s || !s->full || s->N != fm->N || s->M != fm->M || s->D != fm->D) {
+        ghmm_set_error("statistics vector is not a full-covariance one of the model's shape "
+                       "(ghmm_stats_create_full)");
+        return GHMM_ERR_ARG;
+    }
+    return GHMM_OK;
+}
+
+// calc_mix_param over every frame (k_fullstats), the ordered reduction of its partials, and the
+// utterance sums (num_a, den_a, den_c, log P, count) by k_reduce_all without its Gaussian blocks
+static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, D1 = D + 1;
+    const long long E = (long long)G * fs_elems(D);
+    const int NB = (int)((E + FS_THREADS * FS_EPT - 1) / (FS_THREADS * FS_EPT));
+    int rc;
+    // frame-block partials: about four blocks per CU in all, as k_mixstats
+    long long P = ctx->partials > 0 ? ctx->partials : (4LL * ctx->cus + NB - 1) / NB;
+    if (P < 1) P = 1;
+    int GWmax = (FS_THREADS * FS_EPT) / fs_elems(D) + 2;
+    if (GWmax > G) GWmax = G;
+    int FSn = FS_FRAMES;
+    while (FSn > 1 && (size_t)FSn * (D1 + GWmax) * sizeof(double) > 48 * 1024) FSn /= 2;
+    const size_t lds = (size_t)FSn * (D1 + GWmax) * sizeof(double);
+    long long fpb = (c->F + P - 1) / P;
+    fpb = ((fpb + FSn - 1) / FSn) * FSn;
+    if (fpb < FSn) fpb = FSn;
+    P = c->F > 0 ? (c->F + fpb - 1) / fpb : 0;
+    double *stats_c = s->v + (size_t)N * N + 2 * (size_t)N;
+    if (P > 0) {
+        if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, (size_t)P * (size_t)E))) return rc;
+        kscope ks(ctx, GHMM_K_MIXSTATS);
+        hipLaunchKernelGGL(k_fullstats, dim3((unsigned)P, (unsigned)NB), dim3(FS_THREADS), lds, ctx->stream, N, M, D,
+                           c->F, fpb, FSn, c->X, ctx->gamma, ctx->post, fm->mean, ctx->part_mu);
+        if ((rc = launch_ok("k_fullstats"))) return rc;
+    }
+    {
+        kscope ks(ctx, GHMM_K_REDUCE);
+        hipLaunchKernelGGL(k_fullstats_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, G, D,
+                           (int)P, (const double *)ctx->part_mu, stats_c);
+        if ((rc = launch_ok("k_fullstats_reduce"))) return rc;
+        reduce_args ra{};
+        ra.N = N; ra.M = M; ra.D = D; ra.U = c->U; ra.delta = (int)ctx->delta;
+        ra.S = ctx->slots;
+        ra.lpart = ctx->loglik_pieces ? ctx->lpart : nullptr;
+        ra.logk = ctx->logk;
+        ra.part_xi = ctx->part_xi; ra.part_dena = ctx->part_dena; ra.part_denc = ctx->part_denc;
+        ra.loglik = ctx->loglik; ra.stats = s->v;
+        ra.no_mix = 1;
+        ra.tail = s->v + (s->n - 2);
+        ra.mbox = (s->mbox_slot >= 0 && ctx->mbox_page_dev) ? ctx->mbox_page_dev + 4 * s->mbox_slot : nullptr;
+        ra.mbox_seq = ++ctx->mbox_seq;
+        s->mbox_expect = ra.mbox_seq;
+        s->mbox_mark = ctx->launch_mark;
+        s->mbox_valid = ra.mbox != nullptr;
+        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)(N * N + 2 * N + 1)), dim3(RD_THREADS), 0, ctx->stream, ra);
+    }
+    return launch_ok("k_reduce_all");
+}
+
+extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
+    ghmm_model *rm = &fm->rec;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, rm, c))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, true))) return rc;
+    // calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
+    // diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this
+    // model's A and the densities above
+    bool fused = false;
+    if ((rc = run_scan_combine(ctx, rm, c, &fused))) return rc;
+    if (!fused) {
+        if ((rc = run_forward(ctx, rm, c, true))) return rc;
+        if ((rc = run_backward(ctx, rm, c, false))) return rc;
+    }
+    return run_fullstats(ctx, fm, c, s);
+}
+
+extern "C" int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    if ((rc = check_stats_full(fm, s))) return rc;
+    std::vector<double> v(s->n);
+    if ((rc = ghmm_stats_download(ctx, s, v.data()))) return rc;
+    ghmm_host_fmodel h;
+    memset(&h, 0, sizeof h);
+    if ((rc = ghmm_host_fmodel_alloc(&h, fm->N, fm->M, fm->D))) return rc;
+    if (!(rc = ghmm_fmodel_get(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det)) &&
+        !(rc = ghmm_mstep_full_host(v.data(), (int)ctx->delta, &h)))
+        rc = ghmm_fmodel_set(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det);
+    ghmm_host_fmodel_free(&h);
+    return rc;
 }
 
 extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,

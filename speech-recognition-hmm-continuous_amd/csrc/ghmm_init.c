@@ -30,10 +30,15 @@
 #define SPLIT_DOWN 0.995
 #define KMEANS_PASSES 3    /* TF:1043 */
 
+/* shared with ghmm_fulltrain.c (not part of the C ABI) */
+double ghmm_nearest_(const double *x, const double *cells, int n_cells, int D, int *cell);
+int ghmm_init_cells_(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
+                     double first_up, double first_down, int passes, double *cells);
+
 /* nearest cell by squared Euclidean distance; strict '<' so ties keep the lowest
    cell, start value 1e20 as in TF:1179-1215 (a frame farther than that from
    every cell keeps the previous frame's cell) */
-static double nearest(const double *x, const double *cells, int n_cells, int D, int *cell)
+double ghmm_nearest_(const double *x, const double *cells, int n_cells, int D, int *cell)
 {
     double best = 1.0e20;
     for (int i = 0; i < n_cells; i++) {
@@ -68,10 +73,10 @@ static void order_desc(const double *key, int *idx, int n)
     }
 }
 
-static void split_cell(double *cells, int from, int to, int D)
+static void split_cell(double *cells, int from, int to, int D, double up, double down)
 {
-    for (int l = 0; l < D; l++) cells[(size_t)to * D + l] = cells[(size_t)from * D + l] * SPLIT_UP;
-    for (int l = 0; l < D; l++) cells[(size_t)from * D + l] = cells[(size_t)from * D + l] * SPLIT_DOWN;
+    for (int l = 0; l < D; l++) cells[(size_t)to * D + l] = cells[(size_t)from * D + l] * up;
+    for (int l = 0; l < D; l++) cells[(size_t)from * D + l] = cells[(size_t)from * D + l] * down;
 }
 
 /* run [begin,end) of state k in an utterance of T frames */
@@ -82,36 +87,22 @@ static void run_of(int T, int N, int k, int *begin, int *end)
     *end = *begin + q + (k < r ? 1 : 0);
 }
 
-int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
-                    ghmm_host_model *hm)
+/* the cell means of every state: uniform segmentation, LBG splitting and nearest-mean passes.
+   cells[N][M][D] must be zeroed; the doubling split multiplies by (first_up, first_down), the
+   split of the cells of largest distortion and the re-seeding of empty cells by
+   (SPLIT_UP, SPLIT_DOWN).  Shared with the full-covariance trainer's init (ghmm_fulltrain.c). */
+int ghmm_init_cells_(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
+                     double first_up, double first_down, int passes, double *cells)
 {
-    if (!X || !len || n_utt <= 0 || N <= 0 || M <= 0 || D <= 0 || !hm) return GHMM_ERR_ARG;
-    int rc = ghmm_host_model_alloc(hm, N, M, D);
-    if (rc) return rc;
-
-    /* transition matrix */
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++) {
-            double a;
-            if (j > INIT_DELTA + i || j < i) a = 0.0;
-            else if (INIT_DELTA + 1 > N - i) a = 1.0 / (double)(N - i);
-            else a = 1.0 / (double)(INIT_DELTA + 1);
-            hm->A[(size_t)i * N + j] = a;
-        }
-
     size_t cellsz = (size_t)M * D;
-    double *cells = (double *)calloc((size_t)N * cellsz, sizeof(double)); /* [N][M][D] */
     double *sum = (double *)calloc((size_t)N * cellsz, sizeof(double));
     double *dist = (double *)calloc((size_t)N * M, sizeof(double));
     int *count = (int *)calloc((size_t)N * M, sizeof(int));
     int *idx = (int *)calloc((size_t)M, sizeof(int));
-    int *dur = (int *)calloc((size_t)N, sizeof(int));
-    if (!cells || !sum || !dist || !count || !idx || !dur) {
-        free(cells); free(sum); free(dist); free(count); free(idx); free(dur);
-        ghmm_host_model_free(hm);
+    if (!sum || !dist || !count || !idx) {
+        free(sum); free(dist); free(count); free(idx);
         return GHMM_ERR_ALLOC;
     }
-
     /* one cell per state: mean of the state's frames */
     {
         size_t f0 = 0;
@@ -139,16 +130,16 @@ int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M
         for (int k = 0; k < N; k++) {
             double *ck = cells + (size_t)k * cellsz;
             if (2 * n_cells < M) {
-                for (int i = 0; i < n_cells; i++) split_cell(ck, i, n_cells + i, D);
+                for (int i = 0; i < n_cells; i++) split_cell(ck, i, n_cells + i, D, first_up, first_down);
             } else {
                 order_desc(dist + (size_t)k * M, idx, n_cells);
-                for (int i = 0; i < M - n_cells; i++) split_cell(ck, idx[i], n_cells + i, D);
+                for (int i = 0; i < M - n_cells; i++) split_cell(ck, idx[i], n_cells + i, D, SPLIT_UP, SPLIT_DOWN);
             }
         }
         next = (2 * n_cells < M) ? 2 * n_cells : M;
         n_cells = next;
 
-        for (int pass = 0; pass < KMEANS_PASSES; pass++) {
+        for (int pass = 0; pass < passes; pass++) {
             for (int k = 0; k < N; k++)
                 for (int i = 0; i < n_cells; i++) {
                     count[k * M + i] = 0;
@@ -166,7 +157,7 @@ int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M
                         /* TF:1076 `distortion[k][index] += classifying(..,&index)` is
                            unsequenced in C; gcc calls first and indexes with the
                            new cell, which is what is done here */
-                        double d = nearest(x, cells + (size_t)k * cellsz, n_cells, D, &cell);
+                        double d = ghmm_nearest_(x, cells + (size_t)k * cellsz, n_cells, D, &cell);
                         dist[(size_t)k * M + cell] += d;
                         count[k * M + cell]++;
                         for (int l = 0; l < D; l++) sum[(size_t)k * cellsz + (size_t)cell * D + l] += x[l];
@@ -182,9 +173,41 @@ int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M
                 order_desc(dist + (size_t)k * M, idx, n_cells);
                 int i = 0;
                 for (int j = 0; j < n_cells; j++)
-                    if (count[k * M + j] == 0) split_cell(ck, idx[i++], j, D);
+                    if (count[k * M + j] == 0) split_cell(ck, idx[i++], j, D, SPLIT_UP, SPLIT_DOWN);
             }
         }
+    }
+
+    free(sum); free(dist); free(count); free(idx);
+    return GHMM_OK;
+}
+
+int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M, int D,
+                    ghmm_host_model *hm)
+{
+    if (!X || !len || n_utt <= 0 || N <= 0 || M <= 0 || D <= 0 || !hm) return GHMM_ERR_ARG;
+    int rc = ghmm_host_model_alloc(hm, N, M, D);
+    if (rc) return rc;
+
+    /* transition matrix */
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++) {
+            double a;
+            if (j > INIT_DELTA + i || j < i) a = 0.0;
+            else if (INIT_DELTA + 1 > N - i) a = 1.0 / (double)(N - i);
+            else a = 1.0 / (double)(INIT_DELTA + 1);
+            hm->A[(size_t)i * N + j] = a;
+        }
+
+    size_t cellsz = (size_t)M * D;
+    double *cells = (double *)calloc((size_t)N * cellsz, sizeof(double)); /* [N][M][D] */
+    int *count = (int *)calloc((size_t)N * M, sizeof(int));
+    int *dur = (int *)calloc((size_t)N, sizeof(int));
+    if (!cells || !count || !dur ||
+        ghmm_init_cells_(X, len, n_utt, N, M, D, SPLIT_UP, SPLIT_DOWN, KMEANS_PASSES, cells) != GHMM_OK) {
+        free(cells); free(count); free(dur);
+        ghmm_host_model_free(hm);
+        return GHMM_ERR_ALLOC;
     }
 
     /* per-cell variance and weight */
@@ -198,7 +221,7 @@ int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M
                 run_of(len[u], N, k, &b, &e);
                 for (int j = b; j < e; j++) {
                     const double *x = X + (f0 + (size_t)j) * D;
-                    nearest(x, cells + (size_t)k * cellsz, M, D, &cell);
+                    ghmm_nearest_(x, cells + (size_t)k * cellsz, M, D, &cell);
                     size_t g = (size_t)k * M + cell;
                     for (int l = 0; l < D; l++) {
                         double a = x[l] - cells[g * D + l];
@@ -234,6 +257,6 @@ int ghmm_init_model(const double *X, const int32_t *len, int n_utt, int N, int M
         for (int j = 0; j < M; j++) c[j] /= s;
     }
 
-    free(cells); free(sum); free(dist); free(count); free(idx); free(dur);
+    free(cells); free(count); free(dur);
     return GHMM_OK;
 }

@@ -1015,6 +1015,10 @@ struct reduce_args {
     long long F;
     double kappa; // relative rounding bound of the expanded sums (accumulation length x eps)
     double *stats;
+    // the full-covariance trainer (ghmm_estep_full): no_mix = 1 leaves out the per-Gaussian blocks
+    // (k_fullstats_reduce writes those sums); tail = where (loglik, n_utt) go (nullptr: behind num_var)
+    int no_mix = 0;
+    double *tail = nullptr;
 };
 
 __global__ void __launch_bounds__(RD_THREADS) k_reduce_all(reduce_args a)
@@ -1022,7 +1026,7 @@ __global__ void __launch_bounds__(RD_THREADS) k_reduce_all(reduce_args a)
     __shared__ double sh[RD_THREADS];
     __shared__ double sh2[RD_THREADS];
     const int N = a.N, M = a.M, D = a.D, G = N * M, D1 = D + 1;
-    const int NG = a.Pm > 0 ? a.NT * 16 : G;
+    const int NG = a.no_mix ? 0 : (a.Pm > 0 ? a.NT * 16 : G);
     const int tid = threadIdx.x;
     double *num_a = a.stats, *den_a = num_a + (size_t)N * N, *den_c = den_a + N;
     double *num_c = den_c + N, *num_mu = num_c + G, *num_var = num_mu + (size_t)G * D;
@@ -1216,8 +1220,9 @@ __global__ void __launch_bounds__(RD_THREADS) k_reduce_all(reduce_args a)
         }
         v = block_sum_fixed(v, sh);
         if (tid == 0) {
-            num_var[(size_t)G * D] = v;            // loglik
-            num_var[(size_t)G * D + 1] = (double)U; // n_utt
+            double *tail = a.tail ? a.tail : num_var + (size_t)G * D;
+            tail[0] = v;           // loglik
+            tail[1] = (double)U;   // n_utt
             if (a.mbox) {
                 __hip_atomic_store(a.mbox, __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(a.mbox + 1, __double_as_longlong((double)U), __ATOMIC_RELAXED,

@@ -13,6 +13,13 @@
  *   - [initial_model] works (the reference reads argv[argc], a NULL, TF:218);
  *   - no MAX_* capacity limits (up to GHMM_MAX_STREAMS = 8 feature streams).
  *
+ * Built with -DGHMM_FULL_COV it is bin/hmm-continuous-train-full-fs, the full-covariance trainer
+ * (TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c, main TFF:106-378): same argv, usage
+ * text, stopping rule and report, one feature stream.  The initial model is built on the host
+ * (ghmm_init_model_full) or read with ghmm_hmm_read_full, each iteration is ghmm_estep_full on the
+ * GPU and ghmm_mstep_full, and the model is written with ghmm_hmm_write_full (8-byte prefix).
+ * P > 1 and GHMM_WORLD > 1 are refused.
+ *
  * Several GPUs: start one process per GPU with
  *     GHMM_WORLD=<ranks> GHMM_RANK=<0..ranks-1> GHMM_COMM_ID=<a path unique to the job>
  *     [GHMM_DEVICE=<gpu index, default = rank>]
@@ -48,6 +55,20 @@ static int env_int(const char *name, int dflt)
 
 static void usage(void)
 {
+#ifdef GHMM_FULL_COV
+    /* TFF:166-175 */
+    puts("Usage: hmm_continuous_full_fs word states_number param_number mix_number1 ... mix_numberN  input_file1 ... input_fileN output_file [initial_model]");
+    puts("word: word that will be represented by the model");
+    puts("states_number: number of states");
+    puts("param_number: number of parameters to train the model");
+    puts("mix_number1: number of mixtures per state (parameter 1)");
+    puts("mix_numberN: number of mixtures per state (parameter N)");
+    puts("input_file1: name of file with names of files with parameters 1");
+    puts("input_fileN: name of file with names of files with parameters N");
+    puts("output_file: output file name");
+    puts("initial_model: name of initial model, if there is one");
+    exit(1);
+#endif
     puts("Usage: hmm_continuous_fs word states_number param_number mix_number1 ... mix_numberN  input_file1 ... input_fileN output_file [initial_model]");
     puts("word: word that will be represented by the model");
     puts("states_number: number of states");
@@ -73,9 +94,117 @@ static void report_name(const char *model, char *out, size_t n)
     strncat(out, ".txt", n - strlen(out) - 1);
 }
 
+/* report lines of writing_text, TF:2189-2259 / TFF:2421-2527, with the cpu time exactly as the
+   reference formats it (TF:364-369; its /60 assumes 60 ticks/s) */
+static void write_report(const char *text_file, const char *first_line, const char *output, const char *word,
+                         int N, int P, const int *M, const char *const *list, int n_utt, double probab,
+                         int iteration, const char *t_start)
+{
+    char t_end[64], t_cpu[64];
+    struct tms tm_cpu;
+    times(&tm_cpu);
+    time_t cpu = (time_t)(int)(tm_cpu.tms_utime / 60.0);
+    struct tm *g = gmtime(&cpu);
+    g->tm_mday -= 1;
+    strftime(t_cpu, sizeof t_cpu, "%d %X", g);
+    time_t now;
+    time(&now);
+    strftime(t_end, sizeof t_end, "%d-%h-%Y %X", localtime(&now));
+
+    FILE *ft = fopen(text_file, "w");
+    if (!ft) {
+        printf("can't open file %s \n", text_file);
+        exit(1);
+    }
+    fprintf(ft, "%s\n", first_line);
+    fprintf(ft, "model file: %s \n", output);
+    fprintf(ft, "word: %s \n", word);
+    fprintf(ft, "number of states: %d \n", N);
+    fprintf(ft, "number of parameters: %d \n", P);
+    for (int p = 0; p < P; p++) fprintf(ft, "number of mixtures %d: %d \n", p + 1, M[p]);
+    for (int p = 0; p < P; p++) fprintf(ft, "parameter %d: %s \n", p + 1, list[p]);
+    fprintf(ft, "threshould to finish training: %f \n", THRESHOLD);
+    fprintf(ft, "number of exemplars in training sequence: %d \n", n_utt);
+    fprintf(ft, "mean probability: %f \n", probab);
+    fprintf(ft, "number of iterations: %d \n", iteration);
+    fprintf(ft, "starting time: %s \n", t_start);
+    fprintf(ft, "ending time: %s \n", t_end);
+    fprintf(ft, "cpu time: %s \n", t_cpu);
+    if (ferror(ft) || fclose(ft) != 0) {
+        printf("writing error on file %s \n", text_file);
+        exit(1);
+    }
+}
+
+#ifdef GHMM_FULL_COV
+/* main's EM loop of TFF (TFF:202-376) over the utterances already in memory */
+static int train_full(const char *word, int N, int M, int D, const double *X, const int32_t *len, int n_utt,
+                      size_t frames, const char *initial, const char *output, const char *list,
+                      const char *text_file, const char *t_start, int device)
+{
+    ghmm_host_fmodel hfm;
+    memset(&hfm, 0, sizeof hfm);
+    int rc;
+    if (initial) {
+        if ((rc = ghmm_hmm_read_full(initial, &hfm))) die("initial model", rc);
+        if (hfm.D != D) {
+            printf("initial model %s has %d coefficients, data has %d \n", initial, hfm.D, D);
+            exit(1);
+        }
+        N = hfm.N;
+        M = hfm.M;
+    } else if ((rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) {
+        die("creating initial model", rc);
+    }
+    snprintf(hfm.word, sizeof hfm.word, "%s", word);
+    ghmm_ctx *ctx;
+    ghmm_fmodel *fm;
+    ghmm_corpus *corpus;
+    ghmm_stats *stats;
+    if ((rc = ghmm_ctx_create(device, NULL, &ctx))) die("GPU context", rc);
+    if ((rc = ghmm_corpus_create(ctx, X, len, n_utt, D, &corpus))) die("corpus", rc);
+    if ((rc = ghmm_fmodel_create(ctx, N, M, D, &fm))) die("model", rc);
+    if ((rc = ghmm_fmodel_set(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
+    if ((rc = ghmm_stats_create_full(ctx, N, M, D, &stats))) die("statistics", rc);
+    double lp[2] = {0.0, 0.0};
+
+    printf("\r\nCreating HMM using Forward-Backward algorithm (Baum-Welch)");
+    double probab, old_probab = 1.0, variation; /* TFF:135-137 */
+    int iteration = 0;
+    do {
+        iteration++;
+        printf("\r\nStarting training sequence (%d utterances, %zu frames)", n_utt, frames);
+        if ((rc = ghmm_estep_full(ctx, fm, corpus, stats))) die("E-step", rc);
+        if ((rc = ghmm_stats_loglik(ctx, stats, lp))) die("E-step", rc);
+        probab = lp[0];
+        printf("\r\nEnding training sequence");
+        variation = fabs((old_probab - probab) / old_probab);
+        printf("\r\nVerifying Probability: %f > Threshold: %f", variation, THRESHOLD);
+        if (variation > THRESHOLD) {
+            old_probab = probab;
+            if ((rc = ghmm_mstep_full(ctx, fm, stats))) die("M-step", rc);
+        }
+    } while (variation > THRESHOLD);
+    printf("\r\nFinal Probability = %f\r\n\r\n", variation);
+    probab /= (double)n_utt;
+
+    if ((rc = ghmm_fmodel_get(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
+    if ((rc = ghmm_hmm_write_full(output, &hfm, 8))) die("writing model", rc);
+    write_report(text_file,
+                 "Continuous HMM created using Forward Backward algorithm. It is considered full covariance matrix. It is considered a final state.",
+                 output, word, N, 1, &M, &list, n_utt, probab, iteration, t_start);
+    ghmm_stats_destroy(ctx, stats);
+    ghmm_fmodel_destroy(ctx, fm);
+    ghmm_corpus_destroy(ctx, corpus);
+    ghmm_ctx_destroy(ctx);
+    ghmm_host_fmodel_free(&hfm);
+    return 0;
+}
+#endif
+
 int main(int argc, char **argv)
 {
-    char t_start[64], t_end[64], t_cpu[64], text_file[4096];
+    char t_start[64], text_file[4096];
     time_t now;
     time(&now);
     strftime(t_start, sizeof t_start, "%d-%h-%Y %X", localtime(&now));
@@ -110,6 +239,17 @@ int main(int argc, char **argv)
 
     const int world = env_int("GHMM_WORLD", 1), rank = env_int("GHMM_RANK", 0);
     const char *comm_id = getenv("GHMM_COMM_ID");
+#ifdef GHMM_FULL_COV
+    if (P != 1) {
+        printf("param_number = %d: the full-covariance trainer takes one feature stream \n", P);
+        exit(1);
+    }
+    if (world != 1) {
+        printf("GHMM_WORLD=%d: the full-covariance trainer runs on one GPU \n", world);
+        exit(1);
+    }
+    comm_id = NULL;
+#endif
     if (world < 1 || rank < 0 || rank >= world) {
         printf("GHMM_RANK=%d GHMM_WORLD=%d: bad rank layout \n", rank, world);
         exit(1);
@@ -211,6 +351,10 @@ int main(int argc, char **argv)
         free(files[p]);
     }
     free(mine);
+#ifdef GHMM_FULL_COV
+    return train_full(word, N, M[0], D[0], X[0], len, n_utt, frames, initial, output, list[0], text_file,
+                      t_start, device);
+#endif
 
     ghmm_host_model hm[GHMM_MAX_STREAMS];
     memset(hm, 0, sizeof hm);
@@ -300,43 +444,11 @@ int main(int argc, char **argv)
         if ((rc = ghmm_model_get(ctx, model[p], hm[p].A, hm[p].c, hm[p].mean, hm[p].inv_var, hm[p].det)))
             die("model", rc);
 
-    /* cpu time exactly as the reference formats it (TF:364-369; its /60 assumes 60 ticks/s) */
-    struct tms tm_cpu;
-    times(&tm_cpu);
-    time_t cpu = (time_t)(int)(tm_cpu.tms_utime / 60.0);
-    struct tm *g = gmtime(&cpu);
-    g->tm_mday -= 1;
-    strftime(t_cpu, sizeof t_cpu, "%d %X", g);
-    time(&now);
-    strftime(t_end, sizeof t_end, "%d-%h-%Y %X", localtime(&now));
-
     if (rank != 0) goto done; /* every rank holds the same model; rank 0 writes it */
     if ((rc = ghmm_hmm_write_streams(output, hm, P, 8))) die("writing model", rc);
-
-    FILE *ft = fopen(text_file, "w");
-    if (!ft) {
-        printf("can't open file %s \n", text_file);
-        exit(1);
-    }
-    /* report lines of writing_text, TF:2189-2259 */
-    fprintf(ft, "Continuous HMM created using forward backward algorithm (diagonal covariance matrix). It is considered a final state.\n");
-    fprintf(ft, "model file: %s \n", output);
-    fprintf(ft, "word: %s \n", word);
-    fprintf(ft, "number of states: %d \n", N);
-    fprintf(ft, "number of parameters: %d \n", P);
-    for (int p = 0; p < P; p++) fprintf(ft, "number of mixtures %d: %d \n", p + 1, M[p]);
-    for (int p = 0; p < P; p++) fprintf(ft, "parameter %d: %s \n", p + 1, list[p]);
-    fprintf(ft, "threshould to finish training: %f \n", THRESHOLD);
-    fprintf(ft, "number of exemplars in training sequence: %d \n", n_utt);
-    fprintf(ft, "mean probability: %f \n", probab);
-    fprintf(ft, "number of iterations: %d \n", iteration);
-    fprintf(ft, "starting time: %s \n", t_start);
-    fprintf(ft, "ending time: %s \n", t_end);
-    fprintf(ft, "cpu time: %s \n", t_cpu);
-    if (ferror(ft) || fclose(ft) != 0) {
-        printf("writing error on file %s \n", text_file);
-        exit(1);
-    }
+    write_report(text_file,
+                 "Continuous HMM created using forward backward algorithm (diagonal covariance matrix). It is considered a final state.",
+                 output, word, N, P, M, list, n_utt, probab, iteration, t_start);
 
 done:
     ghmm_comm_destroy(comm);

@@ -111,6 +111,10 @@ SYMBOLS = {
     "ghmm_emission_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_score_full": (C.c_int, [_vp, _vp, _vp, _dp], True),
     "ghmm_score_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
+    "ghmm_stats_len_full": (C.c_size_t, [C.c_int, C.c_int, C.c_int], False),
+    "ghmm_stats_create_full": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
+    "ghmm_estep_full": (C.c_int, [_vp, _vp, _vp, _vp], True),
+    "ghmm_mstep_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -135,6 +139,10 @@ SYMBOLS = {
     "ghmm_hmm_write_full": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct), C.c_int], False),
     "ghmm_init_model": (C.c_int, [_dp, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(HostModelStruct)], False),
+    "ghmm_init_model_full": (C.c_int, [_dp, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(HostFullModelStruct)], False),
+    "ghmm_mstep_full_host": (C.c_int, [_dp, C.c_int, C.POINTER(HostFullModelStruct)], False),
+    "ghmm_inv_cov_full": (C.c_double, [C.c_int, _dp], False),
     "ghmm_synth_truth": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp, _dp], False),
     "ghmm_synth_utterances": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                         C.c_int64, C.c_int, _ip, _dp], False),
@@ -290,6 +298,43 @@ class HostFullModel:
         """(A, c, mean, inv_cov, det): the argument order of ghmm_fmodel_set"""
         return self.A, self.c, self.mean, self.inv_cov, self.det
 
+    def copy(self):
+        return HostFullModel(self.A.copy(), self.c.copy(), self.mean.copy(), self.inv_cov.copy(),
+                             self.det.copy(), self.word)
+
+    @staticmethod
+    def _from_struct(s, lib):
+        N, M, D = s.N, s.M, s.D
+        hm = HostFullModel(np.ctypeslib.as_array(s.A, (N, N)).copy(),
+                           np.ctypeslib.as_array(s.c, (N, M)).copy(),
+                           np.ctypeslib.as_array(s.mean, (N, M, D)).copy(),
+                           np.ctypeslib.as_array(s.inv_cov, (N, M, D, D)).copy(),
+                           np.ctypeslib.as_array(s.det, (N, M)).copy(), s.word.decode())
+        lib.ghmm_host_fmodel_free(C.byref(s))
+        return hm
+
+    @staticmethod
+    def init_from(X, lens, N, M):
+        """creating_initial_model of the full-covariance trainer (TFF:731) on in-memory utterances
+        (ghmm_init_model_full)."""
+        lib = host_lib()
+        X = _f64(X)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        s = HostFullModelStruct()
+        _check(lib.ghmm_init_model_full(_d(X), lens.ctypes.data_as(_ip), len(lens), N, M, X.shape[1],
+                                        C.byref(s)), lib)
+        return HostFullModel._from_struct(s, lib)
+
+    def mstep(self, stats, delta=1):
+        """ghmm_mstep_full_host: the M-step of TFF (TFF:306-341) from a full statistics vector;
+        returns the new model (this one is left as it is)."""
+        lib = host_lib()
+        out = self.copy()
+        v = _f64(stats)
+        assert v.size == stats_len_full(self.N, self.M, self.D)
+        _check(lib.ghmm_mstep_full_host(_d(v), int(delta), C.byref(out._struct())), lib)
+        return out
+
     def _struct(self):
         s = HostFullModelStruct()
         s.word = self.word.encode()[:MAX_WORD - 1]
@@ -303,19 +348,20 @@ class HostFullModel:
         lib = host_lib()
         s = HostFullModelStruct()
         _check(lib.ghmm_hmm_read_full(os.fsencode(path), C.byref(s)), lib)
-        N, M, D = s.N, s.M, s.D
-        hm = HostFullModel(np.ctypeslib.as_array(s.A, (N, N)).copy(),
-                           np.ctypeslib.as_array(s.c, (N, M)).copy(),
-                           np.ctypeslib.as_array(s.mean, (N, M, D)).copy(),
-                           np.ctypeslib.as_array(s.inv_cov, (N, M, D, D)).copy(),
-                           np.ctypeslib.as_array(s.det, (N, M)).copy(), s.word.decode())
-        lib.ghmm_host_fmodel_free(C.byref(s))
-        return hm
+        return HostFullModel._from_struct(s, lib)
 
     def write(self, path, len_bytes=8):
         lib = host_lib()
         s = self._struct()
         _check(lib.ghmm_hmm_write_full(os.fsencode(path), C.byref(s), len_bytes), lib)
+
+
+def inv_cov_full(cov):
+    """ghmm_inv_cov_full (TFF's inv_cov_matrix): (det, matrix) — the inverse, or the matrix as it
+    came where det == 0"""
+    a = _f64(cov).copy()
+    det = host_lib().ghmm_inv_cov_full(a.shape[0], _d(a))
+    return det, a
 
 
 def perfil_read(path):
@@ -434,6 +480,24 @@ def split_stats(v, N, M, D):
     return out
 
 
+def stats_len_full(N, M, D):
+    return N * N + 2 * N + N * M * (1 + D + D * (D + 1) // 2) + 2
+
+
+def split_stats_full(v, N, M, D):
+    """Views into a full-covariance statistics vector (ghmm_stats_create_full); num_cov holds the
+    upper triangle (k <= l, row-major) of every Gaussian, in numpy.triu_indices(D) order."""
+    G, DT = N * M, D * (D + 1) // 2
+    o = 0
+    out = {}
+    for name, n, shape in (("num_a", N * N, (N, N)), ("den_a", N, (N,)), ("den_c", N, (N,)),
+                           ("num_c", G, (N, M)), ("num_mu", G * D, (N, M, D)),
+                           ("num_cov", G * DT, (N, M, DT)), ("loglik", 1, ()), ("n_utt", 1, ())):
+        out[name] = v[o:o + n].reshape(shape)
+        o += n
+    return out
+
+
 class Context:
     """One GPU, one stream.  `stream` = a hipStream_t as int (e.g. torch's
     torch.cuda.current_stream().cuda_stream) or None for a private stream."""
@@ -487,6 +551,10 @@ class Context:
 
     def stats(self, N, M, D, dev_ptr=None):
         return Stats(self, N, M, D, dev_ptr)
+
+    def stats_full(self, N, M, D):
+        """statistics vector of the full-covariance trainer (ghmm_stats_create_full)"""
+        return Stats(self, N, M, D, full=True)
 
     # ---- the path, row by row
     def emission(self, model, corpus, want_post=True):
@@ -575,6 +643,21 @@ class Context:
         _check(self.lib.ghmm_score_full_batch(self.h, arr, len(fmodels), corpus.h, _d(out)),
                self.lib)
         return out
+
+    # ---- the full-covariance trainer
+    @staticmethod
+    def init_model_full(X, lens, N, M):
+        """TFF's initial model (host code, ghmm_init_model_full) as a HostFullModel"""
+        return HostFullModel.init_from(X, lens, N, M)
+
+    def estep_full(self, fmodel, corpus, stats):
+        """TFF's E-step (ghmm_estep_full) into a stats_full vector; b / post / gamma stay in the
+        workspace (fetch)"""
+        _check(self.lib.ghmm_estep_full(self.h, fmodel.h, corpus.h, stats.h), self.lib)
+
+    def mstep_full(self, fmodel, stats):
+        """TFF's M-step (ghmm_mstep_full: host numerics, then the model is set again)"""
+        _check(self.lib.ghmm_mstep_full(self.h, fmodel.h, stats.h), self.lib)
 
     def viterbi(self, model, corpus):
         path = np.empty(corpus.frames, dtype=np.int32)
@@ -715,12 +798,19 @@ class Comm:
 
 
 class Stats:
-    def __init__(self, ctx, N, M, D, dev_ptr=None):
-        self.ctx, self.N, self.M, self.D = ctx, N, M, D
-        self.n = stats_len(N, M, D)
-        assert ctx.lib.ghmm_stats_len(N, M, D) == self.n
+    def __init__(self, ctx, N, M, D, dev_ptr=None, full=False):
+        self.ctx, self.N, self.M, self.D, self.full = ctx, N, M, D, full
+        if full:
+            self.n = stats_len_full(N, M, D)
+            assert ctx.lib.ghmm_stats_len_full(N, M, D) == self.n
+        else:
+            self.n = stats_len(N, M, D)
+            assert ctx.lib.ghmm_stats_len(N, M, D) == self.n
         h = _vp()
-        if dev_ptr is None:
+        if full:
+            assert dev_ptr is None, "a full-covariance statistics vector is always the library's own"
+            _check(ctx.lib.ghmm_stats_create_full(ctx.h, N, M, D, C.byref(h)), ctx.lib)
+        elif dev_ptr is None:
             _check(ctx.lib.ghmm_stats_create(ctx.h, N, M, D, C.byref(h)), ctx.lib)
         else:
             _check(ctx.lib.ghmm_stats_wrap(ctx.h, N, M, D, _vp(dev_ptr), C.byref(h)), ctx.lib)
