@@ -291,7 +291,7 @@ int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_hos
 
 /* RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c, the reference's
  * full-covariance recogniser.  A separate opaque model: nothing of the diagonal E-step,
- * M-step or Viterbi takes it.  One feature stream, 1 <= N <= 64 states, M >= 1 mixtures,
+ * M-step or Viterbi takes it (its own Viterbi is below).  One feature stream, 1 <= N <= 64 states, M >= 1 mixtures,
  * 1 <= D <= 48 coefficients (GHMM_ERR_UNSUPPORTED outside; the reference's caps are 15, 5
  * and 16).  Per Gaussian: mean[D], det (of the NON-inverted covariance) and the inverse
  * covariance inv_cov[D][D] row-major as the .hmm file stores it (RC:591-707):
@@ -305,7 +305,8 @@ int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_hos
 typedef struct ghmm_fmodel ghmm_fmodel;
 int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out);
 void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm);
-/* host -> device; also rebuilds the per-Gaussian constant pow(2 pi, D/2) * sqrt(|det|) */
+/* host -> device; also rebuilds the per-Gaussian constants den = pow(2 pi, D/2) * sqrt(|det|) and
+ * log(c) - log(den), and log A (A > 0 ? log(A) : -inf) for the Viterbi calls, all on the host */
 int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
                     const double *mean, const double *inv_cov, const double *det);
 /* device -> host (synchronises); any pointer may be NULL */
@@ -325,6 +326,27 @@ int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *logl
  * bit for bit what ghmm_score_full gives word by word.  Synchronises. */
 int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                           double *loglik_host);
+/* Viterbi decoding of full-covariance models (absent from the reference, as the diagonal Viterbi
+ * is): the diagonal definition (ghmm_viterbi, oracle/ghmm_oracle.c) with the quadratic form above.
+ *     lk = log(c) - log(den);  e_m = lk_m - aux_m / 2     (den and aux as in calc_gaus above)
+ *     log b_i(t) = m + log(sum_m exp(e_m - m)),  m = max_m e_m;  -inf when every e_m is -inf
+ * (so c == 0 gives e = -inf; det == 0 gives lk = +inf and a log b of NaN, the formula's values).
+ * In the log domain a frame far from every Gaussian keeps a finite log b where the linear densities
+ * of ghmm_score_full underflow to 0 (its score is then -inf or NaN).  The lattice is ghmm_viterbi's:
+ * one-hot start, delta_t(j) = max_i (delta_{t-1}(i) + log a_ij) + log b_j(t), ties take the lowest
+ * i, score = delta_{T-1}(N-1), path by back-pointers from state N-1; T = 0 scores 0.  The score
+ * therefore ends in the last state: it is not RC's forward score, which has no final-state term.
+ * path_host[F] = state per frame, score_host[U] = best log score; U = 0 touches neither.
+ * Afterwards ghmm_fetch(GHMM_BUF_B) returns log b[F][N].  Synchronises. */
+int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *path_host,
+                      double *score_host);
+/* The Viterbi score of every (word, utterance) pair in three launches, like ghmm_score_full_batch:
+ * the gather of the words' Gaussians, one log-emission launch over the concatenated vocabulary and
+ * one lattice launch (score only, no path).  All models share M and D.  score_host[k*U + u] is bit
+ * for bit what ghmm_viterbi_full gives word k; GHMM_BUF_B then holds log b[F][sum of N].
+ * Synchronises. */
+int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                            double *score_host);
 
 /* -------------------------------------------- the full-covariance trainer */
 

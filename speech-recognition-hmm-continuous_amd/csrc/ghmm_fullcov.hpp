@@ -22,6 +22,16 @@
 // behind the array).
 // The densities of a wave's states go to an LDS tile first and leave as rows of contiguous
 // states (b[F][NS], row-major): ordinary vector stores, 8 states = 64 bytes per frame row.
+//
+// FC_LOG is the full-covariance Viterbi's variant (ghmm_viterbi_full): log b instead of b, with
+// the diagonal Viterbi's definition (oracle/ghmm_oracle.c, orc_log_emission) on the quadratic form
+// above.  Per Gaussian e = lk - aux/2, lk = log(c) - log(den) prepared on the host like den;
+// per state log b = m + log(sum_m exp(e_m - m)), m = max_m e_m, -inf when every e is -inf.
+// The sum is taken online (one exp per Gaussian, as the linear form has): a larger e rescales the
+// running sum by exp(m_old - e) and adds 1, any other adds exp(e - m), an e of -inf adds exactly 0.
+// That is the oracle's sum up to rounding and gives its special values: an e of NaN makes the sum
+// NaN (log b NaN unless every other e is -inf, then -inf), an e of +inf (det == 0, c > 0) makes
+// m = +inf, where the oracle's exp(inf - inf) gives NaN.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,12 +41,16 @@ constexpr int FC_WAVES = 4;   // waves per block (one frame tile)
 constexpr int FC_SC = 8;      // states per wave
 constexpr int FC_DMAX = 48;   // widest feature vector built
 constexpr int FC_SLACK = 64;  // doubles allocated behind mean[] and inv_cov[] (the padded columns' reads)
+// what k_emission_full writes into b
+constexpr int FC_LIN = 0;  // the recogniser's densities (RC)
+constexpr int FC_POST = 1; // the trainer's densities and the mixture posteriors (TFF)
+constexpr int FC_LOG = 2;  // log densities for the Viterbi lattice
 
 // doubles of LDS a block needs: the frame tile and every wave's density tile
 __host__ __device__ inline int fc_lds_doubles(int D) { return WAVE * (D | 1) + FC_WAVES * WAVE * (FC_SC | 1); }
 
 //
-// POST = true is the trainer's variant (TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c,
+// MODE = FC_POST is the trainer's variant (TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c,
 // calc_symbol_probab + calc_gaus, TFF:1775-1887), which also writes the mixture posteriors
 // post[F][NS*M].  It differs from the recogniser's in two places, both reproduced:
 //   - a density of +inf becomes 1e20 (`isinf(gaus) == 1`: +inf only; a Gaussian with det == 0,
@@ -45,13 +59,14 @@ __host__ __device__ inline int fc_lds_doubles(int D) { return WAVE * (D | 1) + F
 //     divide): post = (c * gaus) / b, or 0 where b == 0.
 // The weighted densities go to post as they are formed and are divided in place once b is known
 // (each lane rereads only what it wrote itself).
-template <int DB, bool POST = false>
+template <int DB, int MODE = FC_LIN>
 __global__ void __launch_bounds__(FC_WAVES * WAVE)
 k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
                 const double *__restrict__ mean, const double *__restrict__ inv_cov,
                 const double *__restrict__ den, const double *__restrict__ c, double *__restrict__ b,
-                double *__restrict__ post)
+                double *__restrict__ post, const double *__restrict__ lk)
 {
+    constexpr bool POST = MODE == FC_POST, LOG = MODE == FC_LOG;
     extern __shared__ double lds[];
     const int DS = D | 1; // odd row stride: conflict-free per-lane reads
     const int SS = FC_SC | 1;
@@ -73,6 +88,7 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
     const double *x = xt + (lane < nf ? lane : nf - 1) * DS;
     for (int s = 0; s < ns; s++) {
         double bi = 0.0;
+        double mx = -INFINITY; // (LOG: the running maximum; bi is the sum relative to it)
         for (int m = 0; m < M; m++) {
             const size_t g = (size_t)(s0 + s) * M + m;
             const double *mu = mean + g * D;
@@ -90,7 +106,13 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
 #pragma unroll
             for (int i = 0; i < DB; i++)
                 if (i < D) aux = fma(x[i] - mu[i], t[i], aux); // (uniform branch)
-            if constexpr (POST) {
+            if constexpr (LOG) {
+                const double e = lk[g] - 0.5 * aux;
+                const bool up = e > mx; // (false for a NaN e)
+                const double r = exp(up ? mx - e : (e == -INFINITY ? -INFINITY : e - mx));
+                bi = up ? fma(bi, r, 1.0) : bi + r;
+                mx = up ? e : mx;
+            } else if constexpr (POST) {
                 double gaus = exp(aux * -0.5) / den[g];
                 if (gaus == INFINITY && den[g] != 0.0) gaus = 1e20;
                 const double gm = gaus * c[g];
@@ -101,6 +123,7 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
                 bi += gaus * c[g];
             }
         }
+        if constexpr (LOG) bi = mx == -INFINITY ? -INFINITY : mx == INFINITY ? NAN : mx + log(bi);
         if constexpr (POST) {
             if (lane < nf) {
                 double *pr = post + (f0 + lane) * ((long long)NS * M) + (long long)(s0 + s) * M;
@@ -239,19 +262,20 @@ k_fullstats_reduce(int G, int D, int P, const double *__restrict__ part, double 
     else num_cov[(size_t)g * DT + r - 1 - D] = v;
 }
 
-// ghmm_score_full_batch: word k's Gaussians (ng of them from g0) copied into the concatenated model
+// ghmm_score_full_batch / ghmm_viterbi_full_batch: word k's Gaussians (ng of them from g0) copied into the concatenated model
 struct fgather_src {
-    const double *c, *mean, *inv_cov, *den;
+    const double *c, *mean, *inv_cov, *den, *lk;
     int g0, ng;
 };
 __global__ void __launch_bounds__(256)
 k_gather_fmodels(int D, const fgather_src *__restrict__ src, double *__restrict__ c, double *__restrict__ mean,
-                 double *__restrict__ inv_cov, double *__restrict__ den)
+                 double *__restrict__ inv_cov, double *__restrict__ den, double *__restrict__ lk)
 {
     const fgather_src s = src[blockIdx.x];
     for (int k = threadIdx.x; k < s.ng; k += 256) {
         c[s.g0 + k] = s.c[k];
         den[s.g0 + k] = s.den[k];
+        lk[s.g0 + k] = s.lk[k];
     }
     const size_t n = (size_t)s.ng * D, o = (size_t)s.g0 * D;
     for (size_t k = threadIdx.x; k < n; k += 256) mean[o + k] = s.mean[k];

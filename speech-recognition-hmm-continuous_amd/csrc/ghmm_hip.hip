@@ -2279,6 +2279,9 @@ struct ghmm_fmodel {
     int N = 0, M = 0, D = 0;
     double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
     double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
+    // ghmm_viterbi_full: log(c) - log(den) per Gaussian, and A > 0 ? log(A) : -inf, both formed on
+    // the host (the oracle's expressions, evaluated by the same libm)
+    double *lk = nullptr, *logA = nullptr;
     // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
     // run_scan_combine): N, and A (aliases the A above, owned there) with its band flag.  Nothing
     // else of it is set; it is never passed to ghmm_model_destroy.
@@ -2298,7 +2301,8 @@ static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
     int rc;
     if ((rc = dev_alloc(&fm->A, (size_t)N * N)) || (rc = dev_alloc(&fm->c, G)) ||
         (rc = dev_alloc(&fm->mean, nmean)) || (rc = dev_alloc(&fm->inv_cov, ncov)) ||
-        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G))) {
+        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G)) || (rc = dev_alloc(&fm->lk, G)) ||
+        (rc = dev_alloc(&fm->logA, (size_t)N * N))) {
         ghmm_fmodel_destroy(ctx, fm);
         return rc;
     }
@@ -2336,7 +2340,7 @@ extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den};
+    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den, fm->lk, fm->logA};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete fm;
@@ -2355,15 +2359,21 @@ extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, 
         for (int j = 0; j < fm->N; j++)
             if (A[(size_t)i * fm->N + j] != 0.0 && j != i && j != i + 1) fm->rec.banded = false;
     // calc_gaus's normaliser as the reference forms it: aux1 = pow(2 pi, D/2.0), aux2 = pow(|det|, 0.5)
-    std::vector<double> den(G);
+    std::vector<double> den(G), lk(G), logA(NN);
     const double aux1 = pow(2.0 * M_PI, fm->D / 2.0);
-    for (size_t g = 0; g < G; g++) den[g] = aux1 * pow(fabs(det[g]), 0.5);
+    for (size_t g = 0; g < G; g++) {
+        den[g] = aux1 * pow(fabs(det[g]), 0.5);
+        lk[g] = log(c[g]) - log(den[g]);
+    }
+    for (size_t k = 0; k < NN; k++) logA[k] = A[k] > 0.0 ? log(A[k]) : -INFINITY;
     HIP_TRY(hipMemcpyAsync(fm->A, A, NN * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(fm->c, c, G * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(fm->mean, mean, G * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(fm->inv_cov, inv_cov, G * fm->D * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(fm->det, det, G * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(fm->den, den.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->lk, lk.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->logA, logA.data(), NN * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(stream_sync(ctx)); // (pageable sources)
     return GHMM_OK;
 }
@@ -2431,7 +2441,8 @@ static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
     return GHMM_OK;
 }
 
-static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, bool want_post = false)
+// mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b)
+static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN)
 {
     // the workspace now holds densities no diagonal model owns: the row API refuses them
     // (need_emission), and alpha^ / W / log P of an earlier pass no longer go with b
@@ -2440,7 +2451,7 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
     ctx->em_m = nullptr;
     ctx->em_c = c;
     ctx->em_epoch = -1;
-    ctx->b_is_log = false;
+    ctx->b_is_log = mode == FC_LOG;
     ctx->own_bwd_done = false;
     ctx->beta_valid = false;
     ctx->loglik_pieces = false;
@@ -2452,12 +2463,18 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
     kscope ks(ctx, GHMM_K_EMISSION);
 #define GHMM_FCK(DBV)                                                                                         \
     do {                                                                                                      \
-        if (want_post)                                                                                        \
-            hipLaunchKernelGGL((k_emission_full<DBV, true>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, \
-                               fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, ctx->post); \
+        if (mode == FC_POST)                                                                                  \
+            hipLaunchKernelGGL((k_emission_full<DBV, FC_POST>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,     \
+                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
+                               ctx->post, (const double *)nullptr);                                           \
+        else if (mode == FC_LOG)                                                                              \
+            hipLaunchKernelGGL((k_emission_full<DBV, FC_LOG>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,      \
+                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
+                               (double *)nullptr, fm->lk);                                                    \
         else                                                                                                  \
             hipLaunchKernelGGL(k_emission_full<DBV>, grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M, \
-                               fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, (double *)nullptr); \
+                               fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, (double *)nullptr, \
+                               (const double *)nullptr);                                                      \
     } while (0)
     switch (DB) {
     case 8: GHMM_FCK(8); break;
@@ -2502,26 +2519,32 @@ extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, d
     return GHMM_OK;
 }
 
-extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
-                                     double *loglik_host)
+// the checks of the full batch calls past their null arguments: every model shares M and D, the
+// corpus has that D; NS = the vocabulary's states, Nmax = the largest model's
+static int fvocab_check(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, const ghmm_corpus *c,
+                        const char *what, int *NS, int *Nmax)
 {
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(models && n_models > 0 && c, "null argument");
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
     const int M = models[0]->M, D = models[0]->D;
-    int NS = 0;
+    *NS = *Nmax = 0;
     for (int k = 0; k < n_models; k++) {
         if (models[k]->M != M || models[k]->D != D) {
-            ghmm_set_error("ghmm_score_full_batch: every model must have the same M and D");
+            ghmm_set_error("%s: every model must have the same M and D", what);
             return GHMM_ERR_UNSUPPORTED;
         }
-        NS += models[k]->N;
+        *NS += models[k]->N;
+        *Nmax = models[k]->N > *Nmax ? models[k]->N : *Nmax;
     }
-    if ((rc = check_full(ctx, models[0], c))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    // the concatenated vocabulary (NS states, transitions unused), kept in the context between calls
+    return check_full(ctx, models[0], c);
+}
+
+// The concatenated vocabulary (NS states, transitions unused), kept in the context between calls:
+// every word's Gaussians gathered into it by one launch, and the table of the words' recursions
+// (tab[k].A = word k's A, or its log A for the Viterbi lattice).
+static int fvocab_gather(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, int NS, bool log_a,
+                         ghmm_fmodel **cat_out, const fwd_model **tab_out)
+{
+    int rc;
+    const int M = models[0]->M, D = models[0]->D;
     if (ctx->fbt_cat && (ctx->fbt_cat->N != NS || ctx->fbt_cat->M != M || ctx->fbt_cat->D != D)) {
         ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
         ctx->fbt_cat = nullptr;
@@ -2534,10 +2557,11 @@ extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, 
         int go = 0, so = 0;
         for (int k = 0; k < n_models; k++) {
             const ghmm_fmodel *m = models[k];
-            tab[k].A = m->A;
+            tab[k].A = log_a ? m->logA : m->A;
             tab[k].N = m->N;
             tab[k].bo = so;
             src[k].c = m->c; src[k].mean = m->mean; src[k].inv_cov = m->inv_cov; src[k].den = m->den;
+            src[k].lk = m->lk;
             src[k].g0 = go; src[k].ng = m->N * M;
             go += m->N * M;
             so += m->N;
@@ -2547,15 +2571,32 @@ extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, 
     if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, tab_bytes + src_bytes + 16))) return rc;
     fwd_model *dtab = (fwd_model *)ctx->fbt_tab;
     fgather_src *dsrc = (fgather_src *)(ctx->fbt_tab + ((tab_bytes + 15) / 16) * 16);
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
     HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_gather_fmodels, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
-                       cat->mean, cat->inv_cov, cat->den);
+                       cat->mean, cat->inv_cov, cat->den, cat->lk);
     if ((rc = launch_ok("k_gather_fmodels"))) return rc;
-    if ((rc = ws_full(ctx, NS, M, c)) || (rc = run_emission_full(ctx, cat, c))) return rc;
-    int Nmax = 0;
-    for (int k = 0; k < n_models; k++) Nmax = models[k]->N > Nmax ? models[k]->N : Nmax;
+    *cat_out = cat;
+    *tab_out = dtab;
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                     double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(models && n_models > 0 && c, "null argument");
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
+    int NS, Nmax;
+    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_score_full_batch", &NS, &Nmax))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    ghmm_fmodel *cat;
+    const fwd_model *dtab;
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    if ((rc = fvocab_gather(ctx, models, n_models, NS, false, &cat, &dtab))) return rc;
+    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c))) return rc;
     {
         const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
         const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
@@ -2566,6 +2607,65 @@ extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, 
     }
     if ((rc = launch_ok("k_forward_multi"))) return rc;
     HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+// ------------------------------------------------ the full-covariance Viterbi
+
+extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *path_host,
+                                 double *score_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    if (c->U == 0) return GHMM_OK;
+    const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
+    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * L + 16))) return rc; // rows of L bytes
+    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
+    {
+        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
+                                            fm->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik, ctx->sink,
+                                            c->order));
+    }
+    if ((rc = launch_ok("k_viterbi"))) return rc;
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                       double *score_host)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(models && n_models > 0 && c, "null argument");
+    ARG_CHECK(score_host || c->U == 0, "null destination");
+    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
+    int NS, Nmax;
+    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_viterbi_full_batch", &NS, &Nmax))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    ghmm_fmodel *cat;
+    const fwd_model *dtab;
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    if ((rc = fvocab_gather(ctx, models, n_models, NS, true, &cat, &dtab))) return rc;
+    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c, FC_LOG))) return rc;
+    {
+        const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
+        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                            ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                            c->order));
+    }
+    if ((rc = launch_ok("k_viterbi_multi"))) return rc;
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
                            ctx->stream));
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
@@ -2643,7 +2743,7 @@ extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, g
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, rm, c))) return rc;
     if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
     if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
-    if ((rc = run_emission_full(ctx, fm, c, true))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_POST))) return rc;
     // calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
     // diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this
     // model's A and the densities above

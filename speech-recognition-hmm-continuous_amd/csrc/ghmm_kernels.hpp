@@ -1560,9 +1560,11 @@ k_init_classify(int N, int M, int D, int n_cells, int U, long long F, int FR,
 // structure is chosen once per wave: for a left-to-right model only the candidates i = j-1 and
 // i = j exist (every other log a_ij is -inf and can never win a strict `>`), taken with one DPP
 // row shift instead of N lane reads.  Back-pointers are one byte, rows of L bytes per frame.
-template <int L, bool BANDED>
+// lb = the utterance's log b rows, ldb doubles apart (N, or the vocabulary's NS).  PSI = false:
+// score only, no back-pointer is stored (k_viterbi_multi); the max-plus arithmetic is the same.
+template <int L, bool BANDED, bool PSI = true>
 __device__ __forceinline__ double viterbi_run(int N, int T, int j, bool act, const double *__restrict__ logA,
-                                     const double *__restrict__ lb, unsigned char *__restrict__ ps,
+                                     const double *__restrict__ lb, int ldb, unsigned char *__restrict__ ps,
                                      double *__restrict__ sink)
 {
     double lacol[BANDED ? 1 : L];
@@ -1574,8 +1576,8 @@ __device__ __forceinline__ double viterbi_run(int N, int T, int j, bool act, con
     const double la_prev = (act && j > 0) ? logA[(j - 1) * N + j] : -INFINITY;
     // idle lanes: zeros from the sink's read-only half (stride 0), back-pointers into its other half
     const double *pl = act ? lb + j : sink + WAVE;
-    const ptrdiff_t db = act ? N : 0;
-    unsigned char *pp = act ? ps + j : (unsigned char *)sink;
+    const ptrdiff_t db = act ? ldb : 0;
+    unsigned char *pp = PSI && act ? ps + j : (unsigned char *)sink;
     const ptrdiff_t dp = act ? L : 0;
     auto bnext = [&]() {
         const double v = *pl;
@@ -1583,8 +1585,10 @@ __device__ __forceinline__ double viterbi_run(int N, int T, int j, bool act, con
         return v;
     };
     double d = ((j == 0) ? 0.0 : -INFINITY) + bnext();
-    *pp = 0;
-    pp += dp;
+    if (PSI) {
+        *pp = 0;
+        pp += dp;
+    }
     auto step = [&](double q) {
         double best = -INFINITY;
         int arg = 0;
@@ -1611,8 +1615,10 @@ __device__ __forceinline__ double viterbi_run(int N, int T, int j, bool act, con
                 }
         }
         d = best + q;
-        *pp = (unsigned char)arg;
-        pp += dp;
+        if (PSI) {
+            *pp = (unsigned char)arg;
+            pp += dp;
+        }
     };
     double q[PF];
     int t = 1;
@@ -1666,8 +1672,8 @@ k_viterbi(int N, int U, const double *__restrict__ logA, const double *__restric
     unsigned char *ps = psi + (size_t)f0 * L; // rows of L bytes
     double *snk = wave_sink(sink);
     double d;
-    if (banded) d = viterbi_run<L, true>(N, T, j, act, logA, logb + f0 * N, ps, snk);
-    else d = viterbi_run<L, false>(N, T, j, act, logA, logb + f0 * N, ps, snk);
+    if (banded) d = viterbi_run<L, true>(N, T, j, act, logA, logb + f0 * N, N, ps, snk);
+    else d = viterbi_run<L, false>(N, T, j, act, logA, logb + f0 * N, N, ps, snk);
     const double sc = __shfl(d, N - 1, L);
     __threadfence_block();
     if (j != 0) return;
@@ -1700,6 +1706,45 @@ k_viterbi(int N, int U, const double *__restrict__ logA, const double *__restric
             s = ps[(size_t)t * L + s];
         }
     }
+}
+
+// ghmm_viterbi_full_batch: k_viterbi's lattice for every (model, utterance) pair of a concatenated
+// vocabulary in one launch, as k_forward_multi does the forward pass: blockIdx.y = word model,
+// tab[k].A = its log A, logb[F][NS] with model k in columns bo_k .. bo_k + N_k - 1.  Score only:
+// score[k * U + u] = delta_{T-1}(N_k - 1), bit for bit what k_viterbi gives that model alone
+// (the same viterbi_run, without its back-pointer stores).
+template <int L>
+__global__ void __launch_bounds__(WAVE)
+k_viterbi_multi(int U, int NS, const fwd_model *__restrict__ tab, const double *__restrict__ logb,
+                const long long *__restrict__ off, double *__restrict__ score, double *__restrict__ sink,
+                const int *__restrict__ order)
+{
+    const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
+    const int j = threadIdx.x % L;
+    const int k = blockIdx.y;
+    if (slot >= U) return;
+    const int u = order[slot];
+    const fwd_model mk = tab[k];
+    const int N = mk.N;
+    const double *logA = mk.A;
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    if (T <= 0) {
+        if (j == 0) score[(size_t)k * U + u] = 0.0;
+        return;
+    }
+    const bool act = j < N;
+    bool offband = false;
+    for (int i = 0; i < N; i++)
+        offband |= act && (logA[i * N + j] != -INFINITY && i != j && i != j - 1);
+    const bool banded = !__any(offband);
+    double *snk = wave_sink(sink);
+    const double *lb = logb + f0 * NS + mk.bo;
+    double d;
+    if (banded) d = viterbi_run<L, true, false>(N, T, j, act, logA, lb, NS, nullptr, snk);
+    else d = viterbi_run<L, false, false>(N, T, j, act, logA, lb, NS, nullptr, snk);
+    const double sc = __shfl(d, N - 1, L);
+    if (j == 0) score[(size_t)k * U + u] = sc;
 }
 
 } // namespace ghmm

@@ -111,6 +111,8 @@ SYMBOLS = {
     "ghmm_emission_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_score_full": (C.c_int, [_vp, _vp, _vp, _dp], True),
     "ghmm_score_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
+    "ghmm_viterbi_full": (C.c_int, [_vp, _vp, _vp, _ip, _dp], True),
+    "ghmm_viterbi_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
     "ghmm_stats_len_full": (C.c_size_t, [C.c_int, C.c_int, C.c_int], False),
     "ghmm_stats_create_full": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
     "ghmm_estep_full": (C.c_int, [_vp, _vp, _vp, _vp], True),
@@ -641,6 +643,23 @@ class Context:
         arr = (_vp * len(fmodels))(*[m.h for m in fmodels])
         out = np.empty((len(fmodels), corpus.n_utt), dtype=np.float64)
         _check(self.lib.ghmm_score_full_batch(self.h, arr, len(fmodels), corpus.h, _d(out)),
+               self.lib)
+        return out
+
+    def viterbi_full(self, fmodel, corpus):
+        """best path (state per frame) and its log score per utterance, ending in the last state;
+        log b stays in the workspace (fetch(BUF_B, (frames, N)))"""
+        path = np.empty(corpus.frames, dtype=np.int32)
+        score = np.empty(corpus.n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_full(self.h, fmodel.h, corpus.h, path.ctypes.data_as(_ip),
+                                          _d(score)), self.lib)
+        return path, score
+
+    def viterbi_full_batch(self, fmodels, corpus):
+        """out[k, u] = Viterbi log score of utterance u under model k (= viterbi_full's, bit for bit)"""
+        arr = (_vp * len(fmodels))(*[m.h for m in fmodels])
+        out = np.empty((len(fmodels), corpus.n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_full_batch(self.h, arr, len(fmodels), corpus.h, _d(out)),
                self.lib)
         return out
 
