@@ -347,6 +347,32 @@ int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *p
  * Synchronises. */
 int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                             double *score_host);
+/* The forward score of full-covariance models in the log domain (absent from the reference): the
+ * sum over paths where ghmm_viterbi_full takes the best one, on the same log b, lk and log A
+ * (log a_ij = a_ij > 0 ? log(a_ij) : -inf, formed by ghmm_fmodel_set).
+ *     la_0(j) = (j == 0 ? 0 : -inf) + log b_j(0)                      (the one-hot start)
+ *     la_t(j) = LSE_{i : a_ij > 0} (la_{t-1}(i) + log a_ij) + log b_j(t)
+ *     LSE(x)  = m + log(sum_i exp(x_i - m)),  m = max_i x_i
+ * LSE is -inf when it has no term or every term is -inf, and NaN when a term is NaN.  A transition
+ * with a_ij == 0 is not a term: a NaN in a predecessor that cannot be reached from does not leak.
+ *     final_state == 0:  log P = LSE_j la_{T-1}(j)   calc_probability (RC:822-836), no final-state
+ *                        term; equal to ghmm_score_full up to rounding wherever that is finite
+ *     final_state != 0:  log P = la_{T-1}(N-1)       the trainer's convention (TFF:299): the log P
+ *                        that ghmm_estep_full leaves in GHMM_BUF_LOGLIK, and the sum-over-paths
+ *                        counterpart of ghmm_viterbi_full's score
+ * Where the linear densities of ghmm_score_full underflow to 0 on a whole frame (its score is then
+ * -inf or NaN) this score stays finite.  T = 0 scores 0; U = 0 touches nothing.  Caps and refusals
+ * are ghmm_score_full's (GHMM_OPT_ROBUST set: GHMM_ERR_UNSUPPORTED).  The lattice launch counts
+ * under GHMM_K_FORWARD.  Afterwards ghmm_fetch(GHMM_BUF_B) returns log b[F][N].  Synchronises. */
+int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
+                       double *loglik_host);
+/* The same score of every (word, utterance) pair in three launches, like ghmm_viterbi_full_batch:
+ * the gather, one log-emission launch over the concatenated vocabulary, one lattice launch.  All
+ * models share M and D.  loglik_host[k*U + u] is bit for bit what ghmm_logscore_full gives word k
+ * (that call is the same lattice kernel on a table of one word); GHMM_BUF_B then holds
+ * log b[F][sum of N].  Synchronises. */
+int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                             int final_state, double *loglik_host);
 
 /* -------------------------------------------- the full-covariance trainer */
 

@@ -2671,6 +2671,63 @@ extern "C" int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models
     return GHMM_OK;
 }
 
+// ------------------------------------------------ the full-covariance log-domain forward score
+
+// k_logforward_multi over the n_models entries of dtab on the log b in the workspace; scores to the host
+static int run_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
+                          const ghmm_corpus *c, int final_state, double *loglik_host)
+{
+    int rc;
+    const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
+    const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+    {
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                            ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                            c->order, final_state));
+    }
+    if ((rc = launch_ok("k_logforward_multi"))) return rc;
+    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
+                                  double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if (c->U == 0) return GHMM_OK;
+    // the batch call's lattice launch on a table of one word
+    const fwd_model one = {fm->logA, fm->N, 0};
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
+    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
+    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
+}
+
+extern "C" int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                        int final_state, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(models && n_models > 0 && c, "null argument");
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
+    int NS, Nmax;
+    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_logscore_full_batch", &NS, &Nmax))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    ghmm_fmodel *cat;
+    const fwd_model *dtab;
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    if ((rc = fvocab_gather(ctx, models, n_models, NS, true, &cat, &dtab))) return rc;
+    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c, FC_LOG))) return rc;
+    return run_logforward(ctx, dtab, n_models, NS, Nmax, c, final_state, loglik_host);
+}
+
 // ------------------------------------------------ the full-covariance trainer (TFF)
 
 static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)

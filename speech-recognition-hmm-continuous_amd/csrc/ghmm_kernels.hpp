@@ -1747,4 +1747,144 @@ k_viterbi_multi(int U, int NS, const fwd_model *__restrict__ tab, const double *
     if (j == 0) score[(size_t)k * U + u] = sc;
 }
 
+// ------------------------------------------------------------------ log-domain forward
+// The sum-over-paths lattice on log b (ghmm_logscore_full; definition in include/ghmm.h):
+//   la_0(j) = (j == 0 ? 0 : -inf) + logb_j(0)
+//   la_t(j) = LSE_{i : a_ij > 0} (la_{t-1}(i) + log a_ij) + logb_j(t)
+//   LSE(x) = m + log sum exp(x_i - m), m = max x_i; -inf without a term above -inf; NaN with a NaN term
+// viterbi_run with the max replaced by LSE: the same lanes, cursor, prefetch and sink, no per-frame
+// store.  A transition with log a_ij = -inf is not a term (its predecessor's NaN does not leak),
+// which a loop-invariant select decides ahead of the chain.
+//   banded: the two terms c1 (from j-1, one DPP shift) and c0 (from j): with hi / lo their larger /
+//     smaller, LSE = hi + log1p(exp(lo - hi)): one compare, one exp (exp_emis) and one log1p on the
+//     chain.
+//     `c0 < c1` is false for a NaN, lo - hi is then NaN.
+//   dense: two passes over the N terms (max, then the sum of exp), the terms formed again in the
+//     second pass instead of kept: N exp a step.
+// Returns la_{T-1}(j); idle lanes return -inf.
+template <int L, bool BANDED>
+__device__ __forceinline__ double logforward_run(int N, int T, int j, bool act, const double *__restrict__ logA,
+                                                 const double *__restrict__ lb, int ldb,
+                                                 const double *__restrict__ sink)
+{
+    double lacol[BANDED ? 1 : L];
+    if (!BANDED) {
+#pragma unroll
+        for (int i = 0; i < L; i++) lacol[BANDED ? 0 : i] = (act && i < N) ? logA[i * N + j] : -INFINITY;
+    }
+    const double la_self = act ? logA[j * N + j] : -INFINITY;
+    const double la_prev = (act && j > 0) ? logA[(j - 1) * N + j] : -INFINITY;
+    const bool t_self = la_self != -INFINITY, t_prev = la_prev != -INFINITY;
+    // idle lanes: zeros from the sink's read-only half (stride 0)
+    const double *pl = act ? lb + j : sink + WAVE;
+    const ptrdiff_t db = act ? ldb : 0;
+    auto bnext = [&]() {
+        const double v = *pl;
+        pl += db;
+        return v;
+    };
+    double d = ((j == 0) ? 0.0 : -INFINITY) + bnext();
+    auto step = [&](double q) {
+        double r;
+        if (BANDED) {
+            // (the lane exchanges stand outside the selects: every lane must take part in them,
+            // a lane switched off by its own select would hand its readers 0)
+            const double dup = group_up1<L>(d);
+            const double c1 = t_prev ? dup + la_prev : -INFINITY;
+            const double c0 = t_self ? d + la_self : -INFINITY;
+            const bool up = c0 < c1;
+            const double hi = up ? c1 : c0, lo = up ? c0 : c1;
+            const double x = lo == -INFINITY ? -INFINITY : lo - hi; // (not -inf - -inf; a NaN lo stays)
+            r = hi + log1p(exp_emis(x));
+        } else {
+            double m = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < L; i++)
+                if (i < N) {
+                    const double la = lacol[BANDED ? 0 : i], di = __shfl(d, i, L);
+                    const double v = la != -INFINITY ? di + la : -INFINITY;
+                    m = fmax(m, v); // (a NaN term is passed over here and taken by the sum)
+                }
+            const double mm = m == -INFINITY ? 0.0 : m;
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < L; i++)
+                if (i < N) {
+                    const double la = lacol[BANDED ? 0 : i], di = __shfl(d, i, L);
+                    const double v = la != -INFINITY ? di + la : -INFINITY;
+                    s += exp_emis(v - mm);
+                }
+            r = m + log(s);
+        }
+        d = r + q;
+    };
+    double q[PF];
+    int t = 1;
+#pragma unroll
+    for (int k = 0; k < PF; k++) q[k] = bnext();
+    for (; t + PF <= T; t += PF) {
+        double qn[PF];
+#pragma unroll
+        for (int k = 0; k < PF; k++) qn[k] = bnext();
+#pragma unroll
+        for (int k = 0; k < PF; k++) step(q[k]);
+#pragma unroll
+        for (int k = 0; k < PF; k++) q[k] = qn[k];
+    }
+#pragma unroll BANDED ? PF - 1 : 1 // (the dense step is too long to be laid out PF - 1 times more)
+    for (int k = 0; k < PF - 1; k++)
+        if (t + k < T) step(q[k]);
+    return act ? d : -INFINITY;
+}
+
+// ghmm_logscore_full / ghmm_logscore_full_batch: the lattice above for every (model, utterance)
+// pair of a concatenated vocabulary in one launch, laid out as k_viterbi_multi: blockIdx.y = word
+// model, tab[k].A = its log A, logb[F][NS] with model k in columns bo_k .. bo_k + N_k - 1.
+//   final_state != 0: score[k * U + u] = la_{T-1}(N_k - 1)
+//   final_state == 0: score[k * U + u] = LSE_j la_{T-1}(j), one cross-lane LSE behind the lattice
+// The single call is this kernel on a one-entry table.
+template <int L>
+__global__ void __launch_bounds__(WAVE)
+k_logforward_multi(int U, int NS, const fwd_model *__restrict__ tab, const double *__restrict__ logb,
+                   const long long *__restrict__ off, double *__restrict__ score, double *__restrict__ sink,
+                   const int *__restrict__ order, int final_state)
+{
+    const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
+    const int j = threadIdx.x % L;
+    const int k = blockIdx.y;
+    if (slot >= U) return;
+    const int u = order[slot];
+    const fwd_model mk = tab[k];
+    const int N = mk.N;
+    const double *logA = mk.A;
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    if (T <= 0) {
+        if (j == 0) score[(size_t)k * U + u] = 0.0;
+        return;
+    }
+    const bool act = j < N;
+    bool offband = false;
+    for (int i = 0; i < N; i++)
+        offband |= act && (logA[i * N + j] != -INFINITY && i != j && i != j - 1);
+    const bool banded = !__any(offband);
+    const double *snk = wave_sink(sink);
+    const double *lb = logb + f0 * NS + mk.bo;
+    double d;
+    if (banded) d = logforward_run<L, true>(N, T, j, act, logA, lb, NS, snk);
+    else d = logforward_run<L, false>(N, T, j, act, logA, lb, NS, snk);
+    double sc;
+    if (final_state) {
+        sc = __shfl(d, N - 1, L);
+    } else {
+        double m = d; // (-inf in the idle lanes; fmax passes over a NaN, the sum takes it)
+#pragma unroll
+        for (int o = L / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, L));
+        m = fmax(m, -INFINITY);
+        const double mm = m == -INFINITY ? 0.0 : m;
+        sc = m + log(group_sum<L>(exp_emis(d - mm)));
+    }
+    if (j == 0) score[(size_t)k * U + u] = sc;
+}
+
 } // namespace ghmm

@@ -20,7 +20,10 @@
  * recogniser RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c: the same
  * argv, lists and bookkeeping (RC:283-412), its usage text and header (RC:1019-1033), models read
  * with ghmm_hmm_read_full (RC:591-707, one stream) and scored with ghmm_score_full_batch, whose
- * log P has no final-state term (calc_probability, RC:822-836).
+ * log P has no final-state term (calc_probability, RC:822-836).  With GHMM_LOG_SCORE=1 in the
+ * environment that program scores in the log domain instead (ghmm_logscore_full_batch, final_state
+ * = 0: the same quantity, finite where the linear densities underflow) and says so in the report's
+ * second line; without the variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -131,6 +134,10 @@ int main(int argc, char **argv)
     for (int i = 0; i < K; i++) coef_model[i] = atof(argv[K + 2 + i]);
     const char *output_file = argv[argc - 1], *word_file = argv[argc - 2];
     int rc;
+#ifdef GHMM_FULL_COV
+    const char *env_log = getenv("GHMM_LOG_SCORE");
+    const int log_score = env_log && strcmp(env_log, "1") == 0;
+#endif
 
     /* models: one list per set, the same vocabulary in every set */
 #ifdef GHMM_FULL_COV
@@ -265,7 +272,8 @@ int main(int argc, char **argv)
 #ifdef GHMM_FULL_COV
     /* writing_header, RC:1019-1033 (coef_model is a double there) */
     fprintf(f_out, "Isolated word recognition using Continuous HMM. It is considered full covariance matrix.\n");
-    fprintf(f_out, "Algorithm used for recognition: Forward \n");
+    fprintf(f_out, log_score ? "Algorithm used for recognition: Forward (log domain) \n"
+                             : "Algorithm used for recognition: Forward \n");
     fprintf(f_out, "Number of models: %d  \n", K);
     for (int i = 0; i < K; i++) {
         fprintf(f_out, "Model name %d: %s\n", i + 1, argv[2 + i]);
@@ -297,7 +305,8 @@ int main(int argc, char **argv)
 #ifdef GHMM_FULL_COV
         for (int j = 0; j < K; j++) {
             /* the whole vocabulary in one batched call when the models share M (ghmm_score_full_batch),
-               model by model otherwise (ghmm_score_full) */
+               model by model otherwise (ghmm_score_full); GHMM_LOG_SCORE=1: their log-domain
+               counterparts without the final-state term */
             ghmm_corpus *corpus;
             if ((rc = ghmm_corpus_create(ctx, X[j][0], len[j], n_utt, D[j][0], &corpus))) die("corpus", rc);
             ghmm_fmodel **fm = (ghmm_fmodel **)calloc((size_t)word_number, sizeof(ghmm_fmodel *));
@@ -314,7 +323,12 @@ int main(int argc, char **argv)
                 if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, &fm[k]))) die("model", rc);
                 if ((rc = ghmm_fmodel_set(ctx, fm[k], m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
             }
-            if (same) {
+            if (log_score && same) {
+                if ((rc = ghmm_logscore_full_batch(ctx, fm, word_number, corpus, 0, all))) die("scoring", rc);
+            } else if (log_score) {
+                for (int k = 0; k < word_number; k++)
+                    if ((rc = ghmm_logscore_full(ctx, fm[k], corpus, 0, all + (size_t)k * n_utt))) die("scoring", rc);
+            } else if (same) {
                 if ((rc = ghmm_score_full_batch(ctx, fm, word_number, corpus, all))) die("scoring", rc);
             } else {
                 for (int k = 0; k < word_number; k++)

@@ -113,6 +113,8 @@ SYMBOLS = {
     "ghmm_score_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
     "ghmm_viterbi_full": (C.c_int, [_vp, _vp, _vp, _ip, _dp], True),
     "ghmm_viterbi_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
+    "ghmm_logscore_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
+    "ghmm_logscore_full_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
     "ghmm_stats_len_full": (C.c_size_t, [C.c_int, C.c_int, C.c_int], False),
     "ghmm_stats_create_full": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
     "ghmm_estep_full": (C.c_int, [_vp, _vp, _vp, _vp], True),
@@ -661,6 +663,24 @@ class Context:
         out = np.empty((len(fmodels), corpus.n_utt), dtype=np.float64)
         _check(self.lib.ghmm_viterbi_full_batch(self.h, arr, len(fmodels), corpus.h, _d(out)),
                self.lib)
+        return out
+
+    def logscore_full(self, fmodel, corpus, final_state=False):
+        """log-domain forward score per utterance: LSE over the last frame's states, or the last
+        state's alone with final_state; finite where score_full underflows; log b stays in the
+        workspace (fetch(BUF_B, (frames, N)))"""
+        out = np.empty(corpus.n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_logscore_full(self.h, fmodel.h, corpus.h, int(bool(final_state)), _d(out)),
+               self.lib)
+        return out
+
+    def logscore_full_batch(self, fmodels, corpus, final_state=False):
+        """out[k, u] = log-domain forward score of utterance u under model k (= logscore_full's, bit
+        for bit)"""
+        arr = (_vp * len(fmodels))(*[m.h for m in fmodels])
+        out = np.empty((len(fmodels), corpus.n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_logscore_full_batch(self.h, arr, len(fmodels), corpus.h,
+                                                 int(bool(final_state)), _d(out)), self.lib)
         return out
 
     # ---- the full-covariance trainer
