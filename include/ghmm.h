@@ -396,6 +396,40 @@ int ghmm_stats_create_full(ghmm_ctx *ctx, int N, int M, int D, ghmm_stats **out)
  * reproducible).  Afterwards ghmm_fetch(GHMM_BUF_B / _POST / _GAMMA ...) returns the trainer's
  * arrays.  Asynchronous on the context's stream. */
 int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *stats);
+/* The same E-step with every quantity formed in the log domain (absent from the reference): where
+ * ghmm_estep_full's linear densities underflow to 0 on a whole frame (c_t = 1/0, NaN statistics) this
+ * call keeps finite statistics.  ghmm_estep_full's contract otherwise: the same
+ * ghmm_stats_create_full vector, overwritten; asynchronous on the context's stream; bitwise
+ * reproducible; GHMM_OPT_DELTA and GHMM_OPT_PARTIALS honoured; GHMM_OPT_ROBUST gives
+ * GHMM_ERR_UNSUPPORTED, a diagonal statistics vector GHMM_ERR_ARG; ghmm_mstep_full takes the result.
+ * Emission: lk, e_m = lk_m - aux_m / 2 and log b_i(t) are ghmm_viterbi_full's, from the same online
+ * log-sum-exp, bit for bit.
+ *     post_t(i,m) = exp(e_m - log b_i(t)), or 0 where log b_i(t) = -inf
+ * TFF's clamp of a +inf density to 1e20 has no counterpart: a Gaussian that is not positive definite
+ * keeps its finite e.
+ * Lattice: log a_ij is ghmm_fmodel_set's; a transition with a_ij == 0 is not a term; LSE as above.
+ *     la_0(j)      = (j == 0 ? 0 : -inf) + log b_j(0)
+ *     la_t(j)      = LSE_{i : a_ij > 0} (la_{t-1}(i) + log a_ij) + log b_j(t)     (ghmm_logscore_full's)
+ *     lbe_{T-1}(i) = (i == N-1 ? 0 : -inf)
+ *     lbe_t(i)     = LSE_{j : a_ij > 0} (log a_ij + (log b_j(t+1) + lbe_{t+1}(j)))
+ *     log P_u      = la_{T-1}(N-1)            -> GHMM_BUF_LOGLIK and the vector's loglik (TFF:299)
+ *     log Z_u      = LSE_j la_{T-1}(j)        the normaliser of gamma and xi
+ *     gamma_t(i)   = exp(la_t(i) + lbe_t(i) - log Z_u)
+ *     xi_t(i,j)    = exp(la_t(i) + log a_ij + log b_j(t+1) + lbe_{t+1}(j) - log Z_u),
+ *                    t < T-1, a_ij > 0, i <= j <= i + delta
+ *     num_a[i][j] = sum_u sum_{t<T-1} xi_t(i,j);  den_a[i] = sum_u sum_{t<T-1} gamma_t(i);
+ *     den_c[i] = sum_u sum_{t<T} gamma_t(i);  num_c / num_mu / num_cov: calc_mix_param on
+ *     w = gamma * post, the launches of ghmm_estep_full.
+ * The normaliser is log Z_u, not log P_u: TFF's scaled recursions give gamma = alpha^ beta^ / c_t,
+ * which divides by the probability of the observations over ALL end states while beta starts in the
+ * last state only, so a frame's gammas sum to exp(log P_u - log Z_u) <= 1, the same value at every t.
+ * An utterance with T < N or no path into the last state has every lbe = -inf: its gammas are exactly
+ * 0 and log P_u = -inf, as in the linear call.  Where log Z_u is not finite the utterance's gamma rows
+ * are 0 and it adds nothing to any sum except loglik (its log P_u as it is) and n_utt.  T = 0 adds 0 to
+ * loglik and counts in n_utt.  A NaN log b (det == 0) gives the formula's values.
+ * Afterwards ghmm_fetch returns GHMM_BUF_B: log b, _POST, _GAMMA, _LOGLIK, _ALPHA: la, _BETA: lbe.
+ * The lattice launch counts under GHMM_K_FORWARD. */
+int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *stats);
 /* The M-step (TFF:306-341): downloads the statistics and the model, applies ghmm_mstep_full_host
  * with GHMM_OPT_DELTA, and sets the model again.  Synchronises. */
 int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);

@@ -32,6 +32,12 @@
 // That is the oracle's sum up to rounding and gives its special values: an e of NaN makes the sum
 // NaN (log b NaN unless every other e is -inf, then -inf), an e of +inf (det == 0, c > 0) makes
 // m = +inf, where the oracle's exp(inf - inf) gives NaN.
+//
+// FC_LOGPOST is the log-domain E-step's variant (ghmm_estep_full_log): FC_LOG's online sum, operation
+// for operation, so that log b has FC_LOG's bits, plus the mixture posteriors in FC_POST's pattern:
+// e_m goes to post as it is formed and is replaced in place by exp(e_m - log b) once the state's
+// log b is known, 0 where log b is -inf (each lane rereads only what it wrote itself).  There is no
+// clamp of a +inf density: a Gaussian that is not positive definite keeps its finite e.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +51,7 @@ constexpr int FC_SLACK = 64;  // doubles allocated behind mean[] and inv_cov[] (
 constexpr int FC_LIN = 0;  // the recogniser's densities (RC)
 constexpr int FC_POST = 1; // the trainer's densities and the mixture posteriors (TFF)
 constexpr int FC_LOG = 2;  // log densities for the Viterbi lattice
+constexpr int FC_LOGPOST = 3; // log densities and the mixture posteriors for the log-domain E-step
 
 // doubles of LDS a block needs: the frame tile and every wave's density tile
 __host__ __device__ inline int fc_lds_doubles(int D) { return WAVE * (D | 1) + FC_WAVES * WAVE * (FC_SC | 1); }
@@ -66,7 +73,7 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
                 const double *__restrict__ den, const double *__restrict__ c, double *__restrict__ b,
                 double *__restrict__ post, const double *__restrict__ lk)
 {
-    constexpr bool POST = MODE == FC_POST, LOG = MODE == FC_LOG;
+    constexpr bool POST = MODE == FC_POST, LPOST = MODE == FC_LOGPOST, LOG = MODE == FC_LOG || LPOST;
     extern __shared__ double lds[];
     const int DS = D | 1; // odd row stride: conflict-free per-lane reads
     const int SS = FC_SC | 1;
@@ -112,6 +119,8 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
                 const double r = exp(up ? mx - e : (e == -INFINITY ? -INFINITY : e - mx));
                 bi = up ? fma(bi, r, 1.0) : bi + r;
                 mx = up ? e : mx;
+                if constexpr (LPOST)
+                    if (lane < nf) post[(f0 + lane) * ((long long)NS * M) + (long long)g] = e;
             } else if constexpr (POST) {
                 double gaus = exp(aux * -0.5) / den[g];
                 if (gaus == INFINITY && den[g] != 0.0) gaus = 1e20;
@@ -128,6 +137,12 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
             if (lane < nf) {
                 double *pr = post + (f0 + lane) * ((long long)NS * M) + (long long)(s0 + s) * M;
                 for (int m = 0; m < M; m++) pr[m] = bi != 0.0 ? pr[m] / bi : 0.0;
+            }
+        }
+        if constexpr (LPOST) {
+            if (lane < nf) {
+                double *pr = post + (f0 + lane) * ((long long)NS * M) + (long long)(s0 + s) * M;
+                for (int m = 0; m < M; m++) pr[m] = bi != -INFINITY ? exp(pr[m] - bi) : 0.0;
             }
         }
         bt[lane * SS + s] = bi;

@@ -2441,7 +2441,8 @@ static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
     return GHMM_OK;
 }
 
-// mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b)
+// mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b), FC_LOGPOST (log b and
+// the mixture posteriors)
 static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN)
 {
     // the workspace now holds densities no diagonal model owns: the row API refuses them
@@ -2451,7 +2452,7 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
     ctx->em_m = nullptr;
     ctx->em_c = c;
     ctx->em_epoch = -1;
-    ctx->b_is_log = mode == FC_LOG;
+    ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
     ctx->own_bwd_done = false;
     ctx->beta_valid = false;
     ctx->loglik_pieces = false;
@@ -2467,6 +2468,10 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
             hipLaunchKernelGGL((k_emission_full<DBV, FC_POST>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,     \
                                fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
                                ctx->post, (const double *)nullptr);                                           \
+        else if (mode == FC_LOGPOST)                                                                          \
+            hipLaunchKernelGGL((k_emission_full<DBV, FC_LOGPOST>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,  \
+                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
+                               ctx->post, fm->lk);                                                            \
         else if (mode == FC_LOG)                                                                              \
             hipLaunchKernelGGL((k_emission_full<DBV, FC_LOG>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,      \
                                fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
@@ -2810,6 +2815,36 @@ extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, g
         if ((rc = run_forward(ctx, rm, c, true))) return rc;
         if ((rc = run_backward(ctx, rm, c, false))) return rc;
     }
+    return run_fullstats(ctx, fm, c, s);
+}
+
+// The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
+// and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
+// (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
+extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
+    if (c->U) {
+        const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
+        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logfb_fwd<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
+                                            fm->logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk, ctx->sink,
+                                            c->order));
+        if ((rc = launch_ok("k_logfb_fwd"))) return rc;
+        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logfb_bwd<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
+                                            (int)ctx->delta, fm->logA, ctx->b, c->off, ctx->alpha, ctx->logk,
+                                            ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena, ctx->part_denc,
+                                            ctx->sink, c->order));
+        if ((rc = launch_ok("k_logfb_bwd"))) return rc;
+        ctx->beta_valid = true; // ctx->beta holds lbe: ghmm_fetch starts no linear pass on these buffers
+    }
+    ctx->slots = c->U; // one partial per utterance
+    ctx->loglik_pieces = false;
     return run_fullstats(ctx, fm, c, s);
 }
 

@@ -1762,10 +1762,13 @@ k_viterbi_multi(int U, int NS, const fwd_model *__restrict__ tab, const double *
 //   dense: two passes over the N terms (max, then the sum of exp), the terms formed again in the
 //     second pass instead of kept: N exp a step.
 // Returns la_{T-1}(j); idle lanes return -inf.
-template <int L, bool BANDED>
+// STORE = true (k_logfb): every la row is also stored, la_t(j) at out[t * N + j]; idle lanes store into
+// wsink with stride 0.  The arithmetic is the same.
+template <int L, bool BANDED, bool STORE = false>
 __device__ __forceinline__ double logforward_run(int N, int T, int j, bool act, const double *__restrict__ logA,
                                                  const double *__restrict__ lb, int ldb,
-                                                 const double *__restrict__ sink)
+                                                 const double *__restrict__ sink, double *out = nullptr,
+                                                 double *wsink = nullptr)
 {
     double lacol[BANDED ? 1 : L];
     if (!BANDED) {
@@ -1784,6 +1787,12 @@ __device__ __forceinline__ double logforward_run(int N, int T, int j, bool act, 
         return v;
     };
     double d = ((j == 0) ? 0.0 : -INFINITY) + bnext();
+    double *po = STORE ? (act ? out + j : wsink) : nullptr;
+    const ptrdiff_t dpo = act ? N : 0;
+    if (STORE) {
+        *po = d;
+        po += dpo;
+    }
     auto step = [&](double q) {
         double r;
         if (BANDED) {
@@ -1817,6 +1826,10 @@ __device__ __forceinline__ double logforward_run(int N, int T, int j, bool act, 
             r = m + log(s);
         }
         d = r + q;
+        if (STORE) {
+            *po = d;
+            po += dpo;
+        }
     };
     double q[PF];
     int t = 1;
@@ -1885,6 +1898,240 @@ k_logforward_multi(int U, int NS, const fwd_model *__restrict__ tab, const doubl
         sc = m + log(group_sum<L>(exp_emis(d - mm)));
     }
     if (j == 0) score[(size_t)k * U + u] = sc;
+}
+
+// ------------------------------------------------------------------ log-domain forward-backward
+// ghmm_estep_full_log's lattice (definition in include/ghmm.h): one group of L lanes per utterance,
+// lane = state, in three steps over two launches (k_logfb_fwd: 1 and 2, k_logfb_bwd: 3).  As one
+// kernel the dense form held the forward chain's column and the backward chain's row of log A at
+// once and, at L = 32 and 64, spilled vector registers; log Z_u crosses in logz[U].
+//   1. logforward_run with its la rows stored (STORE): la[F][N].
+//   2. log P_u = la_{T-1}(N-1) by one lane read, log Z_u = LSE_j la_{T-1}(j) by the cross-lane LSE of
+//      k_logforward_multi.  log Z_u, not log P_u, normalises gamma and xi: TFF's alpha^ beta^ / c_t
+//      divides by the probability of the observations over all end states.
+//   3. the backward chain from T-1, on w_j = log b_j(t+1) + lbe_{t+1}(j) of lane j:
+//        lbe_t(i) = LSE_{j : a_ij > 0} (log a_ij + w_j)
+//      banded: the two terms from i (own lane) and i+1 (one DPP shift the other way), hi + log1p(exp(lo - hi))
+//      as in the forward step; dense: the lane's row of log A in registers, two passes over N lane reads.
+//      The same step forms gamma_t(i) = exp(la_t(i) + lbe_t(i) - log Z_u) and the band's
+//      xi_t(i, i+o) = exp(((la_t(i) + log a_{i,i+o}) + w_{i+o}) - log Z_u), o = 0 .. delta, and adds them
+//      into den_a / den_c / xi[o] in registers, in descending t.  A lane reads back only the la it
+//      stored itself.
+// Where log Z_u is not finite every gamma and xi of the utterance is 0.  One partial per utterance
+// (slot = u, S = U) for k_reduce_all, as k_backward leaves them.
+template <int L, bool BANDED>
+__device__ __forceinline__ void logbackward_run(int N, int T, int delta, int i, bool act, int u, int U,
+                                                const double *__restrict__ logA, const double *__restrict__ lb,
+                                                double *la, double *__restrict__ lbe, double *__restrict__ gam,
+                                                double logZ, double *__restrict__ part_xi,
+                                                double *__restrict__ part_dena, double *__restrict__ part_denc,
+                                                double *__restrict__ sink)
+{
+    double larow[BANDED ? 1 : L];
+    if (!BANDED) {
+#pragma unroll
+        for (int j = 0; j < L; j++) larow[BANDED ? 0 : j] = (act && j < N) ? logA[i * N + j] : -INFINITY;
+    }
+    const double la_self = act ? logA[i * N + i] : -INFINITY;
+    const double la_next = (act && i + 1 < N) ? logA[i * N + i + 1] : -INFINITY;
+    const bool t_self = la_self != -INFINITY, t_next = la_next != -INFINITY;
+    double laband[MAX_DELTA + 1], xi[MAX_DELTA + 1];
+#pragma unroll
+    for (int o = 0; o <= MAX_DELTA; o++) {
+        laband[o] = (act && i + o < N && o <= delta) ? logA[i * N + i + o] : -INFINITY;
+        xi[o] = 0.0;
+    }
+    const bool zok = fabs(logZ) < INFINITY; // (false for a NaN)
+    const int dn = act ? N : 0;
+    // frame-indexed readers, clamped into the utterance (never predicated); lanes without a state
+    // read zeros from the sink's read-only half and write its other half, both with stride 0
+    const double *pa0 = act ? la + i : sink + WAVE, *pb0 = act ? lb + i : sink + WAVE;
+    auto clampf = [&](int f) { return (size_t)(f < 0 ? 0 : f); };
+    double *pbe = act ? lbe + (size_t)(T - 1) * N + i : sink;
+    double *pg = act ? gam + (size_t)(T - 1) * N + i : sink;
+    double be = (act && i == N - 1) ? 0.0 : -INFINITY;
+    double dena = 0.0, denc;
+    {
+        const double al = act ? pa0[(size_t)(T - 1) * dn] : -INFINITY;
+        const double g = zok ? exp_emis((al + be) - logZ) : 0.0;
+        *pbe = be;
+        *pg = g;
+        denc = g; // gamma_{T-1}: in den_c (t < T) but not in den_a (t < T-1)
+    }
+    // one step t (descending): bn = log b_i(t+1), al = la_t(i)
+    auto step = [&](double bn, double al) {
+        const double w = be + bn; // log b_i(t+1) + lbe_{t+1}(i) on lane i
+        // (the lane exchange stands outside the selects: every lane must take part in it)
+        const double wd = group_down1<L>(w);
+        double r;
+        if (BANDED) {
+            const double c0 = t_self ? la_self + w : -INFINITY;
+            const double c1 = t_next ? la_next + wd : -INFINITY;
+            const bool up = c0 < c1;
+            const double hi = up ? c1 : c0, lo = up ? c0 : c1;
+            const double x = lo == -INFINITY ? -INFINITY : lo - hi; // (not -inf - -inf; a NaN lo stays)
+            r = hi + log1p(exp_emis(x));
+        } else {
+            double m = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < L; j++)
+                if (j < N) {
+                    const double la_ij = larow[BANDED ? 0 : j], wj = __shfl(w, j, L);
+                    const double v = la_ij != -INFINITY ? la_ij + wj : -INFINITY;
+                    m = fmax(m, v); // (a NaN term is passed over here and taken by the sum)
+                }
+            const double mm = m == -INFINITY ? 0.0 : m;
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < L; j++)
+                if (j < N) {
+                    const double la_ij = larow[BANDED ? 0 : j], wj = __shfl(w, j, L);
+                    const double v = la_ij != -INFINITY ? la_ij + wj : -INFINITY;
+                    s += exp_emis(v - mm);
+                }
+            r = m + log(s);
+        }
+        // the band's xi: a transition with a_{i,i+o} == 0 (or outside the model / the band) is not a term
+        xi[0] += (zok && laband[0] != -INFINITY) ? exp_emis(((al + laband[0]) + w) - logZ) : 0.0;
+        xi[1] += (zok && laband[1] != -INFINITY) ? exp_emis(((al + laband[1]) + wd) - logZ) : 0.0;
+#pragma unroll
+        for (int o = 2; o <= MAX_DELTA; o++)
+            if (o <= delta) {
+                const double wj = __shfl_down(w, o, L);
+                xi[o] += (zok && laband[o] != -INFINITY) ? exp_emis(((al + laband[o]) + wj) - logZ) : 0.0;
+            }
+        be = r;
+        const double g = zok ? exp_emis((al + be) - logZ) : 0.0;
+        *pbe = be;
+        *pg = g;
+        dena += g;
+    };
+    // prefetch depth: the dense step (N exp) hides a load behind a single step, and its row of log A
+    // leaves no registers for deeper queues
+    constexpr int Q = BANDED ? PF : 2;
+    double qb[Q], qa[Q];
+    int t = T - 2;
+#pragma unroll
+    for (int k = 0; k < Q; k++) {
+        const size_t f = clampf(t - k);
+        qb[k] = pb0[(f + 1 < (size_t)T ? f + 1 : (size_t)T - 1) * dn];
+        qa[k] = pa0[f * dn];
+    }
+    pbe -= dn; pg -= dn;
+    for (; t - Q + 1 >= 0; t -= Q) {
+        double nb[Q], na[Q];
+#pragma unroll
+        for (int k = 0; k < Q; k++) {
+            const size_t f = clampf(t - Q - k);
+            nb[k] = pb0[(f + 1 < (size_t)T ? f + 1 : (size_t)T - 1) * dn];
+            na[k] = pa0[f * dn];
+        }
+#pragma unroll BANDED ? Q : 1 // (the dense step is too long to be laid out Q times)
+        for (int k = 0; k < Q; k++) {
+            step(qb[k], qa[k]);
+            pbe -= dn; pg -= dn;
+        }
+#pragma unroll
+        for (int k = 0; k < Q; k++) {
+            qb[k] = nb[k]; qa[k] = na[k];
+        }
+    }
+#pragma unroll BANDED ? Q - 1 : 1
+    for (int k = 0; k < Q - 1; k++)
+        if (t - k >= 0) {
+            step(qb[k], qa[k]);
+            pbe -= dn; pg -= dn;
+        }
+    if (act) {
+#pragma unroll
+        for (int o = 0; o <= MAX_DELTA; o++) // compile-time indices: the arrays stay in registers
+            if (o <= delta) part_xi[pxi_at(u, i, o, U)] = xi[o];
+        part_dena[pden_at(u, i, U)] = dena;
+        part_denc[pden_at(u, i, U)] = dena + denc;
+    }
+}
+
+// The forward launch: la[F][N], log P_u into loglik[u], log Z_u into logz[u].
+template <int L>
+__global__ void __launch_bounds__(WAVE)
+k_logfb_fwd(int N, int U, const double *__restrict__ logA, const double *__restrict__ logb,
+            const long long *__restrict__ off, double *la, double *__restrict__ loglik, double *__restrict__ logz,
+            double *__restrict__ sink, const int *__restrict__ order)
+{
+    const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
+    const int j = threadIdx.x % L;
+    if (slot >= U) return;
+    const int u = order[slot];
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    if (T <= 0) {
+        if (j == 0) {
+            loglik[u] = 0.0;
+            logz[u] = 0.0;
+        }
+        return;
+    }
+    const bool act = j < N;
+    bool offband = false;
+    for (int i = 0; i < N; i++)
+        offband |= act && (logA[i * N + j] != -INFINITY && i != j && i != j - 1);
+    const bool banded = !__any(offband);
+    double *snk = wave_sink(sink);
+    const double *lb = logb + f0 * N;
+    double d;
+    if (banded) d = logforward_run<L, true, true>(N, T, j, act, logA, lb, N, snk, la + f0 * N, snk);
+    else d = logforward_run<L, false, true>(N, T, j, act, logA, lb, N, snk, la + f0 * N, snk);
+    const double lp = __shfl(d, N - 1, L);
+    double m = d; // (-inf in the idle lanes; fmax passes over a NaN, the sum takes it)
+#pragma unroll
+    for (int o = L / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, L));
+    m = fmax(m, -INFINITY);
+    const double mm = m == -INFINITY ? 0.0 : m;
+    const double lz = m + log(group_sum<L>(exp_emis(d - mm)));
+    if (j == 0) {
+        loglik[u] = lp;
+        logz[u] = lz;
+    }
+}
+
+// The backward launch, with the same utterance-to-lane layout: lane j reads back the la column it
+// stored in the forward launch.
+template <int L>
+__global__ void __launch_bounds__(WAVE)
+k_logfb_bwd(int N, int U, int delta, const double *__restrict__ logA, const double *__restrict__ logb,
+            const long long *__restrict__ off, double *la, const double *__restrict__ logz,
+            double *__restrict__ lbe, double *__restrict__ gamma, double *__restrict__ part_xi,
+            double *__restrict__ part_dena, double *__restrict__ part_denc, double *__restrict__ sink,
+            const int *__restrict__ order)
+{
+    const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
+    const int i = threadIdx.x % L;
+    if (slot >= U) return;
+    const int u = order[slot];
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    const bool act = i < N;
+    if (T <= 0) {
+        if (act) {
+            for (int o = 0; o <= delta; o++) part_xi[pxi_at(u, i, o, U)] = 0.0;
+            part_dena[pden_at(u, i, U)] = 0.0;
+            part_denc[pden_at(u, i, U)] = 0.0;
+        }
+        return;
+    }
+    // band-diagonal by rows: a_ij > 0 only for j == i and j == i + 1
+    bool offband = false;
+    for (int j = 0; j < N; j++)
+        offband |= act && (logA[i * N + j] != -INFINITY && j != i && j != i + 1);
+    const bool banded = !__any(offband);
+    double *snk = wave_sink(sink);
+    const double lz = logz[u];
+    if (banded)
+        logbackward_run<L, true>(N, T, delta, i, act, u, U, logA, logb + f0 * N, la + f0 * N, lbe + f0 * N,
+                                 gamma + f0 * N, lz, part_xi, part_dena, part_denc, snk);
+    else
+        logbackward_run<L, false>(N, T, delta, i, act, u, U, logA, logb + f0 * N, la + f0 * N, lbe + f0 * N,
+                                  gamma + f0 * N, lz, part_xi, part_dena, part_denc, snk);
 }
 
 } // namespace ghmm

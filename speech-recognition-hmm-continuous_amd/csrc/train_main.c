@@ -18,7 +18,9 @@
  * text, stopping rule and report, one feature stream.  The initial model is built on the host
  * (ghmm_init_model_full) or read with ghmm_hmm_read_full, each iteration is ghmm_estep_full on the
  * GPU and ghmm_mstep_full, and the model is written with ghmm_hmm_write_full (8-byte prefix).
- * P > 1 and GHMM_WORLD > 1 are refused.
+ * P > 1 and GHMM_WORLD > 1 are refused.  GHMM_LOG_TRAIN=1 takes ghmm_estep_full_log for every
+ * iteration (finite where a frame's linear densities underflow) and says so in one line of output;
+ * the report is the same.
  *
  * Several GPUs: start one process per GPU with
  *     GHMM_WORLD=<ranks> GHMM_RANK=<0..ranks-1> GHMM_COMM_ID=<a path unique to the job>
@@ -168,13 +170,17 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
     if ((rc = ghmm_stats_create_full(ctx, N, M, D, &stats))) die("statistics", rc);
     double lp[2] = {0.0, 0.0};
 
+    /* GHMM_LOG_TRAIN=1: every iteration's E-step in the log domain (ghmm_estep_full_log) */
+    const int log_train = env_int("GHMM_LOG_TRAIN", 0) != 0;
     printf("\r\nCreating HMM using Forward-Backward algorithm (Baum-Welch)");
+    if (log_train) printf("\r\nE-step in the log domain (GHMM_LOG_TRAIN)");
     double probab, old_probab = 1.0, variation; /* TFF:135-137 */
     int iteration = 0;
     do {
         iteration++;
         printf("\r\nStarting training sequence (%d utterances, %zu frames)", n_utt, frames);
-        if ((rc = ghmm_estep_full(ctx, fm, corpus, stats))) die("E-step", rc);
+        if ((rc = log_train ? ghmm_estep_full_log(ctx, fm, corpus, stats) : ghmm_estep_full(ctx, fm, corpus, stats)))
+            die("E-step", rc);
         if ((rc = ghmm_stats_loglik(ctx, stats, lp))) die("E-step", rc);
         probab = lp[0];
         printf("\r\nEnding training sequence");

@@ -118,6 +118,7 @@ SYMBOLS = {
     "ghmm_stats_len_full": (C.c_size_t, [C.c_int, C.c_int, C.c_int], False),
     "ghmm_stats_create_full": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
     "ghmm_estep_full": (C.c_int, [_vp, _vp, _vp, _vp], True),
+    "ghmm_estep_full_log": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_mstep_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
@@ -693,6 +694,11 @@ class Context:
         """TFF's E-step (ghmm_estep_full) into a stats_full vector; b / post / gamma stay in the
         workspace (fetch)"""
         _check(self.lib.ghmm_estep_full(self.h, fmodel.h, corpus.h, stats.h), self.lib)
+
+    def estep_full_log(self, fmodel, corpus, stats):
+        """the same E-step in the log domain (ghmm_estep_full_log): finite where estep_full's linear
+        densities underflow; afterwards fetch(BUF_B) is log b, BUF_ALPHA / BUF_BETA the log lattices"""
+        _check(self.lib.ghmm_estep_full_log(self.h, fmodel.h, corpus.h, stats.h), self.lib)
 
     def mstep_full(self, fmodel, stats):
         """TFF's M-step (ghmm_mstep_full: host numerics, then the model is set again)"""
