@@ -1069,6 +1069,110 @@ def test_long_utterances_against_oracle(G, ctx):
         obj.close()
 
 
+def _scores_against_oracle(got, hm, X, lens, what, must_be_finite=True):
+    """forward scores per utterance at fuzz_viterbi_case's bar: 1e-10 relative, or the oracle's
+    non-finite value itself"""
+    o = 0
+    for u, T in enumerate(lens):
+        ref = O.score(hm, X[o:o + T])
+        assert np.isfinite(ref) or not must_be_finite, f"{what} utterance {u}: the oracle's score is {ref!r}"
+        assert ((np.isnan(ref) and np.isnan(got[u])) or got[u] == ref
+                or abs(got[u] - ref) <= 1e-10 * abs(ref)), f"{what} T={T}: {got[u]!r} vs {ref!r}"
+        o += T
+
+
+def test_score_long_utterances_against_oracle(G, ctx):
+    """ghmm_score, ghmm_score_batch and ghmm_score_streams past 512 frames.  The score-only scan keeps
+    -sum_t log c_t as a product of mantissas and a sum of exponents in one accumulator per utterance
+    (log_product, ghmm_kernels.hpp), and folds the product's exponent back in every 512 values: 511
+    frames stay below the first fold, 512 and 513 sit on it, 1025 passes two, and at 4100 the
+    product of mantissas (about half a bit lost per frame) would have left the normal range had
+    nothing folded it.  16-lane groups with a band-diagonal and with a dense A."""
+    lens = [511, 512, 513, 1025, 4100, 17]
+    hm, X, lens = synth_case(G, 10, 8, 39, lens)
+    other = synth_case(G, 10, 8, 39, lens, perturb=0.2)[0]
+    dense, Xd, lensd = synth_case(G, 9, 4, 13, [513, 4100], dense_A=True)
+    dense2 = synth_case(G, 9, 4, 13, [513, 4100], dense_A=True, seed=4, perturb=0.2)[0]
+    for tag, hms, Xc, ln in (("banded", (hm, other), X, lens), ("dense", (dense, dense2), Xd, lensd)):
+        corpus = ctx.corpus(Xc, ln)
+        models = [ctx.model(h) for h in hms]
+        try:
+            _scores_against_oracle(ctx.score(models[0], corpus), hms[0], Xc, ln, f"{tag} score")
+            batch = ctx.score_batch(models, corpus)
+            for k, h in enumerate(hms):
+                _scores_against_oracle(batch[k], h, Xc, ln, f"{tag} score_batch word {k}", must_be_finite=k == 0)
+        finally:
+            for o in models + [corpus]:
+                o.close()
+    # two streams: the forward pass keeps c_t and takes its logarithms lane by lane afterwards
+    hm1, X1, ln = synth_case(G, 10, 8, 39, [513, 1025])
+    hm2, X2, _ = synth_case(G, 10, 4, 13, [513, 1025], first=50)
+    hm2.A[:] = hm1.A
+    models, corpora = [ctx.model(hm1), ctx.model(hm2)], [ctx.corpus(X1, ln), ctx.corpus(X2, ln)]
+    try:
+        ref = [O.score_streams([hm1, hm2], [X1[o:o + t], X2[o:o + t]]) for o, t in ((0, 513), (513, 1025))]
+        assert np.isfinite(ref).all()
+        assert_close(ctx.score_streams(models, corpora), ref, rtol=1e-9, what="two streams")
+    finally:
+        for o in models + corpora:
+            o.close()
+
+
+# log P of the E-step and of the row API is summed from c_t after the scan, by accumulators (log_product)
+# that take every 16th value: lane i of the utterance's 16-lane group (3 states: L = 16).
+#   site F, forward_utt's loop: lane i takes t = i, i + 16, ... of the whole utterance, ceil((T - i) / 16)
+#       values.  Reached by ghmm_forward (the row API) under either GHMM_OPT_KERNELS, and by ghmm_estep
+#       under GHMM_OPT_KERNELS = 1 (k_forward); not by ghmm_estep's default paths, whose forward scan
+#       leaves the logarithms to the combine pass.
+#   site C, combine_group's loop: the utterance is cut in CB_CH = 8 chunks (k_combine, GHMM_OPT_FUSED_SCAN
+#       = 2) or in SC_GROUPS / upb = 32 / 4 = 8 (k_scan_combine, the default: utterances of 160 frames
+#       or more get upb = 4), and lane i takes every 16th value of its chunk: about T / 128 values.
+#       Reached by ghmm_estep under the default and under GHMM_OPT_FUSED_SCAN = 2 on a band-diagonal A.
+#   T =   8 209: F 513 or 514 per lane (one fold)      C 64 or 65 per lane and chunk (none)
+#   T =  16 500: F 1 031 or 1 032 (two folds)          C 128 or 129 (none)
+#   T =  66 000: F 4 125                               C 8 250 / 16 = 515 or 516 (one fold)
+#   T = 282 000: F 17 625                              C 35 250 / 16 = 2 203 or 2 204 (four folds)
+# The product of mantissas loses about half a bit per value, so past some 2 044 values per accumulator
+# it leaves the normal range unless it is folded: the last length does that at both sites.
+PAST_512 = {"one_fold_per_lane": [8209, 16500], "one_fold_per_chunk": [66000], "underflow_per_chunk": [282000]}
+
+
+@pytest.mark.parametrize("name", sorted(PAST_512))
+def test_loglik_pieces_past_512_values_per_lane(G, ctx, name):
+    """log P per utterance (GHMM_BUF_LOGLIK) and summed (ghmm_stats_loglik) after ghmm_estep, and
+    GHMM_BUF_LOGLIK after ghmm_forward alone, against the oracle under every scan path: the one
+    launch (default), the paired scans with a separate combine launch (GHMM_OPT_FUSED_SCAN = 2) and
+    the reference's order (GHMM_OPT_KERNELS = 1).  3 x 1 x 2: a few MB at 282 000 frames."""
+    N, M, D = 3, 1, 2
+    hm, X, lens = synth_case(G, N, M, D, PAST_512[name])
+    off = np.concatenate([[0], np.cumsum(lens)])
+    ref = np.array([O.estep(hm, X[off[u]:off[u + 1]], lens[u:u + 1], dumps=False)[0][-2] for u in range(len(lens))])
+    ref_sum = O.estep(hm, X, lens, dumps=False)[0][-2]
+    assert np.isfinite(ref).all() and np.isfinite(ref_sum)
+    model, corpus = ctx.model(hm), ctx.corpus(X, lens)
+    stats = ctx.stats(N, M, D)
+    try:
+        for tag, opt, val in (("one launch", G.OPT_FUSED_SCAN, 0), ("separate launches", G.OPT_FUSED_SCAN, 2),
+                              ("reference order", G.OPT_KERNELS, 1)):
+            ctx.set_option(opt, val)
+            try:
+                ctx.estep(model, corpus, stats)
+                total, n = stats.loglik()
+                assert_close(ctx.fetch(G.BUF_LOGLIK, (len(lens),)), ref, what=f"{name}, {tag}: loglik after estep")
+                assert_close(total, ref_sum, what=f"{name}, {tag}: summed loglik")
+                assert n == len(lens)
+                if opt == G.OPT_FUSED_SCAN and val == 2:
+                    continue        # (ghmm_forward does not read this option)
+                ctx.emission(model, corpus, False)
+                ctx.forward(model, corpus)
+                assert_close(ctx.fetch(G.BUF_LOGLIK, (len(lens),)), ref, what=f"{name}, {tag}: loglik after forward")
+            finally:
+                ctx.set_option(opt, 0)
+    finally:
+        for o in (model, corpus, stats):
+            o.close()
+
+
 @pytest.mark.parametrize("seed", [68, 253, 437] + list(range(12)))
 def test_fuzz_short_utterances_against_oracle(G, ctx, seed):
     """Utterances of 1 .. N + 30 frames, some shorter than the model: no path into the last state.
