@@ -433,6 +433,36 @@ int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_sta
 /* The M-step (TFF:306-341): downloads the statistics and the model, applies ghmm_mstep_full_host
  * with GHMM_OPT_DELTA, and sets the model again.  Synchronises. */
 int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
+/* The same M-step (TFF:306-341) by HIP kernels on the context's stream, where `stats` lies (owned,
+ * wrapped or just all-reduced): nothing is downloaded, no model arithmetic runs on the host, the
+ * stream is not synchronised.  `fm` is rewritten in place; GHMM_OPT_DELTA is honoured; a diagonal
+ * statistics vector or one of another shape gives GHMM_ERR_ARG, a null model GHMM_ERR_ARG.
+ * M <= 256 (what the per-state kernel keeps in LDS): above it the call returns GHMM_ERR_UNSUPPORTED,
+ * launches nothing and leaves the model as it is (ghmm_mstep_full has no such cap).
+ * A, c, mean, the matrix slot and det are ghmm_mstep_full_host's BIT FOR BIT (a NaN's sign and payload
+ * aside): the same correctly rounded operations, uncontracted, in the same order.  Its quirks:
+ *   updating_transition_probab (TFF:1907-1929): a row with den_a == 0 is kept; inside i <= j <= i + delta
+ *     a = num_a / den_a, outside it 0.
+ *   updating_mix_param (TFF:1951-2000): a state with den_c == 0 is skipped, and its matrix slot, which
+ *     holds last iteration's INVERSE, is inverted again; otherwise c = num_c / den_c, mean = num_mu /
+ *     num_c, upper triangle = num_cov / num_c (num_c == 0: 0/0 entries), diagonal floored at 1e-5, mirrored.
+ *   changing_zero_coef (TFF:1377-1393) per state: weights floored at 1e-5, summed in index order, divided.
+ *   inv_cov_matrix (TFF:2058-2202) per Gaussian, D > 1: decomposition with its serial k sums; det = the
+ *     product of the pivots in index order, a NaN det becomes 0; det == 0 leaves the matrix un-inverted;
+ *     inv_triang_matrix by subdiagonals; the product sums (im*im)/d terms in increasing k and mirrors the
+ *     upper triangle.  D = 1: det = var, inverse = 1 / var, no treat_zero_det.
+ *   treat_zero_det (TFF:2226-2265) per state, D > 1: `sorting`'s stable decreasing order (strict <); a
+ *     Gaussian with det < 1e-20 takes the next donor's mean x1.05 (the donor's x0.95), matrix, det and half
+ *     its weight, serially over j, so a donor may already have been modified; the weights are renormalised;
+ *     M = 1 splits the Gaussian with itself.
+ * The derived constants are formed on the device as ghmm_mstep forms the diagonal ones: pow(2 pi, D/2)
+ * comes from the host as a kernel argument, den = that * sqrt(|det|), lk = log(c) - log(den), log a =
+ * a > 0 ? log(a) : -inf.  These three are NOT bit-equal to ghmm_fmodel_set's, which uses the host's
+ * pow(x, 0.5) and log: they agree to the last few ulp.
+ * The model's band flag (which recursions the next E-step takes) becomes `was banded && delta <= 1`, as
+ * in ghmm_mstep: the host does not see the new A, so the flag is conservative (a model set with a wider
+ * A keeps the general recursions).  Both launches count under GHMM_K_MSTEP. */
+int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
 
 /* -------------------------------------- several GPUs: the one collective */
 

@@ -298,4 +298,239 @@ k_gather_fmodels(int D, const fgather_src *__restrict__ src, double *__restrict_
     for (size_t k = threadIdx.x; k < n2; k += 256) inv_cov[o2 + k] = s.inv_cov[k];
 }
 
+// ------------------------------------------------ the trainer's M-step on the device (ghmm_mstep_full_dev)
+//
+// ghmm_mstep_full_host (csrc/ghmm_fulltrain.c: TFF:306-341) in two launches on the context's stream:
+//   k_fmstep_gauss  a block per Gaussian: updating_mix_param's quotients, the diagonal floor and the
+//                   mirror, then inv_cov_matrix (decomposition, calc_det, inv_triang_matrix, the
+//                   product) — or det = var, 1 / var at D = 1;
+//   k_fmstep_state  a block per state, afterwards: the weights and changing_zero_coef, treat_zero_det
+//                   (D > 1), the state's row of A, and den / lk / log A.
+// Every value the host route computes is computed here by the same IEEE operations in the same order,
+// so A, c, mean, the matrix slot and det come out bit-equal to the host's (NaN payloads aside).  That
+// needs three things.  (1) No contraction: the library is built with -ffp-contract=on, so both bodies
+// open with `#pragma clang fp contract(off)`; `/` on doubles is the correctly rounded division.
+// (2) Every sum over k or l runs in ONE lane, in the host's order; the lanes only spread independent
+// rows or entries.  (3) What the host does serially over Gaussians (sorting, the treat_zero_det walk,
+// the weight sums) runs in lane 0 on LDS copies; the walk is reduced there to a list of (receiver,
+// donor) pairs, and the D and D x D copies of each pair are then made by all lanes in the list's
+// order.  A lane owns the same coefficient (entry) in every pair, so a donor that an earlier pair has
+// modified is read as modified without a barrier.
+// LDS of k_fmstep_gauss: the covariance [D][D | 1] — its strict lower triangle becomes T in place
+// (decomposition reads an entry of cov only when it writes that entry of T), the diagonal and the
+// upper triangle stay, and give the matrix back where det == 0 — the inverse of T [D][D | 1], and the
+// pivots: (2 D (D | 1) + D) doubles, 38 016 bytes at D = 48.
+constexpr int FM_THREADS = 256;
+constexpr int FM_MAXM = 256;       // Gaussians per state k_fmstep_state holds in LDS (ghmm.h states it)
+constexpr double FM_FLOOR = 1.0e-5;    // TFF:38
+constexpr double FM_ZERO_DET = 1e-20;  // TFF:2242
+
+__host__ __device__ inline size_t fm_gauss_lds_bytes(int D) { return ((size_t)2 * D * (D | 1) + D) * sizeof(double); }
+
+// entry q of a row-major upper triangle (k <= l) of a D x D matrix
+__device__ inline void fm_tri(int q, int D, int &k, int &l)
+{
+    int r = 0, o = 0;
+    while (q - o >= D - r) {
+        o += D - r;
+        r++;
+    }
+    k = r;
+    l = r + (q - o);
+}
+
+__global__ void __launch_bounds__(FM_THREADS)
+k_fmstep_gauss(int N, int M, int D, const double *__restrict__ stats, double *__restrict__ mean,
+               double *__restrict__ inv_cov, double *__restrict__ det)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double fm_lds[];
+    const int g = blockIdx.x, i = g / M, tid = threadIdx.x, G = N * M, DS = D | 1, DT = D * (D + 1) / 2;
+    const double *den_c = stats + (size_t)N * N + N, *num_c = den_c + N, *num_mu = num_c + G;
+    const double *num_cov = num_mu + (size_t)G * D;
+    double *C = fm_lds, *IM = C + D * DS, *dd = IM + D * DS;
+    double *cv = inv_cov + (size_t)g * D * D;
+    // updating_mix_param (TFF:1951-2000); a state with den_c == 0 keeps its slot: last iteration's
+    // inverse, inverted again below
+    const bool upd = den_c[i] != 0.0;
+    if (upd) {
+        const double ncg = num_c[g];
+        const double *nc = num_cov + (size_t)g * DT;
+        for (int k = tid; k < D; k += FM_THREADS) mean[(size_t)g * D + k] = num_mu[(size_t)g * D + k] / ncg;
+        for (int q = tid; q < DT; q += FM_THREADS) {
+            int k, l;
+            fm_tri(q, D, k, l);
+            double v = nc[q] / ncg;
+            if (k == l && v < FM_FLOOR) v = FM_FLOOR; // (a NaN stays)
+            C[k * DS + l] = v;
+            C[l * DS + k] = v;
+        }
+    } else {
+        for (int e = tid; e < D * D; e += FM_THREADS) C[(e / D) * DS + e % D] = cv[e];
+    }
+    __syncthreads();
+    if (D == 1) { // TFF:330-334: det = var, inverse = 1 / var
+        if (tid == 0) {
+            det[g] = C[0];
+            cv[0] = 1.0 / C[0];
+        }
+        return;
+    }
+    // decomposition (TFF:2058-2096): a lane per row below the pivot, the pivot's own sum in another
+    // wave's lane; T[r][j] overwrites cov[r][j]
+    if (tid == 0) dd[0] = C[0];
+    for (int r = 1 + tid; r < D; r += FM_THREADS) C[r * DS] = C[r * DS] / C[0];
+    __syncthreads();
+    for (int j = 1; j < D; j++) {
+        if (tid == FM_THREADS - 1) {
+            double s = C[j * DS + j];
+            for (int k = 0; k < j; k++) s -= C[j * DS + k] * C[j * DS + k] * dd[k];
+            dd[j] = s;
+        }
+        for (int r = j + 1 + tid; r < D; r += FM_THREADS) {
+            double s = C[r * DS + j];
+            for (int k = 0; k < j; k++) s -= C[r * DS + k] * dd[k] * C[j * DS + k];
+            C[r * DS + j] = s;
+        }
+        __syncthreads();
+        for (int r = j + 1 + tid; r < D; r += FM_THREADS) C[r * DS + j] = C[r * DS + j] / dd[j];
+        __syncthreads();
+    }
+    // calc_det (TFF:2020-2032), every lane for itself; a NaN becomes 0 (TFF:2176)
+    double dt = 1.0;
+    for (int k = 0; k < D; k++) dt *= dd[k];
+    if (dt != dt) dt = 0.0;
+    if (tid == 0) det[g] = dt;
+    if (dt == 0.0) {
+        // quirk (TFF:2179): the matrix stays as it came, un-inverted
+        if (upd)
+            for (int q = tid; q < DT; q += FM_THREADS) {
+                int k, l;
+                fm_tri(q, D, k, l);
+                const double v = C[k * DS + l];
+                cv[k * D + l] = v;
+                cv[l * D + k] = v;
+            }
+        return;
+    }
+    // inv_triang_matrix (TFF:2118-2142) by subdiagonals, a lane per row
+    for (int k = tid; k < D; k += FM_THREADS) IM[k * DS + k] = 1.0;
+    __syncthreads();
+    for (int k = 0; k < D - 1; k++) {
+        for (int r = k + 1 + tid; r < D; r += FM_THREADS) {
+            const int j = r - k - 1;
+            double s = 0.0;
+            for (int l = j; l < r; l++) s -= C[r * DS + l] * IM[l * DS + j];
+            IM[r * DS + j] = s;
+        }
+        __syncthreads();
+    }
+    // the product (TFF:2183-2199): an entry of the upper triangle per lane, its k sum in order
+    for (int q = tid; q < DT; q += FM_THREADS) {
+        int a, b;
+        fm_tri(q, D, a, b);
+        double s = 0.0;
+        for (int k = b; k < D; k++) s += IM[k * DS + a] * IM[k * DS + b] / dd[k];
+        cv[a * D + b] = s;
+        cv[b * D + a] = s;
+    }
+}
+
+__global__ void __launch_bounds__(FM_THREADS)
+k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double norm2pi, int delta,
+               double *__restrict__ A, double *__restrict__ c, double *mean, double *inv_cov,
+               double *__restrict__ det, double *__restrict__ den, double *__restrict__ lk,
+               double *__restrict__ logA)
+{
+#pragma clang fp contract(off)
+    __shared__ double cw[FM_MAXM], dl[FM_MAXM];
+    __shared__ int idx[FM_MAXM], pj[FM_MAXM], pl[FM_MAXM];
+    __shared__ int npairs;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const double *num_a = stats, *den_a = num_a + (size_t)N * N, *den_c = den_a + N, *num_c = den_c + N;
+    // updating_transition_probab (TFF:1907-1929): a row with den_a == 0 is kept; 0 outside the band
+    const double da = den_a[i];
+    for (int j = tid; j < N; j += FM_THREADS) {
+        const size_t q = (size_t)i * N + j;
+        double a = A[q];
+        if (da != 0.0) {
+            a = (j >= i && j - i <= delta) ? num_a[q] / da : 0.0;
+            A[q] = a;
+        }
+        logA[q] = a > 0.0 ? log(a) : -INFINITY;
+    }
+    const double dc = den_c[i];
+    for (int m = tid; m < M; m += FM_THREADS) {
+        const size_t g = (size_t)i * M + m;
+        cw[m] = dc != 0.0 ? num_c[g] / dc : c[g];
+        dl[m] = det[g];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // changing_zero_coef (TFF:1377-1393)
+        double sum = 0.0;
+        for (int k = 0; k < M; k++) {
+            if (cw[k] < FM_FLOOR) cw[k] = FM_FLOOR;
+            sum += cw[k];
+        }
+        for (int k = 0; k < M; k++) cw[k] = cw[k] / sum;
+        int np = 0;
+        if (D > 1) {
+            // treat_zero_det (TFF:2226-2265).  sorting (TFF:1331-1356): adjacent swaps, strict '<',
+            // on the determinants as inv_cov_matrix left them
+            for (int k = 0; k < M; k++) idx[k] = k;
+            bool done = false;
+            while (!done) {
+                done = true;
+                for (int k = 0; k < M - 1; k++) {
+                    const int a = idx[k], b = idx[k + 1];
+                    if (dl[a] < dl[b]) {
+                        idx[k] = b;
+                        idx[k + 1] = a;
+                        done = false;
+                    }
+                }
+            }
+            // the walk: determinants and weights move here, means and matrices by the pairs below
+            int n = 0;
+            for (int j = 0; j < M; j++)
+                if (dl[j] < FM_ZERO_DET) {
+                    const int l = idx[n++];
+                    pj[np] = j;
+                    pl[np] = l;
+                    np++;
+                    dl[j] = dl[l];
+                    cw[l] = cw[l] / 2.0;
+                    cw[j] = cw[l];
+                }
+            sum = 0.0;
+            for (int j = 0; j < M; j++) sum += cw[j];
+            for (int j = 0; j < M; j++) cw[j] = cw[j] / sum;
+        }
+        npairs = np;
+    }
+    __syncthreads();
+    const size_t DD = (size_t)D * D;
+    for (int p = 0; p < npairs; p++) {
+        const size_t gj = (size_t)i * M + pj[p], gl = (size_t)i * M + pl[p];
+        for (int k = tid; k < D; k += FM_THREADS) {
+            const double v = mean[gl * D + k], up = v * 1.05;
+            mean[gj * D + k] = up;
+            mean[gl * D + k] = (gj == gl ? up : v) * 0.95; // (M = 1, or its own donor: split with itself)
+        }
+        if (gj != gl)
+            for (size_t e = tid; e < DD; e += FM_THREADS) inv_cov[gj * DD + e] = inv_cov[gl * DD + e];
+    }
+    // the derived constants, as the diagonal k_mstep forms them (ghmm_fmodel_set's on the host)
+    for (int m = tid; m < M; m += FM_THREADS) {
+        const size_t g = (size_t)i * M + m;
+        const double cg = cw[m], d = dl[m];
+        c[g] = cg;
+        det[g] = d;
+        const double dn = norm2pi * sqrt(fabs(d));
+        den[g] = dn;
+        lk[g] = log(cg) - log(dn);
+    }
+}
+
 } // namespace ghmm

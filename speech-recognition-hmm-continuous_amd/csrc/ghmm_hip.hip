@@ -2866,6 +2866,41 @@ extern "C" int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
     return rc;
 }
 
+// The same M-step by k_fmstep_gauss and k_fmstep_state (ghmm_fullcov.hpp), where the statistics lie:
+// nothing is downloaded and the stream is not synchronised.
+extern "C" int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    if ((rc = check_stats_full(fm, s))) return rc;
+    if (fm->M > FM_MAXM) {
+        ghmm_set_error("the device M-step takes up to %d Gaussians per state (asked: %d); ghmm_mstep_full "
+                       "has no such cap", FM_MAXM, fm->M);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    if (ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
+    // transitions are re-estimated inside the band i <= j <= i + delta only: a band-diagonal A stays
+    // band-diagonal exactly when that band is i, i + 1.  The new A is not seen here, so a model set
+    // with a wider A stays on the general recursions even if its new A happens to be band-diagonal.
+    fm->rec.banded = fm->rec.banded && ctx->delta <= 1;
+    const int N = fm->N, M = fm->M, D = fm->D;
+    const size_t lds = fm_gauss_lds_bytes(D);
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_fmstep_gauss, dim3((unsigned)(N * M)), dim3(FM_THREADS), lds, ctx->stream, N, M, D,
+                           s->v, fm->mean, fm->inv_cov, fm->det);
+    }
+    if ((rc = launch_ok("k_fmstep_gauss"))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_fmstep_state, dim3((unsigned)N), dim3(FM_THREADS), 0, ctx->stream, N, M, D, s->v,
+                           pow(2.0 * M_PI, D / 2.0), (int)ctx->delta, fm->A, fm->c, fm->mean, fm->inv_cov,
+                           fm->det, fm->den, fm->lk, fm->logA);
+    }
+    return launch_ok("k_fmstep_state");
+}
+
 extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
                             double *score_host)
 {

@@ -20,7 +20,9 @@
  * GPU and ghmm_mstep_full, and the model is written with ghmm_hmm_write_full (8-byte prefix).
  * P > 1 and GHMM_WORLD > 1 are refused.  GHMM_LOG_TRAIN=1 takes ghmm_estep_full_log for every
  * iteration (finite where a frame's linear densities underflow) and says so in one line of output;
- * the report is the same.
+ * the report is the same.  GHMM_DEV_MSTEP=1 takes ghmm_mstep_full_dev for every iteration (the
+ * M-step stays on the stream) and says so in one line; above that call's cap on M it says so and
+ * goes back to ghmm_mstep_full.  The two variables combine freely.
  *
  * Several GPUs: start one process per GPU with
  *     GHMM_WORLD=<ranks> GHMM_RANK=<0..ranks-1> GHMM_COMM_ID=<a path unique to the job>
@@ -174,6 +176,9 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
     const int log_train = env_int("GHMM_LOG_TRAIN", 0) != 0;
     printf("\r\nCreating HMM using Forward-Backward algorithm (Baum-Welch)");
     if (log_train) printf("\r\nE-step in the log domain (GHMM_LOG_TRAIN)");
+    /* GHMM_DEV_MSTEP=1: every iteration's M-step on the device (ghmm_mstep_full_dev) */
+    int dev_mstep = env_int("GHMM_DEV_MSTEP", 0) != 0;
+    if (dev_mstep) printf("\r\nM-step on the device (GHMM_DEV_MSTEP)");
     double probab, old_probab = 1.0, variation; /* TFF:135-137 */
     int iteration = 0;
     do {
@@ -188,7 +193,13 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
         printf("\r\nVerifying Probability: %f > Threshold: %f", variation, THRESHOLD);
         if (variation > THRESHOLD) {
             old_probab = probab;
-            if ((rc = ghmm_mstep_full(ctx, fm, stats))) die("M-step", rc);
+            if (dev_mstep && (rc = ghmm_mstep_full_dev(ctx, fm, stats)) == GHMM_ERR_UNSUPPORTED) {
+                printf("\r\nM-step on the host: %s", ghmm_last_error());
+                dev_mstep = 0;
+            } else if (dev_mstep && rc) {
+                die("M-step", rc);
+            }
+            if (!dev_mstep && (rc = ghmm_mstep_full(ctx, fm, stats))) die("M-step", rc);
         }
     } while (variation > THRESHOLD);
     printf("\r\nFinal Probability = %f\r\n\r\n", variation);

@@ -120,6 +120,7 @@ SYMBOLS = {
     "ghmm_estep_full": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_estep_full_log": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_mstep_full": (C.c_int, [_vp, _vp, _vp], True),
+    "ghmm_mstep_full_dev": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -703,6 +704,11 @@ class Context:
     def mstep_full(self, fmodel, stats):
         """TFF's M-step (ghmm_mstep_full: host numerics, then the model is set again)"""
         _check(self.lib.ghmm_mstep_full(self.h, fmodel.h, stats.h), self.lib)
+
+    def mstep_full_dev(self, fmodel, stats):
+        """the same M-step by HIP kernels on the stream (ghmm_mstep_full_dev): asynchronous, nothing
+        is downloaded; the model's parameters equal mstep_full's bit for bit"""
+        _check(self.lib.ghmm_mstep_full_dev(self.h, fmodel.h, stats.h), self.lib)
 
     def viterbi(self, model, corpus):
         path = np.empty(corpus.frames, dtype=np.int32)
