@@ -1,8 +1,8 @@
 """numpy restatement of the full-covariance log-domain E-step (include/ghmm.h, ghmm_estep_full_log)
 in a chosen float type, long double by default.  Shared by test_fullestep_log_host.py, which pins it
 to the long-double LINEAR E-step restatement (fulltrain_ref.estep), and by test_fullestep_log_gpu.py,
-which holds the HIP kernels against it.  Plain numpy, no GPU.  log_emission, lse and lattice_bound
-are fulllogscore_ref's.
+which holds the HIP kernels against it.  Plain numpy, no GPU.  The mixture terms e, their LSE, lse, the
+forward step and lattice_bound are fulllogscore_ref's; calc_mix_param's sums are fulltrain_ref.mix_sums.
 
     e_m = lk_m - aux_m / 2,  log b = LSE_m e_m                       (fulllogscore_ref.log_emission)
     post_t(i,m) = exp(e_m - log b_i(t)), or 0 where log b_i(t) = -inf
@@ -44,41 +44,18 @@ import numpy as np
 
 import fulllogscore_ref as LR
 import fulltrain_ref as R
-from fulllogscore_ref import lattice_bound, log_emission, lse  # noqa: F401  (re-exported)
+from fullcov_support import U53, ergodic, frames, need_extended, rand_fmodel
+from fulllogscore_ref import lse
 
 EM_MODEL_F64 = (8.7e-9, 1.5e-10)
-U53 = 2.0 ** -53
-
-
-def mixture_terms(hm, X, ft=np.longdouble):
-    """e[F][N][M] of log_emission's formula, Gaussian by Gaussian in ft"""
-    if ft is np.longdouble:
-        R.need_extended()
-    N, M, D = hm.N, hm.M, hm.D
-    Xf = np.asarray(X, dtype=np.float64).reshape(-1, D).astype(ft)
-    e = np.empty((len(Xf), N, M), ft)
-    two_pi = ft(2.0 * np.pi)
-    with np.errstate(all="ignore"):
-        for i in range(N):
-            for k in range(M):
-                dif = Xf - hm.mean[i, k].astype(ft)
-                t = dif @ hm.inv_cov[i, k].astype(ft)
-                aux = np.einsum("fi,fi->f", dif, t)
-                den = two_pi ** ft(D / 2.0) * np.sqrt(np.abs(ft(hm.det[i, k])))
-                lk = np.log(ft(hm.c[i, k])) - np.log(den)
-                e[:, i, k] = lk - aux * ft(0.5)
-    return e
 
 
 def emission(hm, X, ft=np.longdouble):
-    """(log b[F][N], post[F][N][M], e[F][N][M]) in ft; log b as log_emission forms it from e"""
-    e = mixture_terms(hm, X, ft)
-    with np.errstate(all="ignore"):
-        m = np.where(np.isnan(e), ft(-np.inf), e).max(-1) if e.shape[0] else np.zeros(e.shape[:2], ft)
-        s = np.exp(e - m[..., None]).sum(-1)
-        logb = np.where(m == -np.inf, ft(-np.inf), m + np.log(s))
-        post = posteriors(e, logb)
-    return logb, post, e
+    """(log b[F][N], post[F][N][M], e[F][N][M]) in ft; log b is fulllogscore_ref.log_emission's: the same
+    two calls"""
+    e = LR.mixture_terms(hm, X, ft)
+    logb = LR.mixture_lse(e)
+    return logb, posteriors(e, logb), e
 
 
 def posteriors(e, logb):
@@ -107,7 +84,7 @@ def lattice_fb(A, logb, delta=1, ft=np.longdouble):
     """one utterance from its log b[T][N] (any float type; widened to ft).  Returns a dict: la, lbe,
     gamma [T][N], xi[N][N] = sum_{t<T-1} xi_t inside the band, logP, logZ, and V, La of the bounds"""
     if ft is np.longdouble:
-        R.need_extended()
+        need_extended()
     A = np.asarray(A, dtype=np.float64)
     N = A.shape[0]
     lb = np.asarray(logb).astype(ft).reshape(-1, N)
@@ -116,15 +93,12 @@ def lattice_fb(A, logb, delta=1, ft=np.longdouble):
            "xi": np.zeros((N, N), ft), "logP": ft(0), "logZ": ft(0), "V": 0.0, "La": 0.0, "T": T}
     if T == 0:
         return out
-    idx = np.arange(N)
     with np.errstate(all="ignore"):
-        terms = A > 0
-        la_A = np.log(np.where(terms, A, 1.0).astype(ft))
+        terms, la_A = LR.log_transitions(A, ft)
         la, lbe = out["la"], out["lbe"]
-        la[0] = np.where(idx == 0, ft(0), ft(-np.inf)) + lb[0]
-        for t in range(1, T):
-            la[t] = lse(la[t - 1][:, None] + la_A, terms) + lb[t]
-        lbe[T - 1] = np.where(idx == N - 1, ft(0), ft(-np.inf))
+        for t, row in enumerate(LR.forward_rows(terms, la_A, lb)):
+            la[t] = row
+        lbe[T - 1] = np.where(np.arange(N) == N - 1, ft(0), ft(-np.inf))
         w = np.zeros((T, N), ft)        # w[t] = log b(t+1) + lbe(t+1)
         for t in range(T - 2, -1, -1):
             w[t] = lb[t + 1] + lbe[t + 1]
@@ -148,7 +122,7 @@ def estep(hm, X, lens, delta=1, ft=np.longdouble, logb=None, post=None):
     dict like fulltrain_ref.estep's: logb, post [F][N][M], gamma, la, lbe [F][N], loglik[U], logZ[U],
     utt (the per-utterance lattice_fb dicts) and stats."""
     if ft is np.longdouble:
-        R.need_extended()
+        need_extended()
     N, M, D = hm.N, hm.M, hm.D
     lens = [int(T) for T in lens]
     F = sum(lens)
@@ -162,7 +136,6 @@ def estep(hm, X, lens, delta=1, ft=np.longdouble, logb=None, post=None):
     st = {"num_a": np.zeros((N, N), ft), "den_a": np.zeros(N, ft), "den_c": np.zeros(N, ft)}
     gamma, la, lbe = (np.zeros((F, N), ft) for _ in range(3))
     ll, lz, utt = np.zeros(len(lens), ft), np.zeros(len(lens), ft), []
-    iu = np.triu_indices(D)
     o = 0
     with np.errstate(all="ignore"):
         for u, T in enumerate(lens):
@@ -174,30 +147,11 @@ def estep(hm, X, lens, delta=1, ft=np.longdouble, logb=None, post=None):
             st["den_a"] += r["gamma"][:-1].sum(0)
             st["den_c"] += r["gamma"].sum(0)
             o += T
-        w = gamma[:, :, None] * post
-        st["num_c"] = w.sum(0)
-        st["num_mu"] = np.einsum("fnm,fd->nmd", w, Xf)
-        cov = np.zeros((N, M, len(iu[0])), ft)
-        for i in range(N):
-            for k in range(M):
-                dif = Xf - hm.mean[i, k].astype(ft)
-                cov[i, k] = np.einsum("f,fk,fk->k", w[:, i, k], dif[:, iu[0]], dif[:, iu[1]])
-        st["num_cov"] = cov
+        st.update(R.mix_sums(gamma[:, :, None] * post, Xf, hm.mean, ft))
         st["loglik"] = ll.sum() if len(lens) else ft(0)
         st["n_utt"] = ft(len(lens))
     return {"logb": logb, "post": post, "gamma": gamma, "la": la, "lbe": lbe, "loglik": ll, "logZ": lz,
             "utt": utt, "stats": st}
-
-
-def em_trajectory_log(G, X, lens, N, M, iterations, ft):
-    """fulltrain_ref.em_trajectory with this E-step"""
-    hm = G.HostFullModel.init_from(X, lens, N, M)
-    trace = []
-    for _ in range(iterations):
-        st = estep(hm, X, lens, 1, ft)["stats"]
-        trace.append(float(st["loglik"]))
-        hm = hm.mstep(R.pack(st), delta=1)
-    return trace, hm
 
 
 # ------------------------------------------------ the shapes the GPU tests run
@@ -211,7 +165,7 @@ EMPTY_DELTAS = (0, 2, 3)
 def make_empty_case(G):
     N, M, D, lens = EMPTY_CASE
     rng = np.random.default_rng(77)
-    hm = LR.rand_fmodel(G, rng, N, M, D, LR.ergodic(rng, N))
-    X = LR.frames(rng, hm, lens)
+    hm = rand_fmodel(G, rng, N, M, D, ergodic(rng, N), spread=1.0, asym=True)
+    X = frames(rng, hm, lens)
     X[5] += 60.0
     return hm, X, np.asarray(lens, dtype=np.int32)

@@ -25,29 +25,35 @@ test_fulllogscore_host.test_float64_spread (which prints it and holds it below 1
 """
 import numpy as np
 
-from fulltrain_ref import need_extended
+from fullcov_support import banded, ergodic, frames, need_extended, offsets, rand_fmodel
+from fulltrain_ref import gaussians
+
+
+def mixture_terms(hm, X, ft=np.longdouble):
+    """e[F][N][M] of the formula above, Gaussian by Gaussian in ft (fulltrain_ref.gaussians)"""
+    if ft is np.longdouble:
+        need_extended()
+    Xf = np.asarray(X, dtype=np.float64).reshape(-1, hm.D).astype(ft)
+    e = np.empty((len(Xf), hm.N, hm.M), ft)
+    with np.errstate(all="ignore"):
+        for i, k, aux, den in gaussians(hm, Xf, ft):
+            lk = np.log(ft(hm.c[i, k])) - np.log(den)
+            e[:, i, k] = lk - aux * ft(0.5)
+    return e
+
+
+def mixture_lse(e):
+    """log b[F][N] from e[F][N][M]"""
+    ft = e.dtype.type
+    with np.errstate(all="ignore"):
+        m = np.where(np.isnan(e), ft(-np.inf), e).max(-1)
+        s = np.exp(e - m[..., None]).sum(-1)
+        return np.where(m == -np.inf, ft(-np.inf), m + np.log(s))
 
 
 def log_emission(hm, X, ft=np.longdouble):
     """log b[F][N] of a HostFullModel in ft"""
-    if ft is np.longdouble:
-        need_extended()
-    N, M, D = hm.N, hm.M, hm.D
-    Xf = np.asarray(X, dtype=np.float64).reshape(-1, D).astype(ft)
-    e = np.empty((len(Xf), N, M), ft)
-    two_pi = ft(2.0 * np.pi)
-    with np.errstate(all="ignore"):
-        for i in range(N):
-            for k in range(M):
-                dif = Xf - hm.mean[i, k].astype(ft)
-                t = dif @ hm.inv_cov[i, k].astype(ft)             # t_i = sum_j dif[j] inv_cov[j][i]
-                aux = np.einsum("fi,fi->f", dif, t)
-                den = two_pi ** ft(D / 2.0) * np.sqrt(np.abs(ft(hm.det[i, k])))
-                lk = np.log(ft(hm.c[i, k])) - np.log(den)
-                e[:, i, k] = lk - aux * ft(0.5)
-        m = np.where(np.isnan(e), ft(-np.inf), e).max(-1)
-        s = np.exp(e - m[..., None]).sum(-1)
-        return np.where(m == -np.inf, ft(-np.inf), m + np.log(s))
+    return mixture_lse(mixture_terms(hm, X, ft))
 
 
 def lse(x, terms=None):
@@ -61,6 +67,23 @@ def lse(x, terms=None):
         return m + np.log(np.exp(x - mm).sum(0))
 
 
+def log_transitions(A, ft):
+    """(the mask a_ij > 0, log a_ij in ft with 0 where a_ij = 0)"""
+    terms = np.asarray(A, dtype=np.float64) > 0
+    return terms, np.log(np.where(terms, A, 1.0).astype(ft))
+
+
+def forward_rows(terms, la_A, lb):
+    """la_0, la_1, ... la_{T-1} in turn from lb = log b[T][N], T >= 1: the one forward step, which
+    fullestep_log_ref.lattice_fb takes too"""
+    ft = lb.dtype.type
+    la = np.where(np.arange(lb.shape[1]) == 0, ft(0), ft(-np.inf)) + lb[0]
+    yield la
+    for t in range(1, len(lb)):
+        la = lse(la[:, None] + la_A, terms) + lb[t]
+        yield la
+
+
 def lattice(A, logb, final_state, ft=np.longdouble, stats=None):
     """the score of one utterance from its log b[T][N] (any float type; widened to ft).  stats, a
     dict, receives V = the largest finite |la| and La = the largest finite |log a_ij|."""
@@ -68,26 +91,18 @@ def lattice(A, logb, final_state, ft=np.longdouble, stats=None):
         need_extended()
     A = np.asarray(A, dtype=np.float64)
     N = A.shape[0]
-    T = len(logb)
-    if T == 0:
+    if len(logb) == 0:
         return ft(0)
-    lb = np.asarray(logb).astype(ft)
+    lb = np.asarray(logb).astype(ft).reshape(-1, N)
     with np.errstate(all="ignore"):
-        terms = A > 0
-        la_A = np.log(np.where(terms, A, 1.0).astype(ft))
-        la = np.where(np.arange(N) == 0, ft(0), ft(-np.inf)) + lb[0]
-        V = np.abs(la[np.isfinite(la)]).max(initial=0)
-        for t in range(1, T):
-            la = lse(la[:, None] + la_A, terms) + lb[t]
+        terms, la_A = log_transitions(A, ft)
+        V = 0
+        for la in forward_rows(terms, la_A, lb):
             V = max(V, np.abs(la[np.isfinite(la)]).max(initial=0))
         if stats is not None:
             stats["V"] = max(float(V), stats.get("V", 0.0))
             stats["La"] = max(float(np.abs(la_A).max()), stats.get("La", 0.0))
         return la[N - 1] if final_state else lse(la)
-
-
-def offsets(lens):
-    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
 def lattice_scores(A, logb, lens, final_state, ft=np.longdouble, stats=None):
@@ -100,20 +115,6 @@ def lattice_scores(A, logb, lens, final_state, ft=np.longdouble, stats=None):
 def logscore(hm, X, lens, final_state, ft=np.longdouble):
     """ghmm_logscore_full restated end to end: [U] in ft"""
     return lattice_scores(hm.A, log_emission(hm, X, ft), lens, final_state, ft)
-
-
-def rel_dist(got, ref):
-    """equal NaN and infinity patterns; the worst |got - ref| / |ref| over the finite ones (a finite
-    reference of 0, an empty utterance's score, must be met exactly)"""
-    got, ref = np.asarray(got, dtype=np.longdouble), np.asarray(ref, dtype=np.longdouble)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), ("NaN pattern differs", got, ref)
-    inf = np.isinf(ref)
-    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], ref[inf]), ("infinities differ", got, ref)
-    fin = np.isfinite(ref)
-    zero = fin & (ref == 0)
-    assert np.array_equal(got[zero], ref[zero])
-    fin &= ~zero
-    return float(np.max(np.abs(got[fin] - ref[fin]) / np.abs(ref[fin]), initial=0.0))
 
 
 # ------------------------------------------------ the lattice's rounding bound
@@ -138,42 +139,6 @@ def lattice_bound(T, N, V, La):
 
 
 # ------------------------------------------------ the shapes the GPU tests run
-
-def banded(rng, N):
-    A = np.zeros((N, N))
-    for i in range(N - 1):
-        A[i, i] = rng.uniform(0.5, 0.9)
-        A[i, i + 1] = 1.0 - A[i, i]
-    A[N - 1, N - 1] = 1.0
-    return A
-
-
-def ergodic(rng, N, zeros=0.4):
-    A = rng.uniform(0.05, 1.0, (N, N)) * (rng.uniform(size=(N, N)) >= zeros)
-    A[np.arange(N), (np.arange(N) + 1) % N] += 0.1  # every row reaches somewhere
-    return A / A.sum(1, keepdims=True)
-
-
-def rand_fmodel(G, rng, N, M, D, A, spread=1.0, base=None, word="w"):
-    c = rng.dirichlet(np.full(M, 3.0), N)
-    mean = (base if base is not None else 0.0) + rng.normal(0.0, spread, (N, M, D))
-    ic = np.empty((N, M, D, D))
-    for i in range(N):
-        for k in range(M):
-            Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-            ic[i, k] = (Q * rng.uniform(0.5, 2.0, D)) @ Q.T
-    ic[0, 0] += np.triu(rng.normal(0.0, 0.3, (D, D)), 1)  # non-symmetric: inv_cov[j][i] order
-    det = 1.0 / np.linalg.det(ic)
-    return G.HostFullModel(A, c, mean, ic, det, word=word)
-
-
-def frames(rng, hm, lens, scale=1.0):
-    F = int(np.sum(lens))
-    i = rng.integers(0, hm.N, F)
-    k = rng.integers(0, hm.M, F)
-    return hm.mean[i, k] + rng.normal(0.0, scale, (F, hm.D))
-
-
 # name: (N, M, D, dense A, utterance lengths); every list has T = 1 and a T < N
 CASES = {
     "l16_banded": (6, 2, 9, False, [70, 1, 33, 129, 3]),
@@ -194,7 +159,7 @@ def make_case(G, name):
     """(HostFullModel, X, lens) of a CASES entry; frame 5 lies 60 units from everything"""
     N, M, D, dense, lens = CASES[name]
     rng = np.random.default_rng(sorted(CASES).index(name) + 100)
-    hm = rand_fmodel(G, rng, N, M, D, ergodic(rng, N) if dense else banded(rng, N))
+    hm = rand_fmodel(G, rng, N, M, D, ergodic(rng, N) if dense else banded(rng, N), spread=1.0, asym=True)
     if name.startswith("c0"):
         hm.c[1] = 0.0
     if name.startswith("det0"):

@@ -14,30 +14,20 @@ import functools
 
 import numpy as np
 
+from fullcov_support import banded, rand_fmodel
+
 MCAP = 256          # ghmm_mstep_full_dev's cap on M (include/ghmm.h)
 FLOOR = 1.0e-5      # TFF:38
 ZERO_DET = 1e-20    # TFF:2242
 
 
 def rand_model(G, rng, N, M, D, dense=False):
-    """left-to-right (or dense) A, Dirichlet weights, inverse covariances with eigenvalues 0.5..2"""
-    A = np.zeros((N, N))
-    for i in range(N - 1):
-        A[i, i] = rng.uniform(0.5, 0.9)
-        A[i, i + 1] = 1.0 - A[i, i]
-    A[N - 1, N - 1] = 1.0
+    """left-to-right (or dense) A, Dirichlet weights, symmetric inverse covariances with eigenvalues 0.5..2"""
+    A = banded(rng, N)
     if dense:
         A = rng.random((N, N)) + 0.05
         A /= A.sum(1, keepdims=True)
-    c = rng.dirichlet(np.full(M, 3.0), N)
-    mean = rng.normal(0.0, 1.0, (N, M, D))
-    ic = np.empty((N, M, D, D))
-    for i in range(N):
-        for k in range(M):
-            Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-            ic[i, k] = (Q * rng.uniform(0.5, 2.0, D)) @ Q.T
-            ic[i, k] = (ic[i, k] + ic[i, k].T) / 2
-    return G.HostFullModel(A, c, mean, ic, 1.0 / np.linalg.det(ic), word="w")
+    return rand_fmodel(G, rng, N, M, D, A, spread=1.0, asym=False, symmetrise=True)
 
 
 def pd_sums(rng, N, M, D):

@@ -1,7 +1,7 @@
 """numpy restatement of the full-covariance recogniser's linear score (include/ghmm.h, ghmm_score_full;
 RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c) in a chosen float type, long
 double by default, and the shapes test_fullscore_gpu.py runs.  Shared with test_fullscore_host.py,
-which pins it to test_fullcov_gpu's float64 restatement and proves that the long cases reach what they
+which pins it to the float64 restatement (np_emission, np_logp) and proves that the long cases reach what they
 are there for.  Plain numpy, no GPU.
 
     b_j(t) = sum_m c_jm exp(-aux_jm / 2) / den_jm        (calc_symbol_probab + calc_gaus, RC:855-954)
@@ -11,8 +11,9 @@ are there for.  Plain numpy, no GPU.
     log P = -sum_t log c_t                               (calc_alpha + calc_probability, RC:733-836)
         no final-state term; an utterance of no frames scores 0
 
-With ft = float64 emission() and logp() are test_fullcov_gpu.np_emission and np_logp operation for
-operation (the same numpy calls on the same dtypes), which test_fullscore_host asserts bit for bit.
+With ft = float64 emission() and logp() are np_emission and np_logp below operation for operation (the
+same numpy calls on the same dtypes), which test_fullscore_host asserts bit for bit; the two pairs stay
+separate code: np_emission / np_logp belong to the float64 family that the recorded runs pin.
 
 The float64 form's relative distance from the long-double one, |x64 - xld| / |xld| over the finite
 scores, as test_fullscore_host.test_float64_spread_sweep and _long print it (and hold it below 1e-13):
@@ -32,9 +33,8 @@ import math
 
 import numpy as np
 
-import fulllogscore_ref as LR
-from fulllogscore_ref import banded, ergodic, frames, offsets, rand_fmodel  # noqa: F401  (one copy of each)
-from fulltrain_ref import need_extended
+from fullcov_support import banded, ergodic, frames, need_extended, offsets, rand_fmodel
+from fulltrain_ref import np_quadform
 
 
 def emission(hm, X, ft=np.longdouble):
@@ -87,7 +87,28 @@ def score(hm, X, lens, ft=np.longdouble):
     return lattice_scores(hm.A, emission(hm, X, ft), lens, ft)
 
 
-rel_dist = LR.rel_dist
+# ------------------------------------------------ the float64 family: RC restated on whole arrays
+
+def np_emission(hm, X):
+    """calc_symbol_probab + calc_gaus, RC:855-954 (det = 0 as the library documents it)"""
+    _, aux, den = np_quadform(hm, X)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        g = np.exp(aux * -0.5) / den[None]
+        return (g * hm.c[None]).sum(-1)
+
+
+def np_logp(A, b):
+    """calc_alpha (one-hot start) + calc_probability without a final-state term, RC:733-836"""
+    N = A.shape[0]
+    lp = 0.0
+    alpha = np.zeros(N)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        for t in range(b.shape[0]):
+            a = (np.eye(N)[0] if t == 0 else alpha @ A) * b[t]
+            c = 1.0 / a.sum()
+            alpha = a * c
+            lp -= np.log(c)
+    return lp
 
 
 # ------------------------------------------------ the score-only scan's accumulator on the CPU
@@ -133,7 +154,7 @@ def emission_case(G, D):
     """(HostFullModel 5 x 3 x D with one asymmetric inverse covariance, X, lens); frame 40 lies 60
     units from everything"""
     rng = np.random.default_rng(4000 + D)
-    hm = rand_fmodel(G, rng, 5, 3, D, banded(rng, 5))
+    hm = rand_fmodel(G, rng, 5, 3, D, spread=1.0, asym=True)
     X = frames(rng, hm, EMISSION_LENS, scale=1.5)
     X[FAR_FRAME] += 60.0
     return hm, X, np.asarray(EMISSION_LENS, dtype=np.int32)
@@ -158,7 +179,7 @@ def sweep_case(G, case):
     """(HostFullModel, X, lens) of a SWEEP entry, the utterances in shuffled order"""
     N, M, D, kind = case
     rng = np.random.default_rng(5000 + SWEEP.index(case))
-    hm = rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind))
+    hm = rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind), spread=1.0, asym=True)
     lens = rng.permutation(np.asarray(SWEEP_LENS, dtype=np.int32))
     assert not np.array_equal(np.argsort(-lens, kind="stable"), np.arange(len(lens)))
     return hm, frames(rng, hm, lens), lens
@@ -169,7 +190,8 @@ def batch_models(G):
     """the words that share BATCH_BASE's corpus with its own model: one of the 16-lane class (dense
     with zeros), one of the 64-lane class (banded)"""
     rng = np.random.default_rng(5100)
-    return tuple(rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind)) for N, M, D, kind in BATCH_EXTRA)
+    return tuple(rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind), spread=1.0, asym=True)
+                 for N, M, D, kind in BATCH_EXTRA)
 
 
 # 3. long utterances through the score-only scan: name -> (N, M, D, A, lengths, the lengths at which
@@ -190,8 +212,8 @@ def long_case(G, name):
     """(HostFullModel, a 3-state word of the same M and D for the batch, X, lens)"""
     N, M, D, kind, lens, _ = LONG[name]
     rng = np.random.default_rng(6000 + sorted(LONG).index(name))
-    hm = rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind))
-    small = rand_fmodel(G, rng, 3, M, D, banded(rng, 3))
+    hm = rand_fmodel(G, rng, N, M, D, make_A(rng, N, kind), spread=1.0, asym=True)
+    small = rand_fmodel(G, rng, 3, M, D, spread=1.0, asym=True)
     return hm, small, frames(rng, hm, lens), np.asarray(lens, dtype=np.int32)
 
 

@@ -20,40 +20,60 @@ An utterance of no frames adds nothing.
 
 The reference program computes in double, where exp overflows above 1.8e308; long double does not
 overflow there.  `+inf` is therefore read as "beyond the largest double": with ft = float64 that
-is the reference's own test, with ft = longdouble it marks the same densities."""
+is the reference's own test, with ft = longdouble it marks the same densities.
+
+gaussians() is the one Gaussian-by-Gaussian quadratic form in ft: the log-domain restatements
+(fulllogscore_ref, fullestep_log_ref) are built on it too.  np_estep and np_quadform are the separate,
+vectorised float64 family (with fullscore_ref.np_emission / np_logp and fullviterbi_ref.log_emission),
+which the host tests hold the ft family against and which is itself pinned to the recorded runs.
+
+The linear E-step's GPU cases (CASES, SWEEP, build) and the EM cases (EM_CASES, em_corpus,
+linear_trajectory) live here; a long-double reference is computed once a session."""
+import functools
+
 import numpy as np
+
+from fullcov_support import need_extended, rand_fmodel, walk_any
 
 STAT_KEYS = ("num_a", "den_a", "den_c", "num_c", "num_mu", "num_cov")
 _DBL_MAX = np.finfo(np.float64).max
 
 
-def have_extended():
-    """long double carries more than double here (x87: eps = 2^-63)"""
-    return np.finfo(np.longdouble).eps < 2.0 ** -60
-
-
-def need_extended():
-    assert have_extended(), ("long double is no wider than double on this platform: "
-                             f"eps = {np.finfo(np.longdouble).eps}")
+def gaussians(hm, Xf, ft):
+    """(i, k, aux[F], den) of every Gaussian in turn, over the frames Xf[F][D] (already of type ft)"""
+    two_pi = ft(2.0 * np.pi)  # TFF's 2 * M_PI: the double constant
+    for i in range(hm.N):
+        for k in range(hm.M):
+            dif = Xf - hm.mean[i, k].astype(ft)
+            t = dif @ hm.inv_cov[i, k].astype(ft)         # t_i = sum_j dif[j] inv_cov[j][i]
+            aux = np.einsum("fi,fi->f", dif, t)
+            den = two_pi ** ft(hm.D / 2.0) * np.sqrt(np.abs(ft(hm.det[i, k])))
+            yield i, k, aux, den
 
 
 def _densities(hm, Xf, ft):
     """c * gaus of every frame and Gaussian, [F][N][M]"""
-    N, M, D = hm.N, hm.M, hm.D
-    gm = np.zeros((len(Xf), N, M), ft)
-    two_pi = ft(2.0 * np.pi)  # TFF's 2 * M_PI: the double constant
+    gm = np.zeros((len(Xf), hm.N, hm.M), ft)
+    for i, k, aux, den in gaussians(hm, Xf, ft):
+        e = np.exp(aux * ft(-0.5))
+        g = e / den
+        if den != 0:
+            g = np.where((e > _DBL_MAX) | (g > _DBL_MAX), ft(1e20), g)
+        gm[:, i, k] = g * ft(hm.c[i, k])
+    return gm
+
+
+def mix_sums(w, Xf, mean, ft):
+    """calc_mix_param (TFF:1714-1753) on the weights w[F][N][M] = gamma * post: num_c, num_mu and
+    num_cov around `mean`, the upper triangle row-major"""
+    N, M, D = mean.shape
+    iu = np.triu_indices(D)
+    cov = np.zeros((N, M, len(iu[0])), ft)
     for i in range(N):
         for k in range(M):
-            dif = Xf - hm.mean[i, k].astype(ft)
-            t = dif @ hm.inv_cov[i, k].astype(ft)         # t_i = sum_j dif[j] inv_cov[j][i]
-            aux = np.einsum("fi,fi->f", dif, t)
-            den = two_pi ** ft(D / 2.0) * np.sqrt(np.abs(ft(hm.det[i, k])))
-            e = np.exp(aux * ft(-0.5))
-            g = e / den
-            if den != 0:
-                g = np.where((e > _DBL_MAX) | (g > _DBL_MAX), ft(1e20), g)
-            gm[:, i, k] = g * ft(hm.c[i, k])
-    return gm
+            dif = Xf - mean[i, k].astype(ft)
+            cov[i, k] = np.einsum("f,fk,fk->k", w[:, i, k], dif[:, iu[0]], dif[:, iu[1]])
+    return {"num_c": w.sum(0), "num_mu": np.einsum("fnm,fd->nmd", w, Xf), "num_cov": cov}
 
 
 def estep(hm, X, lens, delta=1, ft=np.longdouble):
@@ -67,7 +87,6 @@ def estep(hm, X, lens, delta=1, ft=np.longdouble):
     F = sum(lens)
     X = np.asarray(X, dtype=np.float64).reshape(F, D)
     Xf, A = X.astype(ft), hm.A.astype(ft)
-    iu = np.triu_indices(D)
     with np.errstate(all="ignore"):
         gm = _densities(hm, Xf, ft)
         b = gm.sum(-1)
@@ -100,15 +119,7 @@ def estep(hm, X, lens, delta=1, ft=np.longdouble):
             st["den_c"] += ga.sum(0)
             ll[u] = -np.log(c).sum() + np.log(al[T - 1, N - 1])
             o += T
-        w = gamma[:, :, None] * post
-        st["num_c"] = w.sum(0)
-        st["num_mu"] = np.einsum("fnm,fd->nmd", w, Xf)
-        cov = np.zeros((N, M, len(iu[0])), ft)
-        for i in range(N):
-            for k in range(M):
-                dif = Xf - hm.mean[i, k].astype(ft)
-                cov[i, k] = np.einsum("f,fk,fk->k", w[:, i, k], dif[:, iu[0]], dif[:, iu[1]])
-        st["num_cov"] = cov
+        st.update(mix_sums(gamma[:, :, None] * post, Xf, hm.mean, ft))
         st["loglik"] = ll.sum() if len(lens) else ft(0)
         st["n_utt"] = ft(len(lens))
     return {"b": b, "post": post, "gamma": gamma, "alpha": alpha, "beta": beta, "loglik": ll, "stats": st}
@@ -201,9 +212,9 @@ def em_corpus(N, M, D, U, T):
     return X, np.full(U, T, dtype=np.int32)
 
 
-def em_trajectory(G, X, lens, N, M, iterations, ft):
-    """`iterations` x (estep in ft, the library's host M-step) from HostFullModel.init_from:
-    the log-likelihood before every M-step and the last model"""
+def em_trajectory(G, X, lens, N, M, iterations, ft, estep=estep):
+    """`iterations` x (estep in ft: this module's, or fullestep_log_ref's; the library's host M-step)
+    from HostFullModel.init_from: the log-likelihood before every M-step and the last model"""
     hm = G.HostFullModel.init_from(X, lens, N, M)
     trace = []
     for _ in range(iterations):
@@ -211,3 +222,132 @@ def em_trajectory(G, X, lens, N, M, iterations, ft):
         trace.append(float(st["loglik"]))
         hm = hm.mstep(pack(st), delta=1)
     return trace, hm
+
+
+@functools.lru_cache(maxsize=None)
+def linear_trajectory(G, case):
+    """(corpus, lens, long-double trace, last model) of four iterations on EM_CASES[case], computed once"""
+    N, M, D, U, T = EM_CASES[case]
+    X, lens = em_corpus(N, M, D, U, T)
+    return (X, lens) + em_trajectory(G, X, lens, N, M, 4, np.longdouble)
+
+
+# ------------------------------------------------ the float64 family: TFF's E-step, vectorised
+
+def np_quadform(hm, X):
+    """(dif[F][N][M][D], aux[F][N][M], den[N][M]) in float64: aux = sum_i dif[i] (sum_j dif[j]
+    inv_cov[j][i]), den = pow(2 pi, D/2.0) * pow(|det|, 0.5)"""
+    dif = X[:, None, None, :] - hm.mean[None]
+    aux = np.einsum("fnmi,fnmi->fnm", dif, np.einsum("fnmj,nmji->fnmi", dif, hm.inv_cov))
+    return dif, aux, pow(2.0 * np.pi, hm.D / 2.0) * np.power(np.abs(hm.det), 0.5)
+
+
+def np_estep(hm, X, lens):
+    """calc_symbol_probab / calc_gaus (TFF:1775-1887), calc_alpha / calc_beta /
+    calc_transition_probab / calc_den_mix_coef / calc_probability (the diagonal trainer's, final
+    state included) and calc_mix_param (TFF:1714-1753), per utterance, summed"""
+    N, M, D = hm.N, hm.M, hm.D
+    G_, DT = N * M, D * (D + 1) // 2
+    iu = np.triu_indices(D)
+    with np.errstate(all="ignore"):
+        dif, aux, den = np_quadform(hm, X)
+        g = np.exp(aux * -0.5) / den[None]
+        g = np.where((g == np.inf) & (den[None] != 0.0), 1e20, g)
+        gm = g * hm.c[None]
+        b = gm.sum(-1)
+        post = np.where(b[..., None] != 0.0, gm / b[..., None], 0.0)
+    st = {"num_a": np.zeros((N, N)), "den_a": np.zeros(N), "den_c": np.zeros(N), "loglik": 0.0}
+    gamma = np.zeros((len(X), N))
+    A = hm.A
+    o = 0
+    for T in lens:
+        bb = b[o:o + T]
+        al = np.zeros((T, N)); c = np.zeros(T)
+        for t in range(T):
+            a = (np.eye(N)[0] if t == 0 else al[t - 1] @ A) * bb[t]
+            c[t] = 1.0 / a.sum()
+            al[t] = a * c[t]
+        be = np.zeros((T, N))
+        be[T - 1, N - 1] = c[T - 1]
+        for t in range(T - 2, -1, -1):
+            be[t] = (A @ (be[t + 1] * bb[t + 1])) * c[t]
+        ga = al * be / c[:, None]
+        gamma[o:o + T] = ga
+        for i in range(N):
+            for j in (i, i + 1):
+                if j < N:
+                    st["num_a"][i, j] += np.sum(al[:-1, i] * A[i, j] * bb[1:, j] * be[1:, j])
+        st["den_a"] += ga[:-1].sum(0)
+        st["den_c"] += ga.sum(0)
+        st["loglik"] += -np.log(c).sum() + np.log(al[T - 1, N - 1])
+        o += T
+    w = gamma[:, :, None] * post
+    st["num_c"] = w.sum(0)
+    st["num_mu"] = np.einsum("fnm,fd->nmd", w, X)
+    st["num_cov"] = np.einsum("fnm,fnmk,fnml->nmkl", w, dif, dif)[..., iu[0], iu[1]].reshape(N, M, DT)
+    st["n_utt"] = float(len(lens))
+    return b, post.reshape(len(X), G_), gamma, st
+
+
+# ------------------------------------------------ the linear E-step's shapes on the GPU
+
+LENS1 = (70, 1, 33, 129)        # 233 frames: three tiles of 64 and one with 41 frames left
+LENS2 = (90, 140, 64, 65)
+LONG64 = (312, 388, 400, 300, 351, 333, 379, 364)
+
+# id -> (N, M, D, lens, dense A, delta, clamped Gaussian)
+CASES = {}
+for _D in (8, 9, 17, 24, 25, 33, 40, 41, 47, 48):       # every DB of FC_POST, both sides of each boundary
+    CASES[f"db-5x3x{_D}"] = (5, 3, _D, LENS1, False, 1, True)
+for _N, _M, _D in ((17, 2, 13), (32, 2, 13), (33, 1, 13), (64, 2, 6)):  # lane classes 32 / 64, second grid row
+    CASES[f"lanes-{_N}x{_M}x{_D}"] = (_N, _M, _D, LENS2, False, 1, False)
+for _N, _M, _D in ((20, 2, 9), (40, 1, 5)):             # dense A: separate launches, general recursion
+    for _delta in (1, 2):
+        CASES[f"dense-{_N}x{_M}x{_D}-delta{_delta}"] = (_N, _M, _D, (60, 45, 81), True, _delta, False)
+for _delta in (0, 3):                                    # the band of num_a
+    CASES[f"band-6x2x7-delta{_delta}"] = (6, 2, 7, (50, 60, 9), True, _delta, False)
+CASES["short-12x2x6"] = (12, 2, 6, (40, 5, 1, 0, 30), False, 1, False)   # T < N, T = 1, T = 0
+CASES["paths-8x3x16"] = (8, 3, 16, LENS1, False, 1, False)
+for _N, _M, _D in ((64, 4, 1), (64, 8, 1), (64, 3, 3)):  # FSn 16 / 8 / 16 in k_fullstats
+    CASES[f"fsn-{_N}x{_M}x{_D}"] = (_N, _M, _D, (150, 200, 130), False, 1, False)
+CASES["large-64x2x48"] = (64, 2, 48, LONG64, False, 1, False)
+CASES["many-8x3x16"] = (8, 3, 16, (337, 120, 400, 256, 199, 311, 288, 143, 390, 222, 175, 264), False, 1, False)
+SWEEP = [k for k in CASES if k != "many-8x3x16"]
+
+
+@functools.lru_cache(maxsize=None)
+def build(G, name):
+    """(model, frames, lens, delta, the long-double E-step) of a case, computed once"""
+    N, M, D, lens, dense, delta, clamp = CASES[name]
+    rng = np.random.default_rng(sorted(CASES).index(name) + 100)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
+    if dense:
+        A = rng.random((N, N)) + 0.05
+        hm.A[:] = A / A.sum(1, keepdims=True)
+    X = walk_any(rng, hm, lens)
+    if clamp:
+        # a non-positive-definite Gaussian: its density overflows to +inf on every frame and is
+        # clamped to 1e20
+        hm.inv_cov[4, 2] = -np.eye(D)
+        hm.mean[4, 2] = hm.mean[4, 0] + 60.0
+    ref = estep(hm, X, lens, delta, np.longdouble)
+    ll = np.asarray(ref["loglik"], dtype=np.float64)
+    for u, T in enumerate(lens):
+        if T >= N:
+            assert np.isfinite(ll[u]), (name, u)    # no case compares NaN with NaN by accident
+    if clamp:
+        assert np.any(ref["post"][:, 4, 2] > 0)
+    return hm, X, np.asarray(lens, dtype=np.int32), delta, ref
+
+
+def fs_geometry(N, M, D):
+    """run_fullstats' launch geometry (ghmm_hip.hip): frames staged per pass and the Gaussians
+    [g0, g1] of every element batch"""
+    G_, E1 = N * M, 1 + D + D * (D + 1) // 2
+    batch = 256 * 8                                  # FS_THREADS * FS_EPT
+    gwmax = min(batch // E1 + 2, G_)
+    fsn = 32                                         # FS_FRAMES
+    while fsn > 1 and fsn * (D + 1 + gwmax) * 8 > 48 * 1024:
+        fsn //= 2
+    E = G_ * E1
+    return fsn, [(e0 // E1, (min(e0 + batch, E) - 1) // E1) for e0 in range(0, E, batch)]

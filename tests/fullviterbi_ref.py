@@ -5,34 +5,21 @@ test_fullviterbi_host.py and test_fullviterbi_gpu.py; the lattice itself is the 
 (oracle_lib.viterbi_lattice)."""
 import numpy as np
 
+from fulltrain_ref import np_quadform
+
 
 def log_emission(hm, X):
     """log b[F][N] of a HostFullModel:
         lk = log(c) - log(den),  den = pow(2 pi, D/2.0) * pow(|det|, 0.5)
         e_m = lk_m - aux_m / 2,  aux = sum_i dif[i] * (sum_j dif[j] * inv_cov[j][i])
         log b = m + log(sum_m exp(e_m - m)), m = max of the non-NaN e_m; -inf when m is -inf"""
-    D = hm.D
-    dif = X[:, None, None, :] - hm.mean[None]                       # F N M D
-    t = np.einsum("fnmj,nmji->fnmi", dif, hm.inv_cov)
-    aux = np.einsum("fnmi,fnmi->fnm", dif, t)
-    den = pow(2.0 * np.pi, D / 2.0) * np.power(np.abs(hm.det), 0.5)
+    _, aux, den = np_quadform(hm, X)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
         lk = np.log(hm.c) - np.log(den)
         e = lk[None] - 0.5 * aux
         m = np.where(np.isnan(e), -np.inf, e).max(-1)
         s = np.exp(e - m[..., None]).sum(-1)
         return np.where(m == -np.inf, -np.inf, m + np.log(s))
-
-
-def close_logb(got, ref, rtol):
-    """equal NaN and infinity patterns, finite values within rtol * (1 + |ref|)"""
-    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), "NaN pattern differs"
-    inf = np.isinf(ref)
-    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], ref[inf]), "infinities differ"
-    fin = np.isfinite(ref)
-    err = np.abs(got[fin] - ref[fin]) / (1.0 + np.abs(ref[fin]))
-    assert err.size == 0 or err.max() <= rtol, f"max error {err.max():.3e}"
 
 
 def lattice_margins(A, logb, path):

@@ -2,133 +2,25 @@
 recognition_continuous_full_fs.c) on the MI355X — GPU box only.
 
 Checked against recorded runs of the real reference (tests/golden/fullcov_recog.json,
-fullcov_synth13.npz, fullcov_hmm_result.txt: make_golden_fullcov.py), against a numpy restatement
-of calc_gaus / calc_alpha / calc_probability (RC:733-954) below, and against the pinned diagonal
-path.  Tolerances: densities rtol 1e-11 (below 1e-300 a subnormal keeps too few bits for a
+fullcov_synth13.npz, fullcov_hmm_result.txt: make_golden_fullcov.py), against the float64 numpy
+restatement of calc_gaus / calc_alpha / calc_probability (fullscore_ref.np_emission, np_logp), and
+against the pinned diagonal path.  Tolerances: densities rtol 1e-11 (below 1e-300 a subnormal keeps too few bits for a
 relative bound: there the values must agree to 1e-300 absolute, and be 0 exactly where numpy's
 are); scores of the reference within rel 1e-9 / abs 2e-6, as the diagonal recogniser's."""
-import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
 from _load import PKG_DIR
+from conftest import GOLDEN
+from fullcov_support import ctx  # noqa: F401  (the fixture)
+from fullcov_support import (FULL, check_blocks, close_b, code, frames, load_synth, rand_fmodel, same_kind_close,
+                             spoken_blocks)
+from fullscore_ref import np_emission, np_logp
 
 pytestmark = pytest.mark.gpu
-
-FULL = json.load(open(os.path.join(GOLDEN, "fullcov_recog.json")))
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-# ------------------------------------------------------------- restatement of RC
-
-def np_emission(hm, X):
-    """calc_symbol_probab + calc_gaus, RC:855-954 (det = 0 as the library documents it)"""
-    D = hm.D
-    dif = X[:, None, None, :] - hm.mean[None]                       # F N M D
-    t = np.einsum("fnmj,nmji->fnmi", dif, hm.inv_cov)               # sum_j dif[j] inv_cov[j][i]
-    aux = np.einsum("fnmi,fnmi->fnm", dif, t)
-    den = pow(2.0 * np.pi, D / 2.0) * np.power(np.abs(hm.det), 0.5)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
-        g = np.exp(aux * -0.5) / den[None]
-        return (g * hm.c[None]).sum(-1)
-
-
-def np_logp(A, b):
-    """calc_alpha (one-hot start) + calc_probability without a final-state term, RC:733-836"""
-    N = A.shape[0]
-    lp = 0.0
-    alpha = np.zeros(N)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
-        for t in range(b.shape[0]):
-            a = (np.eye(N)[0] if t == 0 else alpha @ A) * b[t]
-            c = 1.0 / a.sum()
-            alpha = a * c
-            lp -= np.log(c)
-    return lp
-
-
-def close_b(got, ref):
-    fin = np.isfinite(ref)
-    assert np.array_equal(np.isnan(got), np.isnan(ref))
-    assert np.array_equal(got[~fin & ~np.isnan(ref)], ref[~fin & ~np.isnan(ref)])
-    assert np.array_equal(got[fin] == 0.0, ref[fin] == 0.0), "zeros differ"
-    assert np.allclose(got[fin], ref[fin], rtol=1e-11, atol=1e-300)
-
-
-def same_kind(got, ref, rtol=1e-9, atol=2e-6):
-    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), "NaN pattern differs"
-    inf = np.isinf(ref)
-    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], ref[inf]), "inf differs"
-    fin = np.isfinite(ref)
-    assert np.allclose(got[fin], ref[fin], rtol=rtol, atol=atol)
-
-
-def rand_fmodel(G, rng, N, M, D, spread=0.3, base=None, word="w", asym=False):
-    A = np.zeros((N, N))
-    for i in range(N - 1):
-        A[i, i] = rng.uniform(0.5, 0.9)
-        A[i, i + 1] = 1.0 - A[i, i]
-    A[N - 1, N - 1] = 1.0
-    c = rng.dirichlet(np.full(M, 3.0), N)
-    mean = (base if base is not None else 0.0) + rng.normal(0.0, spread, (N, M, D))
-    ic = np.empty((N, M, D, D))
-    for i in range(N):
-        for k in range(M):
-            Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-            ic[i, k] = (Q * rng.uniform(0.5, 2.0, D)) @ Q.T
-    if asym:  # a non-symmetric inverse pins inv_cov[j][i] (not [i][j]) in the inner sum
-        ic[0, 0] += np.triu(rng.normal(0.0, 0.3, (D, D)), 1)
-    det = 1.0 / np.linalg.det(ic)
-    return G.HostFullModel(A, c, mean, ic, det, word=word)
-
-
-def frames(rng, hm, lens, scale=1.0):
-    F = int(np.sum(lens))
-    i = rng.integers(0, hm.N, F)
-    k = rng.integers(0, hm.M, F)
-    return hm.mean[i, k] + rng.normal(0.0, scale, (F, hm.D))
-
-
-def bubble(p):
-    """sorting_probab, RC:968-995 (NaN-blind)"""
-    idx = list(range(len(p)))
-    done = False
-    while not done:
-        done = True
-        for i in range(len(p) - 1):
-            if p[idx[i]] < p[idx[i + 1]]:
-                idx[i], idx[i + 1] = idx[i + 1], idx[i]
-                done = False
-    return idx
-
-
-def fmt(x):
-    if np.isnan(x):
-        return "nan"
-    return f"{x:f}"
-
-
-def check_blocks(scores, words, blocks):
-    """scores[k, u]; blocks = the reference's printed rankings"""
-    for u, blk in enumerate(blocks):
-        order = bubble(scores[:, u])
-        assert [words[i] for i in order] == [w for w, _ in blk["ranking"]], blk["spoken"]
-        for i, (w, txt) in zip(order, blk["ranking"]):
-            if "nan" in txt or "inf" in txt:
-                assert fmt(scores[i, u]).lstrip("-") == txt.lstrip("-"), (blk["spoken"], w)
-            else:
-                assert scores[i, u] == pytest.approx(float(txt), rel=1e-9, abs=2e-6), (blk["spoken"], w)
 
 
 # ------------------------------------------------------------------- the tests
@@ -156,17 +48,7 @@ def test_shipped_end_to_end(G, tmp_path):
     ref = [l for l in open(os.path.join(GOLDEN, "fullcov_hmm_result.txt")).read().split("\n") if keep(l)]
     assert got == ref == sh["report"]
     # stdout: "<word> :  <score>" rows per spoken word
-    import re
-    blocks, cur = [], None
-    for line in p.stdout.decode().replace("\r", "").split("\n"):
-        m = re.match(r"Spoken word: (\S+)", line)
-        if m:
-            cur = {"spoken": m.group(1), "ranking": []}
-            blocks.append(cur)
-            continue
-        m = re.match(r"(\S+) :  (\S+) $", line)
-        if m and cur is not None:
-            cur["ranking"].append([m.group(1), m.group(2)])
+    blocks = spoken_blocks(p.stdout.decode())
     assert len(blocks) == len(sh["blocks"]) == 13
     for g, r in zip(blocks, sh["blocks"]):
         assert g["spoken"] == r["spoken"]
@@ -179,23 +61,6 @@ def test_shipped_end_to_end(G, tmp_path):
     # fewer than 7 arguments: RC's usage text
     p = subprocess.run([exe, "1", ml], stdout=subprocess.PIPE, timeout=60)
     assert p.returncode == 1 and p.stdout.startswith(b"Usage: recognition_continuous_full ")
-
-
-def load_synth(G):
-    d = np.load(os.path.join(GOLDEN, "fullcov_synth13.npz"))
-    sy = FULL["synthetic"]
-    D = 16
-    iu = np.triu_indices(D)
-    hms, Xs = [], []
-    for w in sy["words"]:
-        t = d[w + ".inv_cov_triu"].astype(np.float64)
-        ic = np.zeros(t.shape[:2] + (D, D))
-        ic[..., iu[0], iu[1]] = t
-        ic[..., iu[1], iu[0]] = t
-        hms.append(G.HostFullModel(d[w + ".A"], d[w + ".c"].astype(np.float64),
-                                   d[w + ".mean"].astype(np.float64), ic, d[w + ".det"], word=w))
-        Xs.append(d[w + ".X"].astype(np.float64))
-    return sy, hms, Xs
 
 
 def test_synthetic_reference_run(G, ctx):
@@ -236,7 +101,7 @@ def test_score_has_no_final_state_term(G, ctx):
     """log P = -sum_t log c_t (RC:822-836); a frame whose densities are all 0 gives -inf when it is
     the utterance's last frame and NaN when one follows it."""
     rng = np.random.default_rng(11)
-    hm = rand_fmodel(G, rng, 6, 2, 9, spread=0.5)
+    hm = rand_fmodel(G, rng, 6, 2, 9, spread=0.5, asym=False)
     lens = [50, 31, 1, 80, 12, 40]
     X = frames(rng, hm, lens, scale=0.7)
     off = np.concatenate([[0], np.cumsum(lens)])
@@ -248,7 +113,7 @@ def test_score_has_no_final_state_term(G, ctx):
     b = np_emission(hm, X)
     ref = np.array([np_logp(hm.A, b[off[u]:off[u + 1]]) for u in range(len(lens))])
     assert got[0] == -np.inf and got[2] == -np.inf and np.isnan(got[3])
-    same_kind(got, ref, rtol=1e-11, atol=0)
+    same_kind_close(got, ref, rtol=1e-11, atol=0)
     fm.close()
     corpus.close()
 
@@ -259,7 +124,7 @@ def test_cross_check_with_diagonal_path(G, ctx):
     gives the same value on both paths."""
     rng = np.random.default_rng(21)
     N, M, D = 7, 3, 12
-    hf = rand_fmodel(G, rng, N, M, D, spread=0.8)
+    hf = rand_fmodel(G, rng, N, M, D, spread=0.8, asym=False)
     iv = rng.uniform(0.5, 2.0, (N, M, D))
     hf.inv_cov = np.zeros((N, M, D, D))
     hf.inv_cov[..., np.arange(D), np.arange(D)] = iv
@@ -287,7 +152,7 @@ def test_cross_check_with_diagonal_path(G, ctx):
     llf = ctx.score_full(fm, corpus)
     last = np.cumsum(lens) - 1
     with np.errstate(divide="ignore", invalid="ignore"):
-        same_kind(llf, lld - np.log(alpha[last, N - 1]), rtol=1e-11, atol=0)
+        same_kind_close(llf, lld - np.log(alpha[last, N - 1]), rtol=1e-11, atol=0)
     fm.close()
     corpus.close()
 
@@ -295,7 +160,7 @@ def test_cross_check_with_diagonal_path(G, ctx):
 def test_batch_equals_word_by_word(G, ctx):
     rng = np.random.default_rng(31)
     base = rng.normal(0.0, 1.0, (1, 1, 9))
-    hms = [rand_fmodel(G, rng, n, 2, 9, spread=0.6, base=base) for n in (6, 3, 17, 6, 40, 1, 9)]
+    hms = [rand_fmodel(G, rng, n, 2, 9, spread=0.6, base=base, asym=False) for n in (6, 3, 17, 6, 40, 1, 9)]
     lens = [33, 80, 1, 57, 120, 15, 64, 200, 9]
     X = frames(rng, hms[0], lens, scale=1.0)
     X[100] += 300.0
@@ -311,40 +176,35 @@ def test_batch_equals_word_by_word(G, ctx):
 
 def test_refusals(G, ctx):
     rng = np.random.default_rng(41)
-
-    def code(fn):
-        with pytest.raises(G.GhmmError) as e:
-            fn()
-        return e.value.code
-    assert code(lambda: ctx.full_model(rand_fmodel(G, rng, 65, 1, 4))) == G.ERR_UNSUPPORTED
-    assert code(lambda: ctx.full_model(rand_fmodel(G, rng, 3, 1, 49))) == G.ERR_UNSUPPORTED
+    assert code(G, lambda: ctx.full_model(rand_fmodel(G, rng, 65, 1, 4, spread=0.3, asym=False))) == G.ERR_UNSUPPORTED
+    assert code(G, lambda: ctx.full_model(rand_fmodel(G, rng, 3, 1, 49, spread=0.3, asym=False))) == G.ERR_UNSUPPORTED
     # the widest model built still works
     for N, D in ((64, 5), (4, 48)):
-        hm = rand_fmodel(G, rng, N, 1, D, spread=0.3)
+        hm = rand_fmodel(G, rng, N, 1, D, spread=0.3, asym=False)
         lens = [70, 40]
         X = frames(rng, hm, lens, scale=0.5)
         fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
         b = np_emission(hm, X)
         off = [0, 70, 110]
         ref = [np_logp(hm.A, b[off[u]:off[u + 1]]) for u in range(2)]
-        same_kind(ctx.score_full(fm, corpus), ref, rtol=1e-11, atol=0)
+        same_kind_close(ctx.score_full(fm, corpus), ref, rtol=1e-11, atol=0)
         fm.close()
         corpus.close()
-    hm = rand_fmodel(G, rng, 5, 2, 6)
-    h3 = rand_fmodel(G, rng, 5, 3, 6)
-    h7 = rand_fmodel(G, rng, 5, 2, 7)
+    hm = rand_fmodel(G, rng, 5, 2, 6, spread=0.3, asym=False)
+    h3 = rand_fmodel(G, rng, 5, 3, 6, spread=0.3, asym=False)
+    h7 = rand_fmodel(G, rng, 5, 2, 7, spread=0.3, asym=False)
     X = frames(rng, hm, [30, 20])
     fm, f3, f7 = ctx.full_model(hm), ctx.full_model(h3), ctx.full_model(h7)
     corpus = ctx.corpus(X, [30, 20])
-    assert code(lambda: ctx.score_full_batch([fm, f3], corpus)) == G.ERR_UNSUPPORTED  # M differs
-    assert code(lambda: ctx.score_full_batch([fm, f7], corpus)) == G.ERR_UNSUPPORTED  # D differs
-    assert code(lambda: ctx.score_full(f7, corpus)) == G.ERR_ARG                      # corpus D
-    assert code(lambda: ctx.emission_full(f7, corpus)) == G.ERR_ARG
+    assert code(G, lambda: ctx.score_full_batch([fm, f3], corpus)) == G.ERR_UNSUPPORTED  # M differs
+    assert code(G, lambda: ctx.score_full_batch([fm, f7], corpus)) == G.ERR_UNSUPPORTED  # D differs
+    assert code(G, lambda: ctx.score_full(f7, corpus)) == G.ERR_ARG                      # corpus D
+    assert code(G, lambda: ctx.emission_full(f7, corpus)) == G.ERR_ARG
     ctx.set_option(G.OPT_ROBUST, 1)
     try:
-        assert code(lambda: ctx.score_full(fm, corpus)) == G.ERR_UNSUPPORTED
-        assert code(lambda: ctx.emission_full(fm, corpus)) == G.ERR_UNSUPPORTED
-        assert code(lambda: ctx.score_full_batch([fm], corpus)) == G.ERR_UNSUPPORTED
+        assert code(G, lambda: ctx.score_full(fm, corpus)) == G.ERR_UNSUPPORTED
+        assert code(G, lambda: ctx.emission_full(fm, corpus)) == G.ERR_UNSUPPORTED
+        assert code(G, lambda: ctx.score_full_batch([fm], corpus)) == G.ERR_UNSUPPORTED
     finally:
         ctx.set_option(G.OPT_ROBUST, 0)
     # the workspace after ghmm_emission_full belongs to no diagonal model
@@ -353,8 +213,8 @@ def test_refusals(G, ctx):
     ctx.emission(dm, corpus, False)
     ctx.forward(dm, corpus)
     ctx.emission_full(fm, corpus)
-    assert code(lambda: ctx.forward(dm, corpus)) == G.ERR_ARG
-    assert code(lambda: ctx.fetch(G.BUF_BETA, (corpus.frames, 5))) == G.ERR_ARG
+    assert code(G, lambda: ctx.forward(dm, corpus)) == G.ERR_ARG
+    assert code(G, lambda: ctx.fetch(G.BUF_BETA, (corpus.frames, 5))) == G.ERR_ARG
     for o in (fm, f3, f7, dm, corpus):
         o.close()
 
@@ -364,7 +224,7 @@ def test_vocabulary_larger_than_one_tile(G, ctx):
     the concatenated vocabulary spans many emission tiles."""
     rng = np.random.default_rng(51)
     base = rng.normal(0.0, 1.5, (1, 1, 16))
-    hms = [rand_fmodel(G, rng, 15, 5, 16, spread=0.5, base=base, word=f"w{k}") for k in range(50)]
+    hms = [rand_fmodel(G, rng, 15, 5, 16, spread=0.5, base=base, word=f"w{k}", asym=False) for k in range(50)]
     lens = rng.integers(20, 90, 240)
     X = base[0, 0] + rng.normal(0.0, 1.0, (int(lens.sum()), 16))
     corpus = ctx.corpus(X, lens)
@@ -377,6 +237,6 @@ def test_vocabulary_larger_than_one_tile(G, ctx):
     for u in (0, 101, 239):
         Xu = X[off[u]:off[u + 1]]
         ref = [np_logp(h.A, np_emission(h, Xu)) for h in hms]
-        same_kind(batch[:, u], ref, rtol=1e-11, atol=0)
+        same_kind_close(batch[:, u], ref, rtol=1e-11, atol=0)
     for o in fms + [corpus]:
         o.close()

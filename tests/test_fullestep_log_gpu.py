@@ -7,11 +7,10 @@ test_fullestep_log_host.py; the bounds are derived in that module's docstring.
              restatement with log b's 1e-11 (1 + |ref|) carried into the exponent
   lattice    the long-double recursion run on the DEVICE's own log b: la, lbe, log P inside
              fulllogscore_ref.lattice_bound, gamma and the transition sums inside the expm1(E) bounds
-  statistics test_fullestep_gpu.check_stats_bound on the device's own gamma and post
+  statistics fullcov_support.check_stats_bound on the device's own gamma and post
   the point  a far frame in every utterance: ghmm_estep_full's loglik is not finite, this call's
              statistics are, and the M-step of them does not lower the next log-likelihood
   four EM iterations against the long-double LINEAR trajectory; plumbing; the command line"""
-import functools
 import os
 import subprocess
 
@@ -22,58 +21,12 @@ import fullestep_log_ref as LE
 import fulllogscore_ref as LR
 import fulltrain_ref as R
 from conftest import GOLDEN
-from test_fullestep_gpu import CASES as LIN_CASES, build as lin_build, check_estep, check_stats_bound, walk_any
-from test_fullestep_log_host import check_lattice
-from test_fulltrain_gpu import RUNS, SHIPPED, TRAIN, rand_model
+from fullcov_support import ctx  # noqa: F401  (the fixture)
+from fullcov_support import (RUNS, SHIPPED, TRAIN, U53, check_estep, check_log_lattice, check_stats_bound, code,
+                             extended, offsets, rand_fmodel, rel_dist, run_device, walk_any)
+from fulltrain_ref import LENS1
 
 pytestmark = pytest.mark.gpu
-extended = pytest.mark.skipif(not R.have_extended(), reason="long double is no wider than double here")
-U53 = 2.0 ** -53
-LENS1 = (70, 1, 33, 129)
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-def code(G, fn):
-    with pytest.raises(G.GhmmError) as e:
-        fn()
-    return e.value.code
-
-
-def run_device(G, ctx, hm, X, lens, delta=1, options=(), twice=False):
-    """estep_full_log under `options`; everything the tests look at, downloaded"""
-    N, M, D = hm.N, hm.M, hm.D
-    F, U = len(X), len(lens)
-    fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
-    st = ctx.stats_full(N, M, D)
-    try:
-        ctx.set_option(G.OPT_DELTA, delta)
-        for opt, val in options:
-            ctx.set_option(opt, val)
-        ctx.estep_full_log(fm, corpus, st)
-        v = st.download()
-        out = dict(v=v, stats=G.split_stats_full(v, N, M, D), logb=ctx.fetch(G.BUF_B, (F, N)),
-                   post=ctx.fetch(G.BUF_POST, (F, N * M)), gamma=ctx.fetch(G.BUF_GAMMA, (F, N)),
-                   la=ctx.fetch(G.BUF_ALPHA, (F, N)), lbe=ctx.fetch(G.BUF_BETA, (F, N)),
-                   ll=ctx.fetch(G.BUF_LOGLIK, (U,)))
-        # fetching lbe started no linear pass on these buffers
-        assert np.array_equal(out["gamma"], ctx.fetch(G.BUF_GAMMA, (F, N)))
-        assert np.array_equal(out["la"], ctx.fetch(G.BUF_ALPHA, (F, N)), equal_nan=True)
-        if twice:
-            ctx.estep_full_log(fm, corpus, st)
-            assert np.array_equal(v.view(np.uint64), st.download().view(np.uint64))
-        return out
-    finally:
-        ctx.set_option(G.OPT_DELTA, 1)
-        for opt, _ in options:
-            ctx.set_option(opt, 0)
-        st.close(); fm.close(); corpus.close()
-
 
 # ------------------------------------------------------------------- emission
 
@@ -83,10 +36,10 @@ def test_emission_every_db(G, ctx, D):
     """5 x 3 x D, 233 frames (three tiles of 64 and one of 41), frame 40 moved 60 units away"""
     rng = np.random.default_rng(500 + D)
     N, M = 5, 3
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     X = walk_any(rng, hm, LENS1)
     X[40] += 60.0
-    dev = run_device(G, ctx, hm, X, LENS1)
+    dev = run_device(G, ctx, hm, X, LENS1, log=True)
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, LENS1)
     try:
         ctx.viterbi_full(fm, corpus)
@@ -108,15 +61,6 @@ def test_emission_every_db(G, ctx, D):
 
 
 # ------------------------------------------------------------------- the lattice
-
-def lattice_cases(G):
-    out = {}
-    for name in LE.LATTICE_CASES:
-        out[name] = (name, 1)
-    for delta in LE.EMPTY_DELTAS:
-        out[f"empty_dense_delta{delta}"] = (None, delta)
-    return out
-
 
 LATTICE_IDS = LE.LATTICE_CASES + [f"empty_dense_delta{d}" for d in LE.EMPTY_DELTAS]
 
@@ -159,7 +103,7 @@ def check_against_own_logb(G, dev, hm, X, lens, delta, what):
     """the long-double recursion on the device's own log b and post; returns the reference"""
     N = hm.N
     ref = LE.estep(hm, X, lens, delta, np.longdouble, logb=dev["logb"], post=dev["post"])
-    off = LR.offsets(lens)
+    off = offsets(lens)
     worst = 0.0
     for u, ut in enumerate(ref["utt"]):
         s = slice(off[u], off[u + 1])
@@ -167,7 +111,7 @@ def check_against_own_logb(G, dev, hm, X, lens, delta, what):
         if ut["T"] == 0:
             assert dev["ll"][u] == 0.0
             continue
-        worst = max(worst, check_lattice(f"{what}[{u}]", N, got, ut, what="GPU", xi=False))
+        worst = max(worst, check_log_lattice(f"{what}[{u}]", N, got, ut, what="GPU", xi=False))
         # a frame's gammas sum to rho_u
         if np.isfinite(ut["logZ"]):
             rho = np.exp(ut["logP"] - ut["logZ"])
@@ -195,7 +139,7 @@ def check_against_own_logb(G, dev, hm, X, lens, delta, what):
 @pytest.mark.parametrize("name", LATTICE_IDS)
 def test_lattice_on_the_devices_own_log_b(G, ctx, name):
     hm, X, lens, delta = make(G, name)
-    dev = run_device(G, ctx, hm, X, lens, delta)
+    dev = run_device(G, ctx, hm, X, lens, log=True, delta=delta)
     ref = check_against_own_logb(G, dev, hm, X, lens, delta, name)
     ll = np.asarray(ref["loglik"], dtype=np.float64)
     if name == "c0_banded":
@@ -203,7 +147,7 @@ def test_lattice_on_the_devices_own_log_b(G, ctx, name):
     elif not name.startswith(("c0", "empty")) and not LR.CASES[name][3]:
         short = np.asarray(lens) < hm.N
         assert (ll[short] == -np.inf).all() and np.isfinite(ll[~short]).all()
-        off = LR.offsets(lens)
+        off = offsets(lens)
         for u in np.nonzero(short)[0]:
             assert np.all(dev["gamma"][off[u]:off[u + 1]] == 0.0)
     if name.startswith("empty"):
@@ -216,7 +160,7 @@ def test_lattice_on_the_devices_own_log_b(G, ctx, name):
 @pytest.mark.parametrize("name", ["l16_banded", "wide_64x2x48"])
 def test_statistics_within_the_derived_bound(G, ctx, name):
     hm, X, lens, delta = make(G, name)
-    dev = run_device(G, ctx, hm, X, lens, delta)
+    dev = run_device(G, ctx, hm, X, lens, log=True, delta=delta)
     worst = check_stats_bound(dev, X, hm, name)
     print(f"{name}: statistics worst error / bound {worst:.4f}")
 
@@ -227,10 +171,10 @@ def test_statistics_within_the_derived_bound(G, ctx, name):
 def test_far_frames_train_where_the_linear_call_cannot(G, ctx):
     rng = np.random.default_rng(61)
     N, M, D = 5, 2, 8
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     lens = np.array([60, 45, 81, 70], dtype=np.int32)
     X = walk_any(rng, hm, lens)
-    off = LR.offsets(lens)
+    off = offsets(lens)
     for u in range(len(lens)):
         X[off[u] + 7 + 3 * u] += 60.0        # a far frame in every utterance
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
@@ -252,27 +196,20 @@ def test_far_frames_train_where_the_linear_call_cannot(G, ctx):
         assert np.isfinite(ll1) and ll1 >= ll0
     finally:
         st.close(); fm.close(); corpus.close()
-    dev = run_device(G, ctx, hm, X, lens)
+    dev = run_device(G, ctx, hm, X, lens, log=True)
     assert np.array_equal(dev["v"].view(np.uint64), v.view(np.uint64))
     check_against_own_logb(G, dev, hm, X, lens, 1, "far frames")
     check_stats_bound(dev, X, hm, "far frames")
     # end to end from X: the log-likelihood at test_fulllogscore_gpu's bar, the posteriors at the emission test's
     ref = LE.estep(hm, X, lens, 1, np.longdouble)
     r64 = LE.estep(hm, X, lens, 1, np.float64)
-    d64 = LR.rel_dist(r64["loglik"], ref["loglik"])
-    d = LR.rel_dist(dev["ll"], ref["loglik"])
+    d64 = rel_dist(r64["loglik"], ref["loglik"])
+    d = rel_dist(dev["ll"], ref["loglik"])
     print(f"far frames: loglik GPU {d:.2e}, float64 restatement {d64:.2e}")
     assert d <= max(8.0 * d64, 1e-11)
 
 
 # ------------------------------------------------------------------- four EM iterations
-
-@functools.lru_cache(maxsize=None)
-def linear_trajectory(G, case):
-    N, M, D, U, T = R.EM_CASES[case]
-    X, lens = R.em_corpus(N, M, D, U, T)
-    return (X, lens) + R.em_trajectory(G, X, lens, N, M, 4, np.longdouble)
-
 
 @extended
 @pytest.mark.parametrize("case", range(len(R.EM_CASES)))
@@ -280,7 +217,7 @@ def test_four_em_iterations_track_the_linear_trajectory(G, ctx, case):
     """trace rel 1e-9 (the project's bar); model max(1e-8, 8 x EM_MODEL_F64[case]): 8 x for the device
     taking the float64 restatement's operations in another order"""
     N, M, D, U, T = R.EM_CASES[case]
-    X, lens, trace, ref_hm = linear_trajectory(G, case)
+    X, lens, trace, ref_hm = R.linear_trajectory(G, case)
     assert np.all(np.isfinite(trace))
     fm, corpus = ctx.full_model(G.HostFullModel.init_from(X, lens, N, M)), ctx.corpus(X, lens)
     st = ctx.stats_full(N, M, D)
@@ -308,7 +245,7 @@ def test_reproducible_and_partials(G, ctx):
     hm, X, lens, delta = make(G, "l32_banded")
     first = None
     for partials in (1, 3, 0):
-        dev = run_device(G, ctx, hm, X, lens, delta, options=((G.OPT_PARTIALS, partials),), twice=True)
+        dev = run_device(G, ctx, hm, X, lens, log=True, delta=delta, options=((G.OPT_PARTIALS, partials),), twice=True)
         if first is None:
             first = dev
         else:
@@ -319,7 +256,7 @@ def test_reproducible_and_partials(G, ctx):
 def test_empty_corpus(G, ctx):
     rng = np.random.default_rng(41)
     N, M, D = 4, 2, 6
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     fm = ctx.full_model(hm)
     st = ctx.stats_full(N, M, D)
     busy = ctx.corpus(walk_any(rng, hm, [30]), [30])
@@ -337,7 +274,7 @@ def test_empty_corpus(G, ctx):
 def test_refusals(G, ctx):
     rng = np.random.default_rng(43)
     N, M, D = 4, 2, 6
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     fm = ctx.full_model(hm)
     corpus = ctx.corpus(walk_any(rng, hm, [30]), [30])
     st, diag = ctx.stats_full(N, M, D), ctx.stats(N, M, D)
@@ -366,9 +303,9 @@ def test_linear_estep_afterwards_is_unchanged(G, ctx):
     """no stale log state leaks: estep_full after estep_full_log on the same context still meets its
     own reference"""
     name = "paths-8x3x16"
-    assert name in LIN_CASES
-    hm, X, lens, delta, ref = lin_build(G, name)
-    run_device(G, ctx, hm, X, lens, delta)
+    assert name in R.CASES
+    hm, X, lens, delta, ref = R.build(G, name)
+    run_device(G, ctx, hm, X, lens, log=True, delta=delta)
     N, M, D = hm.N, hm.M, hm.D
     F, U = len(X), len(lens)
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)

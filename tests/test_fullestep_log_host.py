@@ -19,8 +19,8 @@ import pytest
 import fullestep_log_ref as LE
 import fulllogscore_ref as LR
 import fulltrain_ref as R
+from fullcov_support import check_log_lattice, extended, offsets, rel_dist
 
-extended = pytest.mark.skipif(not R.have_extended(), reason="long double is no wider than double here")
 LD_EPS = float(np.finfo(np.longdouble).eps)
 
 
@@ -68,7 +68,7 @@ def test_long_double_restatement_is_the_linear_estep(G):
         assert max(d.values()) <= 1e-9
         assert dl <= 1e-12
         # the per-utterance log P and the arrays mean the same
-        assert LR.rel_dist(log["loglik"], lin["loglik"]) <= 1e-12
+        assert rel_dist(log["loglik"], lin["loglik"]) <= 1e-12
         assert float(np.abs(log["gamma"] - lin["gamma"]).max()) <= 1e-9
         assert float(np.abs(log["post"] - lin["post"]).max()) <= 1e-9
         hm = hm.mstep(R.pack(lin["stats"]), delta=1)
@@ -105,48 +105,16 @@ def test_gammas_sum_to_rho_at_every_frame(G):
                 assert np.all(ut["gamma"] == 0)
 
 
-def check_lattice(name, N, got, exact, what="float64", xi=True):
-    """one utterance, two lattice_fb dicts on the same log b: la, lbe, log P inside lattice_bound with
-    equal -inf / NaN patterns; gamma and the xi sums inside the expm1(E) bound.  Returns the worst
-    error / bound."""
-    T, V, La = exact["T"], exact["V"], exact["La"]
-    if T == 0:
-        return 0.0
-    worst = 0.0
-    lb = LR.lattice_bound(T, N, V, La)
-    for key in ("la", "lbe", "logP"):
-        g = np.atleast_1d(np.asarray(got[key], dtype=np.longdouble)).ravel()
-        r = np.atleast_1d(np.asarray(exact[key], dtype=np.longdouble)).ravel()
-        assert np.array_equal(np.isnan(g), np.isnan(r)), (name, key)
-        inf = np.isinf(r)
-        assert np.array_equal(np.isinf(g), inf) and np.array_equal(g[inf], r[inf]), (name, key)
-        fin = np.isfinite(r)
-        err = float(np.abs(g[fin] - r[fin]).max(initial=0))
-        assert err <= lb, (name, what, key, err, lb)
-        worst = max(worst, err / lb)
-    E = np.longdouble(LE.gamma_exponent_bound(T, N, V, La))
-    g, r = np.asarray(got["gamma"], dtype=np.longdouble), exact["gamma"]
-    tol = r * np.expm1(E) + 4 * LE.U53
-    assert np.all(np.abs(g - r) <= tol), (name, what, "gamma", float((np.abs(g - r) / tol).max()))
-    worst = max(worst, float((np.abs(g - r) / tol).max()))
-    if not xi:      # (the device keeps only the sums over the utterances)
-        return worst
-    g, r = np.asarray(got["xi"], dtype=np.longdouble), exact["xi"]
-    tol = r * np.expm1(E) + (T - 1) * 4 * LE.U53 + T * LE.U53 * r       # per term, and the sum's order
-    assert np.all(np.abs(g - r) <= tol), (name, what, "xi")
-    return worst
-
-
 @extended
 def test_float64_restatement_inside_the_bounds(G):
     """float64 against long double on the same float64 log b, every GPU-test case"""
     for name, hm, X, lens, delta in all_cases(G):
         logb = LR.log_emission(hm, X, np.float64)
-        off = LR.offsets(lens)
+        off = offsets(lens)
         worst = 0.0
         for u in range(len(lens)):
             lbu = logb[off[u]:off[u + 1]]
-            worst = max(worst, check_lattice(f"{name}[{u}]", hm.N, LE.lattice_fb(hm.A, lbu, delta, np.float64),
+            worst = max(worst, check_log_lattice(f"{name}[{u}]", hm.N, LE.lattice_fb(hm.A, lbu, delta, np.float64),
                                              LE.lattice_fb(hm.A, lbu, delta, np.longdouble)))
         print(f"{name}: worst error / bound {worst:.4f}")
 
@@ -161,7 +129,7 @@ def test_four_em_iterations(G, case):
     X, lens = R.em_corpus(N, M, D, U, T)
     trace, ref_hm = R.em_trajectory(G, X, lens, N, M, 4, np.longdouble)
     assert np.all(np.isfinite(trace))
-    got, hm = LE.em_trajectory_log(G, X, lens, N, M, 4, np.float64)
+    got, hm = R.em_trajectory(G, X, lens, N, M, 4, np.float64, estep=LE.estep)
     e_tr = max(abs(x - y) / abs(y) for x, y in zip(got, trace))
     e_model = R.model_err(hm, lambda k: getattr(ref_hm, k))
     print(f"EM_CASES[{case}]: trace {e_tr:.1e}, model {e_model:.1e} (EM_MODEL_F64 {LE.EM_MODEL_F64[case]:.1e})")

@@ -11,7 +11,6 @@ Against what is already pinned to the reference: score_full_batch and the record
 synthetic 13-word set, GHMM_BUF_LOGLIK after estep_full, at rel 1e-9 / abs 2e-6.  NaN and infinity
 patterns are equal wherever two scores are compared; no pair is left out."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -20,44 +19,25 @@ import pytest
 import fulllogscore_ref as LR
 from _load import PKG_DIR
 from conftest import GOLDEN
-from fullviterbi_ref import close_logb
-from test_fullcov_gpu import FULL, check_blocks, load_synth, same_kind
+from fullcov_support import ctx  # noqa: F401  (the fixture)
+from fullcov_support import (FULL, banded, check_blocks, close_logb, code, ergodic, frames, load_synth, offsets,
+                             rand_fmodel, rel_dist, same_kind_close, shipped, spoken_blocks)
 
 pytestmark = pytest.mark.gpu
 
 MISSES = {"vc_220_f_03_ap_010", "vc_220_f_047_ap_0225"}
 
 
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-def code(G, fn):
-    with pytest.raises(G.GhmmError) as e:
-        fn()
-    return e.value.code
-
-
-def shipped(G):
-    sh = FULL["shipped"]
-    hms = [G.HostFullModel.read(os.path.join(GOLDEN, "full_cov_models", f)) for f in sh["models"]]
-    Xs = [G.perfil_read(os.path.join(GOLDEN, "perfil", f)) for f in sh["mean_list"]]
-    return sh, hms, Xs
-
-
 def within_bound(got, A, logb, lens, fs):
     """every score of `got` against the long-double lattice on logb: equal NaN / infinity patterns,
     finite ones inside lattice_bound; returns the worst error / bound"""
-    off = LR.offsets(lens)
+    off = offsets(lens)
     N = A.shape[0]
     worst = 0.0
     for u, T in enumerate(lens):
         st = {}
         exact = LR.lattice(A, logb[off[u]:off[u + 1]], fs, np.longdouble, st)
-        LR.rel_dist([got[u]], [exact])
+        rel_dist([got[u]], [exact])
         if np.isfinite(exact) and T > 0:
             bound = LR.lattice_bound(T, N, st["V"], st["La"])
             err = float(abs(np.longdouble(got[u]) - exact))
@@ -105,9 +85,9 @@ def test_end_to_end(G, ctx, name):
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
     for fs in (0, 1):
         ref = LR.logscore(hm, X, lens, fs)
-        d64 = LR.rel_dist(LR.logscore(hm, X, lens, fs, np.float64), ref)
+        d64 = rel_dist(LR.logscore(hm, X, lens, fs, np.float64), ref)
         bar = max(8.0 * d64, 1e-11)
-        d = LR.rel_dist(ctx.logscore_full(fm, corpus, final_state=bool(fs)), ref)
+        d = rel_dist(ctx.logscore_full(fm, corpus, final_state=bool(fs)), ref)
         print(f"{name} final_state={fs}: GPU {d:.2e}, float64 restatement {d64:.2e}, bar {bar:.2e}")
         assert d <= bar
     fm.close()
@@ -124,13 +104,13 @@ def test_synthetic_set_against_the_pinned_scores(G, ctx):
     lin = ctx.score_full_batch(fms, corpus)
     s0 = ctx.logscore_full_batch(fms, corpus)
     assert s0.shape == (13, 13) and np.isfinite(s0).all()
-    same_kind(s0, lin)
+    same_kind_close(s0, lin)
     check_blocks(s0, sy["words"], sy["blocks"])
     s1 = ctx.logscore_full_batch(fms, corpus, final_state=True)
     for k, (h, fm) in enumerate(zip(hms, fms)):
         st = ctx.stats_full(h.N, h.M, h.D)
         ctx.estep_full(fm, corpus, st)
-        same_kind(s1[k], ctx.fetch(G.BUF_LOGLIK, (13,)))
+        same_kind_close(s1[k], ctx.fetch(G.BUF_LOGLIK, (13,)))
         st.close()
     for o in fms + [corpus]:
         o.close()
@@ -148,14 +128,14 @@ def test_shipped_set_is_finite_where_the_linear_score_is_not(G, ctx):
     assert (~np.isfinite(lin)).sum() == 156
     got = ctx.logscore_full_batch(fms, corpus)
     assert np.isfinite(got).all()
-    same_kind(got[np.isfinite(lin)], lin[np.isfinite(lin)])
+    same_kind_close(got[np.isfinite(lin)], lin[np.isfinite(lin)])
     first = [words[int(np.argmax(got[:, u]))] for u in range(13)]
     spoken = [b["spoken"] for b in sh["blocks"]]
     assert {s for s, f in zip(spoken, first) if s != f} == MISSES
     ref = np.array([[LR.logscore(h, x, [len(x)], 0)[0] for x in Xs] for h in hms])
     r64 = np.array([[LR.logscore(h, x, [len(x)], 0, np.float64)[0] for x in Xs] for h in hms])
-    d64 = LR.rel_dist(r64, ref)
-    d = LR.rel_dist(got, ref)
+    d64 = rel_dist(r64, ref)
+    d = rel_dist(got, ref)
     print(f"shipped: GPU {d:.2e}, float64 restatement {d64:.2e}")
     assert d <= max(8.0 * d64, 1e-11)
     for o in fms + [corpus]:
@@ -179,8 +159,8 @@ def test_one_far_frame(G, ctx):
         got = ctx.logscore_full(fm, corpus, final_state=bool(fs))
         assert np.isfinite(got).all()
         ref = LR.logscore(hm, X, lens, fs)
-        d64 = LR.rel_dist(LR.logscore(hm, X, lens, fs, np.float64), ref)
-        d = LR.rel_dist(got, ref)
+        d64 = rel_dist(LR.logscore(hm, X, lens, fs, np.float64), ref)
+        d = rel_dist(got, ref)
         print(f"far frame final_state={fs}: GPU {d:.2e}, float64 restatement {d64:.2e}")
         assert d <= max(8.0 * d64, 1e-11)
     assert ctx.logscore_full(fm, corpus)[0] == pytest.approx(lin[0], rel=1e-9, abs=2e-6)
@@ -197,7 +177,7 @@ def test_sum_over_paths_is_no_smaller(G, ctx, name):
     s1 = ctx.logscore_full(fm, corpus, final_state=True)
     _, vt = ctx.viterbi_full(fm, corpus)
     logb = ctx.fetch(G.BUF_B, (corpus.frames, hm.N))
-    off = LR.offsets(lens)
+    off = offsets(lens)
     for u, T in enumerate(lens):
         st = {}
         LR.lattice(hm.A, logb[off[u]:off[u + 1]], 0, np.longdouble, st)
@@ -215,10 +195,10 @@ def test_batch_equals_single_calls(G, ctx):
     rng = np.random.default_rng(31)
     base = rng.normal(0.0, 1.0, (1, 1, 9))
     sizes = (6, 3, 17, 6, 40, 1, 9, 64)
-    hms = [LR.rand_fmodel(G, rng, n, 2, 9, LR.ergodic(rng, n) if k % 3 == 2 else LR.banded(rng, n), spread=0.6,
-                          base=base) for k, n in enumerate(sizes)]
+    hms = [rand_fmodel(G, rng, n, 2, 9, ergodic(rng, n) if k % 3 == 2 else banded(rng, n), spread=0.6,
+                       base=base, asym=True) for k, n in enumerate(sizes)]
     lens = [33, 80, 1, 0, 57, 120, 15, 64, 200, 9, 0]
-    X = LR.frames(rng, hms[0], lens)
+    X = frames(rng, hms[0], lens)
     X[100] += 300.0
     corpus = ctx.corpus(X, lens)
     fms = [ctx.full_model(h) for h in hms]
@@ -242,7 +222,7 @@ def test_batch_equals_single_calls(G, ctx):
 
 def test_empty_corpus_touches_nothing(G, ctx):
     rng = np.random.default_rng(4)
-    hm = LR.rand_fmodel(G, rng, 5, 2, 6, LR.banded(rng, 5))
+    hm = rand_fmodel(G, rng, 5, 2, 6, banded(rng, 5), spread=1.0, asym=True)
     fm = ctx.full_model(hm)
     corpus = ctx.corpus(np.zeros((0, 6)), np.zeros(0, dtype=np.int32))
     lib = ctx.lib
@@ -263,11 +243,11 @@ def test_refusals_and_counters(G, ctx):
     """the codes of viterbi_full_batch: M or D differing in a batch, D against the corpus, a null
     destination, GHMM_OPT_ROBUST; the lattice launch counts under GHMM_K_FORWARD"""
     rng = np.random.default_rng(41)
-    hm = LR.rand_fmodel(G, rng, 5, 2, 6, LR.banded(rng, 5))
-    h3 = LR.rand_fmodel(G, rng, 5, 3, 6, LR.banded(rng, 5))
-    h7 = LR.rand_fmodel(G, rng, 5, 2, 7, LR.banded(rng, 5))
+    hm = rand_fmodel(G, rng, 5, 2, 6, banded(rng, 5), spread=1.0, asym=True)
+    h3 = rand_fmodel(G, rng, 5, 3, 6, banded(rng, 5), spread=1.0, asym=True)
+    h7 = rand_fmodel(G, rng, 5, 2, 7, banded(rng, 5), spread=1.0, asym=True)
     lens = [30, 20]
-    X = LR.frames(rng, hm, lens)
+    X = frames(rng, hm, lens)
     fm, f3, f7 = ctx.full_model(hm), ctx.full_model(h3), ctx.full_model(h7)
     corpus = ctx.corpus(X, lens)
     for call, ref in ((ctx.logscore_full_batch, ctx.viterbi_full_batch),):
@@ -336,16 +316,9 @@ def test_command_line_log_score(G, tmp_path):
     assert report[1] == "Algorithm used for recognition: Forward (log domain) "
     assert report[0] == sh["report"][0]
     assert "Correct words: 11" in report and "Errors: 2" in report
-    blocks, cur = [], None
-    for line in p.stdout.decode().replace("\r", "").split("\n"):
-        m = re.match(r"Spoken word: (\S+)", line)
-        if m:
-            cur = {"spoken": m.group(1), "ranking": []}
-            blocks.append(cur)
-            continue
-        m = re.match(r"(\S+) :  (\S+) $", line)
-        if m and cur is not None:
-            cur["ranking"].append((m.group(1), float(m.group(2))))
+    blocks = spoken_blocks(p.stdout.decode())
+    for blk in blocks:
+        blk["ranking"] = [(w, float(txt)) for w, txt in blk["ranking"]]
     assert len(blocks) == 13 and all(len(b["ranking"]) == 13 for b in blocks)
     assert all(np.isfinite(v) for b in blocks for _, v in b["ranking"])
     assert {b["spoken"] for b in blocks if b["ranking"][0][0] != b["spoken"]} == MISSES

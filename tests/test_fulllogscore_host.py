@@ -5,16 +5,14 @@ restatement's log P with final_state = 1, and is finite on the whole shipped set
 reference prints 156 NaN of 169; the float64 restatement's distance from the long-double one, and
 its place inside the lattice's rounding bound, at every shape the GPU tests run."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import fulllogscore_ref as LR
 import fulltrain_ref as R
-from conftest import GOLDEN
+from fullcov_support import check_blocks, load_synth, offsets, rel_dist, shipped
 from fullviterbi_ref import log_emission as log_emission64
-from test_fullcov_gpu import FULL, check_blocks, load_synth
 
 MISSES = {"vc_220_f_03_ap_010", "vc_220_f_047_ap_0225"}
 
@@ -25,13 +23,6 @@ def test_abi_exports_the_log_score(G):
         assert hasattr(lib, name), name
         assert name in G.SYMBOLS, name
     assert callable(G.Context.logscore_full) and callable(G.Context.logscore_full_batch)
-
-
-def shipped(G):
-    sh = FULL["shipped"]
-    hms = [G.HostFullModel.read(os.path.join(GOLDEN, "full_cov_models", f)) for f in sh["models"]]
-    Xs = [G.perfil_read(os.path.join(GOLDEN, "perfil", f)) for f in sh["mean_list"]]
-    return sh, hms, Xs
 
 
 def score_table(hms, Xs, final_state, ft):
@@ -91,7 +82,7 @@ def test_shipped_set(G):
     margin = float((top[-1] - top[-2]).min())
     assert margin > 2.5e4
     sld = score_table(hms, Xs, 0, np.longdouble)
-    spread = LR.rel_dist(s64, sld)
+    spread = rel_dist(s64, sld)
     print(f"shipped: {n_fin} finite prints met within {worst:.2e}; smallest margin {margin:.0f} nats; "
           f"float64 spread {spread:.2e}")
     assert spread < 1e-12
@@ -107,7 +98,7 @@ def test_final_state_is_the_estep_loglik(G):
     ref = R.estep(hm, X, lens, 1, np.longdouble)["loglik"]
     got = LR.logscore(hm, X, lens, 1, np.longdouble)
     assert np.isfinite(np.asarray(ref, dtype=np.float64)).all()
-    d = LR.rel_dist(got, ref)
+    d = rel_dist(got, ref)
     print(f"final_state = 1 against the E-step restatement: {d:.2e}")
     assert d < 1e-15
     # and final_state = 0 is no smaller
@@ -121,17 +112,17 @@ def test_float64_spread(G, name):
     same float64 log b, inside fulllogscore_ref.lattice_bound"""
     hm, X, lens = LR.make_case(G, name)
     N = hm.N
-    off = LR.offsets(lens)
+    off = offsets(lens)
     b64 = LR.log_emission(hm, X, np.float64)
     worst = 0.0
     for fs in (0, 1):
         s64, sld = LR.logscore(hm, X, lens, fs, np.float64), LR.logscore(hm, X, lens, fs)
-        worst = max(worst, LR.rel_dist(s64, sld))
+        worst = max(worst, rel_dist(s64, sld))
         for u, T in enumerate(lens):
             st = {}
             exact = LR.lattice(hm.A, b64[off[u]:off[u + 1]], fs, np.longdouble, st)
             got = LR.lattice(hm.A, b64[off[u]:off[u + 1]], fs, np.float64)
-            LR.rel_dist([got], [exact])
+            rel_dist([got], [exact])
             if np.isfinite(exact):
                 assert abs(np.longdouble(got) - exact) <= LR.lattice_bound(T, N, st["V"], st["La"]), (fs, u)
         if name.startswith("det0"):   # (with final_state = 1 the absorbing NaN state never shows)

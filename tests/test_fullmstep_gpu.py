@@ -22,28 +22,13 @@ import pytest
 import fullmstep_cases as K
 import fulltrain_ref as R
 from conftest import GOLDEN
-from test_fulltrain_gpu import RUNS, SYNTH, TRAIN, check_run, close
-# (corpus, lens, long-double trace, last model) of an EM case: computed once for both modules
-from test_fullestep_log_gpu import linear_trajectory as trajectory
+from fullcov_support import ctx, recorded  # noqa: F401  (the fixtures)
+from fullcov_support import RUNS, SYNTH, TRAIN, U53, check_run, close, code, extended
 
 pytestmark = pytest.mark.gpu
-extended = pytest.mark.skipif(not R.have_extended(), reason="long double is no wider than double here")
 
-U53 = 2.0 ** -53
 LOG_ULP = 3.0   # the device log / exp: no accuracy table of the device library is installed beside the
 #                 compiler, so OpenCL's bound for double log and exp (3 ulp) stands in for it
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def recorded():
-    return np.load(os.path.join(GOLDEN, "fulltrain_models.npz"))
 
 
 def dev_mstep(G, ctx, name):
@@ -214,7 +199,7 @@ def test_derived_constants(G, ctx, name):
 
 def em_on_device(G, ctx, case, estep):
     N, M, D, U, T = R.EM_CASES[case]
-    X, lens, trace, ref_hm = trajectory(G, case)
+    X, lens, trace, ref_hm = R.linear_trajectory(G, case)   # computed once for every module
     assert np.all(np.isfinite(trace))
     fm, corpus = ctx.full_model(G.HostFullModel.init_from(X, lens, N, M)), ctx.corpus(X, lens)
     st = ctx.stats_full(N, M, D)
@@ -297,18 +282,14 @@ def test_refusals(G, ctx):
     wide = K.rand_model(G, rng, 1, K.MCAP + 1, 2)
     wfm, wst = ctx.full_model(wide), ctx.stats_full(1, K.MCAP + 1, 2)
     try:
-        def code(fn):
-            with pytest.raises(G.GhmmError) as e:
-                fn()
-            return e.value.code
-        assert code(lambda: ctx.mstep_full_dev(fm, diag)) == G.ERR_ARG
-        assert code(lambda: ctx.mstep_full_dev(fm, other)) == G.ERR_ARG
+        assert code(G, lambda: ctx.mstep_full_dev(fm, diag)) == G.ERR_ARG
+        assert code(G, lambda: ctx.mstep_full_dev(fm, other)) == G.ERR_ARG
         assert ctx.lib.ghmm_mstep_full_dev(ctx.h, None, other.h) == G.ERR_ARG
         for a, b in zip(fm.get().arrays(), hm.arrays()):
             assert np.array_equal(a, b)
         # M above the cap: refused, nothing launched, the model as it was; the host route takes it
         wst.upload(K.pack(K.pd_sums(rng, 1, K.MCAP + 1, 2)))
-        assert code(lambda: ctx.mstep_full_dev(wfm, wst)) == G.ERR_UNSUPPORTED
+        assert code(G, lambda: ctx.mstep_full_dev(wfm, wst)) == G.ERR_UNSUPPORTED
         for a, b in zip(wfm.get().arrays(), wide.arrays()):
             assert np.array_equal(a, b)
         ctx.mstep_full(wfm, wst)

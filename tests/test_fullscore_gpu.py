@@ -3,7 +3,7 @@ k_emission_full<DB, FC_LIN> and the score-only scan forward_run<L, BANDED, false
 the shape range the library is built for, against the long-double restatement tests/fullscore_ref.py —
 GPU box only.  The restatement and the cases are pinned on the CPU by test_fullscore_host.py.
 
-(1) the emission at every DB, both sides of each boundary, under test_fullcov_gpu.close_b (equal NaN /
+(1) the emission at every DB, both sides of each boundary, under fullcov_support.close_b (equal NaN /
     inf / zero pattern, rtol 1e-11);
 (2) the score at lane classes 16 / 32 / 64 with banded and dense A, every tail residue of the scan's
     unrolled loop, T = 0, T = 1, T < N, utterances stored out of length order: end to end at the 1e-11
@@ -19,20 +19,12 @@ import numpy as np
 import pytest
 
 import fullscore_ref as FR
-from fulltrain_ref import have_extended
-from test_fullcov_gpu import close_b
+from fullcov_support import ctx  # noqa: F401  (the fixture)
+from fullcov_support import close_b, extended, rel_dist
 
 pytestmark = pytest.mark.gpu
-extended = pytest.mark.skipif(not have_extended(), reason="long double is no wider than double here")
 
 SWEEP_IDS = [FR.sweep_id(c) for c in FR.SWEEP]
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
 
 
 def bits(a):
@@ -76,9 +68,9 @@ def test_score_sweep_end_to_end(G, ctx, case):
         fm.close(); corpus.close()
     empty = lens == 0
     assert empty.sum() == 1 and (got[empty] == 0.0).all() and not np.signbit(got[empty]).any()
-    d = FR.rel_dist(got, ref)
+    d = rel_dist(got, ref)
     short = (lens < hm.N) & ~empty
-    d_short = FR.rel_dist(got[short], ref[short])
+    d_short = rel_dist(got[short], ref[short])
     print(f"{FR.sweep_id(case)}: worst relative error {d:.2e}, over the {short.sum()} utterances of T < N "
           f"{d_short:.2e} (bar 1e-11: ratio {d / 1e-11:.3f})")
     assert d <= 1e-11
@@ -98,9 +90,9 @@ def test_score_sweep_lattice_alone(G, ctx, case):
     finally:
         fm.close(); corpus.close()
     exact = FR.lattice_scores(hm.A, b, lens)
-    d64 = FR.rel_dist(FR.lattice_scores(hm.A, b, lens, np.float64), exact)
+    d64 = rel_dist(FR.lattice_scores(hm.A, b, lens, np.float64), exact)
     bar = 1e-12 if d64 <= 1e-13 else 8.0 * d64
-    d = FR.rel_dist(got, exact)
+    d = rel_dist(got, exact)
     print(f"{FR.sweep_id(case)}: lattice alone {d:.2e}, float64 restatement {d64:.2e}, bar {bar:.1e}: "
           f"ratio {d / bar:.4f}")
     assert d <= bar
@@ -147,9 +139,9 @@ def test_long_utterances_through_the_score_only_scan(G, ctx, name):
         for o in fms + [corpus]:
             o.close()
     for u, T in enumerate(lens):
-        print(f"{name} T={T}: score_full {FR.rel_dist(one[u:u + 1], ref[u:u + 1]):.2e}, "
-              f"score_full_batch {FR.rel_dist(batch[1, u:u + 1], ref[u:u + 1]):.2e} (bar 1e-11)")
-    d1, db = FR.rel_dist(one, ref), FR.rel_dist(batch[1], ref)
+        print(f"{name} T={T}: score_full {rel_dist(one[u:u + 1], ref[u:u + 1]):.2e}, "
+              f"score_full_batch {rel_dist(batch[1, u:u + 1], ref[u:u + 1]):.2e} (bar 1e-11)")
+    d1, db = rel_dist(one, ref), rel_dist(batch[1], ref)
     print(f"{name}: worst error / bar {max(d1, db) / 1e-11:.4f}")
     assert d1 <= 1e-11 and db <= 1e-11
     assert np.array_equal(bits(batch[1]), bits(one)) and np.array_equal(batch[0], first, equal_nan=True)

@@ -1,37 +1,36 @@
 """CPU-side tests (no GPU) of the linear full-covariance score's restatement (fullscore_ref.py) and of
-the cases test_fullscore_gpu.py runs: the float64 form is test_fullcov_gpu's pinned np_emission /
-np_logp bit for bit; its distance from the long-double form at every shape; no sweep utterance of at
-least N frames has a NaN reference; and every long case reaches what it is there for, shown by running
-the score-only scan's accumulator (log_product) on the CPU over the case's own c_t in its right form
+the cases test_fullscore_gpu.py runs: the float64 form is the pinned np_emission / np_logp (the
+float64 family, written separately in the same module) bit for bit; its distance from the long-double
+form at every shape; no sweep utterance of at least N frames has a NaN reference; and every long case
+reaches what it is there for, shown by running the score-only scan's accumulator (log_product) on the CPU over the case's own c_t in its right form
 and its two broken ones.  These are conditions on the inputs, not on the device: a case that fails
 them is replaced, not excused."""
 import numpy as np
 import pytest
 
 import fullscore_ref as FR
-from fulltrain_ref import have_extended
-from test_fullcov_gpu import np_emission, np_logp
+from fullcov_support import extended, offsets, rel_dist
+from fullscore_ref import np_emission, np_logp
 
-extended = pytest.mark.skipif(not have_extended(), reason="long double is no wider than double here")
 
 SWEEP_IDS = [FR.sweep_id(c) for c in FR.SWEEP]
 
 
 def test_float64_form_is_the_pinned_restatement(G):
-    """emission() and logp() in float64 = test_fullcov_gpu.np_emission and np_logp, bit for bit, the far
+    """emission() and logp() in float64 = np_emission and np_logp, bit for bit, the far
     frame's zeros and an utterance of one frame included"""
     hm, X, lens = FR.emission_case(G, 9)
     b = FR.emission(hm, X, np.float64)
     ref = np_emission(hm, X)
     assert b.dtype == np.float64 and np.array_equal(b.view(np.uint64), ref.view(np.uint64))
     assert (b[FR.FAR_FRAME] == 0).all() and (b > 0).any()
-    off = FR.offsets(lens)
+    off = offsets(lens)
     for u in range(len(lens)):
         got, want = FR.logp(hm.A, b[off[u]:off[u + 1]], np.float64), np_logp(hm.A, ref[off[u]:off[u + 1]])
         assert np.array_equal(np.float64(got).view(np.uint64), np.float64(want).view(np.uint64)), u
     hm, X, lens = FR.sweep_case(G, FR.SWEEP[1])        # a dense A, T = 0 among the utterances
     b = np_emission(hm, X)
-    off = FR.offsets(lens)
+    off = offsets(lens)
     got = FR.score(hm, X, lens, np.float64)
     want = np.array([np_logp(hm.A, b[off[u]:off[u + 1]]) for u in range(len(lens))])
     assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
@@ -39,7 +38,7 @@ def test_float64_form_is_the_pinned_restatement(G):
 
 
 def spread(hm, X, lens, ref):
-    d = FR.rel_dist(FR.score(hm, X, lens, np.float64), ref)
+    d = rel_dist(FR.score(hm, X, lens, np.float64), ref)
     assert d <= 1e-13
     return d
 
@@ -81,7 +80,7 @@ def test_long_cases_bite(G, name):
     marked = FR.LONG[name][5]
     ref = FR.reference(G, "long", name)
     b = FR.emission(hm, X, np.float64)
-    off = FR.offsets(lens)
+    off = offsets(lens)
     for u, T in enumerate(lens):
         lp, cs = FR.forward(hm.A, b[off[u]:off[u + 1]], np.float64)
         assert cs.dtype == np.float64 and len(cs) == T

@@ -3,180 +3,25 @@ MI355X — GPU box only.
 
 Checked against recorded runs of the real reference (tests/golden/fulltrain_runs.json,
 fulltrain_models.npz, fulltrain_synth.npz: make_golden_fulltrain.py), against the shipped models,
-and against a numpy restatement of TFF's E-step below.  Tolerances: reports' mean probability
-within rel 1e-9 / abs 2e-6 and the same iteration count; models within rel 1e-8 of the recorded
+and against the float64 numpy restatement of TFF's E-step (fulltrain_ref.np_estep).  Tolerances:
+reports' mean probability within rel 1e-9 / abs 2e-6 and the same iteration count; models within rel 1e-8 of the recorded
 64-bit run (inv_cov per Gaussian as max|d| / max|inv_cov|) and within 1e-6 of the shipped 32-bit
 files; E-step arrays and statistics rtol 1e-11, with an absolute floor of 1e-11 times the largest entry
 of their block (sums of both signs cancel; gamma and the sums may hold a value far below that
 where the restatement has an exact 0)."""
-import json
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from _load import PKG_DIR
+from fullcov_support import ctx, recorded  # noqa: F401  (the fixtures)
+from fullcov_support import (FULL, RECOGNISE, RUNS, SHIPPED, SYNTH, TRAIN, check_run, close, code, rand_fmodel, run_cli,
+                             spoken_blocks, walk_any)
+from fulltrain_ref import np_estep
 
 pytestmark = pytest.mark.gpu
-
-RUNS = json.load(open(os.path.join(GOLDEN, "fulltrain_runs.json")))
-RECOG = json.load(open(os.path.join(GOLDEN, "fullcov_recog.json")))
-TRAIN = os.path.join(PKG_DIR, "bin", "hmm-continuous-train-full-fs")
-RECOGNISE = os.path.join(PKG_DIR, "bin", "recognition-continuous-test-full-fs")
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def recorded():
-    return np.load(os.path.join(GOLDEN, "fulltrain_models.npz"))
-
-
-# ------------------------------------------------------------- restatement of TFF
-
-def np_estep(hm, X, lens):
-    """calc_symbol_probab / calc_gaus (TFF:1775-1887), calc_alpha / calc_beta /
-    calc_transition_probab / calc_den_mix_coef / calc_probability (the diagonal trainer's, final
-    state included) and calc_mix_param (TFF:1714-1753), per utterance, summed"""
-    N, M, D = hm.N, hm.M, hm.D
-    G_, DT = N * M, D * (D + 1) // 2
-    iu = np.triu_indices(D)
-    with np.errstate(all="ignore"):
-        dif = X[:, None, None, :] - hm.mean[None]
-        aux = np.einsum("fnmi,fnmi->fnm", dif, np.einsum("fnmj,nmji->fnmi", dif, hm.inv_cov))
-        den = pow(2.0 * np.pi, D / 2.0) * np.power(np.abs(hm.det), 0.5)
-        g = np.exp(aux * -0.5) / den[None]
-        g = np.where((g == np.inf) & (den[None] != 0.0), 1e20, g)
-        gm = g * hm.c[None]
-        b = gm.sum(-1)
-        post = np.where(b[..., None] != 0.0, gm / b[..., None], 0.0)
-    st = {"num_a": np.zeros((N, N)), "den_a": np.zeros(N), "den_c": np.zeros(N), "loglik": 0.0}
-    gamma = np.zeros((len(X), N))
-    A = hm.A
-    o = 0
-    for T in lens:
-        bb = b[o:o + T]
-        al = np.zeros((T, N)); c = np.zeros(T)
-        for t in range(T):
-            a = (np.eye(N)[0] if t == 0 else al[t - 1] @ A) * bb[t]
-            c[t] = 1.0 / a.sum()
-            al[t] = a * c[t]
-        be = np.zeros((T, N))
-        be[T - 1, N - 1] = c[T - 1]
-        for t in range(T - 2, -1, -1):
-            be[t] = (A @ (be[t + 1] * bb[t + 1])) * c[t]
-        ga = al * be / c[:, None]
-        gamma[o:o + T] = ga
-        for i in range(N):
-            for j in (i, i + 1):
-                if j < N:
-                    st["num_a"][i, j] += np.sum(al[:-1, i] * A[i, j] * bb[1:, j] * be[1:, j])
-        st["den_a"] += ga[:-1].sum(0)
-        st["den_c"] += ga.sum(0)
-        st["loglik"] += -np.log(c).sum() + np.log(al[T - 1, N - 1])
-        o += T
-    w = gamma[:, :, None] * post
-    st["num_c"] = w.sum(0)
-    st["num_mu"] = np.einsum("fnm,fd->nmd", w, X)
-    st["num_cov"] = np.einsum("fnm,fnmk,fnml->nmkl", w, dif, dif)[..., iu[0], iu[1]].reshape(N, M, DT)
-    st["n_utt"] = float(len(lens))
-    return b, post.reshape(len(X), G_), gamma, st
-
-
-def rand_model(G, rng, N, M, D):
-    A = np.zeros((N, N))
-    for i in range(N - 1):
-        A[i, i] = rng.uniform(0.5, 0.9)
-        A[i, i + 1] = 1.0 - A[i, i]
-    A[N - 1, N - 1] = 1.0
-    c = rng.dirichlet(np.full(M, 3.0), N)
-    mean = rng.normal(0.0, 1.0, (N, M, D))
-    ic = np.empty((N, M, D, D))
-    for i in range(N):
-        for k in range(M):
-            Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-            ic[i, k] = (Q * rng.uniform(0.5, 2.0, D)) @ Q.T
-    return G.HostFullModel(A, c, mean, ic, 1.0 / np.linalg.det(ic), word="w")
-
-
-def walk(rng, hm, lens):
-    """left-to-right walks through the states, one mixture per frame, unit noise"""
-    out = []
-    for T in lens:
-        cuts = np.sort(rng.choice(np.arange(1, T), hm.N - 1, replace=False))
-        st = np.searchsorted(cuts, np.arange(T), side="right")
-        k = rng.integers(0, hm.M, T)
-        out.append(hm.mean[st, k] + rng.normal(0.0, 0.3, (T, hm.D)))
-    return np.concatenate(out)
-
-
-def close(got, ref, rtol=1e-11, zeros=True):
-    """zeros: the exact zeros must agree (densities, posteriors); gamma and the sums built on it
-    may hold a value far below the bound where the other side has 0"""
-    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
-    if zeros:
-        assert np.array_equal(got == 0.0, ref == 0.0), "zeros differ"
-    scale = np.abs(ref).max() if ref.size else 0.0
-    np.testing.assert_allclose(got, ref, rtol=rtol, atol=rtol * scale)
-
-
-# --------------------------------------------------------------- command line
-
-def run_cli(tmp, word, N, M, perfil_paths, extra=(), env=None, check=True):
-    lst = os.path.join(tmp, "list.txt")
-    open(lst, "w").write("\n".join(perfil_paths) + "\n")
-    out = os.path.join(tmp, "out.hmm")
-    p = subprocess.run([TRAIN, word, str(N), "1", str(M), lst, out, *extra], cwd=tmp, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, timeout=600, env=env)
-    text = p.stdout.decode(errors="replace")
-    if check:
-        assert p.returncode == 0, text[-2000:]
-    return p.returncode, text, out, os.path.join(tmp, "out.txt")
-
-
-def report_value(lines, key):
-    return next(l for l in lines if l.startswith(key)).split(":", 1)[1].strip()
-
-
-def check_run(G, recorded, name, run, out, txt, shipped_hmm=None):
-    rep = [l for l in open(txt).read().split("\n") if l]
-    ref = run["report"]
-    assert rep[0] == ref[0] == ("Continuous HMM created using Forward Backward algorithm. It is considered "
-                                "full covariance matrix. It is considered a final state.")
-    assert report_value(rep, "number of iterations") == report_value(ref, "number of iterations"), name
-    assert report_value(rep, "number of exemplars") == report_value(ref, "number of exemplars"), name
-    assert float(report_value(rep, "mean probability")) == pytest.approx(
-        float(report_value(ref, "mean probability")), rel=1e-9, abs=2e-6), name
-    with open(out, "rb") as f:
-        assert int.from_bytes(f.read(8), "little") == len(name)  # 8-byte length prefix
-    hm = G.HostFullModel.read(out)
-    assert hm.word == name
-
-    def compare(ref_of, tol):
-        for key in ("A", "c", "mean", "det"):
-            np.testing.assert_allclose(getattr(hm, key), ref_of(key), rtol=tol, atol=0, err_msg=f"{name}.{key}")
-        ic, ric = hm.inv_cov, ref_of("inv_cov")
-        for i in range(hm.N):
-            for k in range(hm.M):
-                err = np.abs(ic[i, k] - ric[i, k]).max() / np.abs(ric[i, k]).max()
-                assert err <= tol, (name, i, k, err)
-    compare(lambda k: recorded[f"{name}.{k}"], 1e-8)
-    if shipped_hmm is not None:
-        sh = G.HostFullModel.read(shipped_hmm)
-        compare(lambda k: getattr(sh, k), 1e-6)
-    return hm
-
-
-SHIPPED = sorted(k for k, v in RUNS.items() if v["kind"] == "shipped")
-SYNTH = sorted(k for k, v in RUNS.items() if v["kind"] == "synthetic")
 
 
 def test_shipped_runs_and_recognition(G, recorded, tmp_path):
@@ -195,7 +40,7 @@ def test_shipped_runs_and_recognition(G, recorded, tmp_path):
                   shipped_hmm=shipped if os.path.exists(shipped) else None)
         models.append((name, out))
     # the vocabulary in the recogniser's own order (test/test/models/models.txt)
-    sh = RECOG["shipped"]
+    sh = FULL["shipped"]
     by_name = {f"mean_{n}.hmm": p for n, p in models}
     by_name.update({os.path.basename(p): p for _, p in models})
     tmp = str(tmp_path)
@@ -208,16 +53,7 @@ def test_shipped_runs_and_recognition(G, recorded, tmp_path):
     p = subprocess.run([RECOGNISE, "1", ml, "1", fl, wl, os.path.join(tmp, "result.txt")],
                        stdout=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stdout.decode()[-2000:]
-    blocks, cur = [], None
-    for line in p.stdout.decode().replace("\r", "").split("\n"):
-        m = re.match(r"Spoken word: (\S+)", line)
-        if m:
-            cur = {"spoken": m.group(1), "ranking": []}
-            blocks.append(cur)
-            continue
-        m = re.match(r"(\S+) :  (\S+) $", line)
-        if m and cur is not None:
-            cur["ranking"].append([m.group(1), m.group(2)])
+    blocks = spoken_blocks(p.stdout.decode())
     assert len(blocks) == len(sh["blocks"]) == 13
     for g, r in zip(blocks, sh["blocks"]):
         assert g["spoken"] == r["spoken"]
@@ -247,9 +83,9 @@ def test_synthetic_runs(G, recorded, tmp_path, name):
 def test_estep_matches_restatement(G, ctx, D):
     rng = np.random.default_rng(D)
     N, M = 5, 3
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     lens = [57, 80, 41]
-    X = walk(rng, hm, lens)
+    X = walk_any(rng, hm, lens)
     # one Gaussian with a non-positive-definite matrix: aux < -1420 on frames far from it, its
     # density overflows to +inf and is clamped to 1e20 (state 4's frames, so b stays finite there)
     hm.inv_cov[4, 2] = -np.eye(D)
@@ -282,10 +118,10 @@ def test_estep_clamp_and_zero_b(G, ctx):
     """+inf densities become 1e20; a state whose every density underflows has b = 0 and post = 0"""
     rng = np.random.default_rng(5)
     N, M, D = 3, 2, 4
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     hm.inv_cov[1, 0] = -np.eye(D)          # density exp(+|x - mu|^2 / 2): +inf far away
     hm.mean[2] += 1000.0                   # state 2: every density underflows to exactly 0
-    X = walk(rng, hm, [30])
+    X = walk_any(rng, hm, [30])
     X[:, :] = hm.mean[0, 0] + rng.normal(0.0, 0.3, X.shape)
     X[5] = hm.mean[1, 0] + 50.0
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, [30])
@@ -308,9 +144,9 @@ def test_estep_clamp_and_zero_b(G, ctx):
 
 def test_estep_bitwise_reproducible(G, ctx):
     rng = np.random.default_rng(9)
-    hm = rand_model(G, rng, 8, 3, 16)
+    hm = rand_fmodel(G, rng, 8, 3, 16, spread=1.0, asym=False)
     lens = list(rng.integers(100, 400, 12))
-    X = walk(rng, hm, lens)
+    X = walk_any(rng, hm, lens)
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
     st = ctx.stats_full(8, 3, 16)
     try:
@@ -326,9 +162,9 @@ def test_estep_bitwise_reproducible(G, ctx):
 def test_mstep_equals_host_mstep(G, ctx):
     rng = np.random.default_rng(13)
     N, M, D = 6, 2, 9
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     lens = [120, 90, 150]
-    X = walk(rng, hm, lens)
+    X = walk_any(rng, hm, lens)
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
     st = ctx.stats_full(N, M, D)
     try:
@@ -345,34 +181,30 @@ def test_mstep_equals_host_mstep(G, ctx):
 
 def test_refusals(G, ctx, tmp_path):
     rng = np.random.default_rng(21)
-    hm = rand_model(G, rng, 3, 2, 4)
-    X = walk(rng, hm, [40])
+    hm = rand_fmodel(G, rng, 3, 2, 4, spread=1.0, asym=False)
+    X = walk_any(rng, hm, [40])
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, [40])
     st = ctx.stats_full(3, 2, 4)
     other = ctx.stats_full(3, 3, 4)
     diag = ctx.stats(3, 2, 4)
     try:
-        def code(fn):
-            with pytest.raises(G.GhmmError) as e:
-                fn()
-            return e.value.code
         # D > 48
-        assert code(lambda: ctx.full_model(G.HostFullModel(np.eye(2), np.ones((2, 1)), np.zeros((2, 1, 49)),
+        assert code(G, lambda: ctx.full_model(G.HostFullModel(np.eye(2), np.ones((2, 1)), np.zeros((2, 1, 49)),
                                                            np.tile(np.eye(49), (2, 1, 1, 1)), np.ones((2, 1))))) \
             == G.ERR_UNSUPPORTED
         # GHMM_OPT_ROBUST
         ctx.set_option(G.OPT_ROBUST, 1)
         try:
-            assert code(lambda: ctx.estep_full(fm, corpus, st)) == G.ERR_UNSUPPORTED
+            assert code(G, lambda: ctx.estep_full(fm, corpus, st)) == G.ERR_UNSUPPORTED
         finally:
             ctx.set_option(G.OPT_ROBUST, 0)
         # shape mismatch, and a diagonal statistics vector
-        assert code(lambda: ctx.estep_full(fm, corpus, other)) == G.ERR_ARG
-        assert code(lambda: ctx.estep_full(fm, corpus, diag)) == G.ERR_ARG
-        assert code(lambda: ctx.mstep_full(fm, other)) == G.ERR_ARG
+        assert code(G, lambda: ctx.estep_full(fm, corpus, other)) == G.ERR_ARG
+        assert code(G, lambda: ctx.estep_full(fm, corpus, diag)) == G.ERR_ARG
+        assert code(G, lambda: ctx.mstep_full(fm, other)) == G.ERR_ARG
         # a full vector is refused by the diagonal path
         dm = ctx.model(G.synth_start_model(*G.synth_truth(3, 2, 4)))
-        assert code(lambda: ctx.estep(dm, corpus, st)) == G.ERR_ARG
+        assert code(G, lambda: ctx.estep(dm, corpus, st)) == G.ERR_ARG
         dm.close()
     finally:
         for o in (st, other, diag, fm, corpus):

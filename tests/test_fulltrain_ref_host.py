@@ -3,16 +3,16 @@ trainer's E-step that test_fullestep_gpu.py holds the HIP code against (CPU only
 
 (a) the real reference's recorded runs (tests/golden/fulltrain_runs.json, fulltrain_models.npz):
     the restated E-step + the library's host M-step, iterated with the trainer's stopping rule,
-    under the bars of test_fulltrain_gpu.check_run (iteration count, mean probability within rel
+    under the bars of fullcov_support.check_run (iteration count, mean probability within rel
     1e-9 / abs 2e-6, model within 1e-8).
 (b) the pinned diagonal oracle (oracle/ghmm_oracle.c) on diagonal matrices: dense A, transition
     bands 0..3, utterances shorter than the model, of one frame and of none, 33 and 64 states,
-    which the recorded runs do not cover (assert_close of test_gpu_parity: rtol 1e-8, floor 1e-13,
+    which the recorded runs do not cover (fullcov_support.assert_close: rtol 1e-8, floor 1e-13,
     equal NaN / infinity pattern).
-(c) the float64 result equals test_fulltrain_gpu.np_estep on that file's own four cases.
+(c) the float64 result equals np_estep, the vectorised float64 restatement, on test_fulltrain_gpu's
+    four cases.
 (d) the two multi-iteration cases of test_fullestep_gpu.py are well conditioned: their float64 and
     long-double trajectories differ by at most a hundredth of the bars the GPU test asserts."""
-import json
 import os
 
 import numpy as np
@@ -21,12 +21,10 @@ import pytest
 import fulltrain_ref as R
 import oracle_lib as O
 from conftest import GOLDEN
-from test_fulltrain_gpu import close, np_estep, rand_model, report_value, walk
-from test_gpu_parity import assert_close
+from fullcov_support import RUNS, assert_close, close, extended, rand_fmodel, report_value, walk_any
+from fulltrain_ref import np_estep
 
-RUNS = json.load(open(os.path.join(GOLDEN, "fulltrain_runs.json")))
 FTS = [np.float64, np.longdouble]
-extended = pytest.mark.skipif(not R.have_extended(), reason="long double is no wider than double here")
 
 
 def ft_param(ft):
@@ -117,9 +115,9 @@ def test_float64_equals_the_existing_restatement(G, D):
     """test_fulltrain_gpu.test_estep_matches_restatement's case, clamped Gaussian included"""
     rng = np.random.default_rng(D)
     N, M = 5, 3
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     lens = [57, 80, 41]
-    X = walk(rng, hm, lens)
+    X = walk_any(rng, hm, lens)
     hm.inv_cov[4, 2] = -np.eye(D)
     hm.mean[4, 2] = hm.mean[4, 0] + 60.0
     rb, rpost, rgamma, rst = np_estep(hm, X, lens)
@@ -141,9 +139,9 @@ def test_stats_from_equals_the_estep_sums(G):
     absolute sum bounds its sum"""
     rng = np.random.default_rng(3)
     N, M, D = 4, 2, 5
-    hm = rand_model(G, rng, N, M, D)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=False)
     lens = [30, 0, 25]
-    X = walk(rng, hm, [30, 25])
+    X = walk_any(rng, hm, [30, 25])
     r = R.estep(hm, X, lens, 1, np.float64)
     s, a = R.stats_from(r["gamma"], r["post"], X, hm.mean, np.float64)
     for key in ("num_c", "num_mu", "num_cov"):

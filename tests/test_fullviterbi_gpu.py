@@ -13,71 +13,11 @@ import pytest
 
 import oracle_lib as O
 from conftest import GOLDEN
-from fullviterbi_ref import close_logb, lattice_margins, log_emission
+from fullcov_support import ctx  # noqa: F401  (the fixture)
+from fullcov_support import check_viterbi_lattice, close_logb, code, ergodic, frames, offsets, rand_fmodel
+from fullviterbi_ref import lattice_margins, log_emission
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx(G):
-    c = G.Context(0)
-    yield c
-    c.close()
-
-
-def rand_fmodel(G, rng, N, M, D, spread=0.3, base=None, word="w", A=None):
-    if A is None:  # left-to-right, one step
-        A = np.zeros((N, N))
-        for i in range(N - 1):
-            A[i, i] = rng.uniform(0.5, 0.9)
-            A[i, i + 1] = 1.0 - A[i, i]
-        A[N - 1, N - 1] = 1.0
-    c = rng.dirichlet(np.full(M, 3.0), N)
-    mean = (base if base is not None else 0.0) + rng.normal(0.0, spread, (N, M, D))
-    ic = np.empty((N, M, D, D))
-    for i in range(N):
-        for k in range(M):
-            Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-            ic[i, k] = (Q * rng.uniform(0.5, 2.0, D)) @ Q.T
-    ic[0, 0] += np.triu(rng.normal(0.0, 0.3, (D, D)), 1)  # non-symmetric: inv_cov[j][i] order
-    det = 1.0 / np.linalg.det(ic)
-    return G.HostFullModel(A, c, mean, ic, det, word=word)
-
-
-def ergodic(rng, N, zeros=0.4):
-    A = rng.uniform(0.05, 1.0, (N, N)) * (rng.uniform(size=(N, N)) >= zeros)
-    A[np.arange(N), (np.arange(N) + 1) % N] += 0.1  # every row reaches somewhere
-    return A / A.sum(1, keepdims=True)
-
-
-def frames(rng, hm, lens, scale=1.0):
-    F = int(np.sum(lens))
-    i = rng.integers(0, hm.N, F)
-    k = rng.integers(0, hm.M, F)
-    return hm.mean[i, k] + rng.normal(0.0, scale, (F, hm.D))
-
-
-def offsets(lens):
-    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-
-
-def check_lattice(A, logb, lens, path, score):
-    """path and score bit for bit the oracle lattice's on the same log b"""
-    off = offsets(lens)
-    for u, T in enumerate(lens):
-        if T == 0:
-            assert score[u] == 0.0 and not np.signbit(score[u]), u
-            continue
-        p, s = O.viterbi_lattice(A, logb[off[u]:off[u + 1]])
-        assert np.array_equal(path[off[u]:off[u + 1]], p), u
-        assert np.array_equal(np.float64(score[u]), np.float64(s), equal_nan=True), (u, score[u], s)
-
-
-def code(G, fn):
-    with pytest.raises(G.GhmmError) as e:
-        fn()
-    return e.value.code
-
 
 # ------------------------------------------------------------------- the tests
 
@@ -87,7 +27,7 @@ def test_log_emission_and_lattice(G, ctx, N, M, D):
     """log b (fetch(BUF_B) after viterbi_full) = the restatement within 1e-11 (1 + |ref|), the frame
     far from everything included; path and score = the oracle lattice on that log b, bit for bit"""
     rng = np.random.default_rng(N * 1000 + M * 100 + D)
-    hm = rand_fmodel(G, rng, N, M, D, spread=1.0)
+    hm = rand_fmodel(G, rng, N, M, D, spread=1.0, asym=True)
     lens = [70, 1, 33, 129]
     X = frames(rng, hm, lens, scale=1.5)
     X[5] += 60.0
@@ -97,7 +37,7 @@ def test_log_emission_and_lattice(G, ctx, N, M, D):
     ref = log_emission(hm, X)
     close_logb(logb, ref, 1e-11)
     assert np.isfinite(ref[5]).all()
-    check_lattice(hm.A, logb, lens, path, score)
+    check_viterbi_lattice(hm.A, logb, lens, path, score)
     assert np.isfinite(score[[0, 3]]).all()  # (T >= N: the last state is reached)
     fm.close()
     corpus.close()
@@ -110,12 +50,12 @@ def test_lattice_bit_identical(G, ctx, kind):
     N, M, D = 20, 3, 8
     if kind == "ties":
         # every state the same mixture and every transition 1/N: all candidates tie
-        hm = rand_fmodel(G, rng, N, M, D, A=np.full((N, N), 1.0 / N))
+        hm = rand_fmodel(G, rng, N, M, D, A=np.full((N, N), 1.0 / N), spread=0.3, asym=True)
         for a in (hm.c, hm.mean, hm.inv_cov, hm.det):
             a[:] = a[0]
         hm = G.HostFullModel(hm.A, hm.c, hm.mean, hm.inv_cov, hm.det)
     else:
-        hm = rand_fmodel(G, rng, N, M, D, A=ergodic(rng, N) if kind == "ergodic" else None)
+        hm = rand_fmodel(G, rng, N, M, D, A=ergodic(rng, N) if kind == "ergodic" else None, spread=0.3, asym=True)
     lens = [40, 1, 3, 0, 19, 120, 2, 0, 64]
     X = frames(rng, hm, lens, scale=1.0)
     fm, corpus = ctx.full_model(hm), ctx.corpus(X, lens)
@@ -124,16 +64,16 @@ def test_lattice_bit_identical(G, ctx, kind):
     if kind == "ties":
         assert (logb == logb[:, :1]).all()
         assert np.isfinite(score[[0, 2, 4, 5, 6, 8]]).all() and score[1] == -np.inf  # (T = 1: state 0)
-    check_lattice(hm.A, logb, lens, path, score)
+    check_viterbi_lattice(hm.A, logb, lens, path, score)
     assert score[3] == 0.0 and score[7] == 0.0
     # one frame per model size class: L = 16, 32, 64 lanes
     for n in (5, 31, 64):
-        h = rand_fmodel(G, rng, n, 2, 4, A=ergodic(rng, n) if kind != "banded" else None)
+        h = rand_fmodel(G, rng, n, 2, 4, A=ergodic(rng, n) if kind != "banded" else None, spread=0.3, asym=True)
         ls = [n // 2 + 1, 1, 2 * n]
         Xn = frames(rng, h, ls)
         f, cp = ctx.full_model(h), ctx.corpus(Xn, ls)
         p, s = ctx.viterbi_full(f, cp)
-        check_lattice(h.A, ctx.fetch(G.BUF_B, (cp.frames, n)), ls, p, s)
+        check_viterbi_lattice(h.A, ctx.fetch(G.BUF_B, (cp.frames, n)), ls, p, s)
         f.close()
         cp.close()
     fm.close()
@@ -142,7 +82,7 @@ def test_lattice_bit_identical(G, ctx, kind):
 
 def test_empty_corpus_touches_nothing(G, ctx):
     rng = np.random.default_rng(4)
-    hm = rand_fmodel(G, rng, 5, 2, 6)
+    hm = rand_fmodel(G, rng, 5, 2, 6, spread=0.3, asym=True)
     fm = ctx.full_model(hm)
     corpus = ctx.corpus(np.zeros((0, 6)), np.zeros(0, dtype=np.int32))
     lib = ctx.lib
@@ -162,7 +102,7 @@ def test_finite_where_the_forward_score_is_not(G, ctx):
     """frames far from every Gaussian: score_full gives -inf / NaN (linear densities of 0), the
     log-domain Viterbi a finite score equal to the restatement's within rel 1e-11"""
     rng = np.random.default_rng(11)
-    hm = rand_fmodel(G, rng, 6, 2, 9, spread=0.5)
+    hm = rand_fmodel(G, rng, 6, 2, 9, spread=0.5, asym=True)
     lens = [50, 31, 8, 80, 12, 40]
     X = frames(rng, hm, lens, scale=0.7)
     off = offsets(lens)
@@ -187,7 +127,7 @@ def test_diagonal_inverse_covariance_is_the_diagonal_viterbi(G, ctx):
     near-ties along them), the scores within rel 1e-11"""
     rng = np.random.default_rng(21)
     for N, M, D, A in ((7, 3, 12, None), (9, 2, 5, ergodic(rng, 9))):
-        hf = rand_fmodel(G, rng, N, M, D, spread=0.8, A=A)
+        hf = rand_fmodel(G, rng, N, M, D, spread=0.8, A=A, asym=True)
         iv = rng.uniform(0.5, 2.0, (N, M, D))
         hf.inv_cov = np.zeros((N, M, D, D))
         hf.inv_cov[..., np.arange(D), np.arange(D)] = iv
@@ -231,7 +171,7 @@ def test_batch_shipped_models(G, ctx):
         assert np.array_equal(batch[k], one, equal_nan=True), k
         N = hms[k].N
         assert np.array_equal(logb[:, bo:bo + N], ctx.fetch(G.BUF_B, (corpus.frames, N)), equal_nan=True), k
-        check_lattice(hms[k].A, logb[:, bo:bo + N], lens, path, one)
+        check_viterbi_lattice(hms[k].A, logb[:, bo:bo + N], lens, path, one)
         bo += N
     for o in fms + [corpus]:
         o.close()
@@ -243,7 +183,7 @@ def test_batch_vocabulary_larger_than_one_tile(G, ctx):
     base = rng.normal(0.0, 1.5, (1, 1, 16))
     sizes = [15] * 46 + [1, 33, 64, 7]
     hms = [rand_fmodel(G, rng, n, 5, 16, spread=0.5, base=base, word=f"w{k}",
-                       A=ergodic(rng, n) if k % 9 == 4 else None) for k, n in enumerate(sizes)]
+                       A=ergodic(rng, n) if k % 9 == 4 else None, asym=True) for k, n in enumerate(sizes)]
     lens = rng.integers(20, 90, 240)
     lens[[3, 77]] = [0, 1]
     X = base[0, 0] + rng.normal(0.0, 1.0, (int(lens.sum()), 16))
@@ -264,7 +204,7 @@ def test_special_values_refusals_and_workspace(G, ctx):
     """c = 0 gives -inf and det = 0 gives NaN (the formula's values); the refusals of the full calls;
     score_full unchanged after viterbi_full; the diagonal row API refuses the log densities"""
     rng = np.random.default_rng(41)
-    hm = rand_fmodel(G, rng, 5, 2, 6)
+    hm = rand_fmodel(G, rng, 5, 2, 6, spread=0.3, asym=True)
     hm.c[1] = 0.0          # state 1: every e = -inf
     hm.det[3, 1] = 0.0     # state 3: lk = +inf
     lens = [30, 20]
@@ -275,11 +215,11 @@ def test_special_values_refusals_and_workspace(G, ctx):
     logb = ctx.fetch(G.BUF_B, (corpus.frames, 5))
     assert (logb[:, 1] == -np.inf).all() and np.isnan(logb[:, 3]).all()
     close_logb(logb, log_emission(hm, X), 1e-11)
-    check_lattice(hm.A, logb, lens, path, score)
+    check_viterbi_lattice(hm.A, logb, lens, path, score)
     assert np.array_equal(ctx.score_full(fm, corpus), s1, equal_nan=True)
 
-    h3 = rand_fmodel(G, rng, 5, 3, 6)
-    h7 = rand_fmodel(G, rng, 5, 2, 7)
+    h3 = rand_fmodel(G, rng, 5, 3, 6, spread=0.3, asym=True)
+    h7 = rand_fmodel(G, rng, 5, 2, 7, spread=0.3, asym=True)
     f3, f7 = ctx.full_model(h3), ctx.full_model(h7)
     assert code(G, lambda: ctx.viterbi_full_batch([fm, f3], corpus)) == G.ERR_UNSUPPORTED  # M differs
     assert code(G, lambda: ctx.viterbi_full_batch([fm, f7], corpus)) == G.ERR_UNSUPPORTED  # D differs
@@ -312,7 +252,8 @@ def test_reproducible_and_timed(G, ctx):
     """repeated calls are bitwise equal; the kernels count under GHMM_K_EMISSION / GHMM_K_VITERBI"""
     rng = np.random.default_rng(61)
     base = rng.normal(0.0, 1.0, (1, 1, 13))
-    hms = [rand_fmodel(G, rng, n, 4, 13, base=base, A=ergodic(rng, n) if n == 9 else None) for n in (6, 9, 20)]
+    hms = [rand_fmodel(G, rng, n, 4, 13, base=base, A=ergodic(rng, n) if n == 9 else None, spread=0.3, asym=True)
+           for n in (6, 9, 20)]
     lens = rng.integers(1, 200, 50)
     X = base[0, 0] + rng.normal(0.0, 1.0, (int(lens.sum()), 13))
     corpus = ctx.corpus(X, lens)

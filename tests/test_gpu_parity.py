@@ -21,41 +21,11 @@ import pytest
 import oracle_lib as O
 from conftest import GOLDEN
 from _load import PKG_DIR
+from fullcov_support import RTOL, assert_close  # noqa: F401  (profiles/ call them through this module)
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-8          # asserted
 NORTH_STAR_RTOL = 1e-5  # the bar
-
-
-def assert_close(got, ref, rtol=RTOL, floor=1e-13, what="", rows=False):
-    """|got-ref| <= rtol*|ref| + floor*scale; non-finite entries must agree in kind.
-    scale = max|ref| over the whole array, or (rows=True: per-frame quantities b, alpha^, beta^,
-    gamma, post, whose frames span tens of decades) over the entry's own frame, so that an
-    entry is only excused when it is 13 decades below the largest value OF ITS FRAME."""
-    got = np.asarray(got, dtype=np.float64)
-    ref = np.asarray(ref, dtype=np.float64)
-    if rows and ref.ndim >= 2:
-        r2 = np.abs(ref.reshape(ref.shape[0], -1))
-        r2 = np.where(np.isfinite(r2), r2, 0.0)
-        rmax = r2.max(axis=1, keepdims=True)
-        # (a frame whose reference entries are all 0 — e.g. beta^ of an utterance shorter than the
-        # model, underflown in the reference's scaling — has no scale of its own: the array's)
-        rmax = np.where(rmax > 0.0, rmax, r2.max() if r2.size else 0.0)
-        scale = np.broadcast_to(rmax, r2.shape).ravel()
-    else:
-        scale = None
-    got, ref = got.ravel(), ref.ravel()
-    assert got.shape == ref.shape, what
-    fin = np.isfinite(ref)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), f"{what}: NaN pattern differs"
-    assert np.array_equal(got[~fin & ~np.isnan(ref)], ref[~fin & ~np.isnan(ref)]), f"{what}: inf differs"
-    if fin.any():
-        sc = np.abs(ref[fin]).max() if scale is None else scale[fin]
-        err = np.abs(got[fin] - ref[fin])
-        tol = rtol * np.abs(ref[fin]) + floor * sc
-        worst = (err / np.maximum(tol, 1e-320)).max()
-        assert worst <= 1.0, f"{what}: worst error {worst:.3g} x tolerance"
 
 
 def assert_frames(got, ref, what, rtol=RTOL):
