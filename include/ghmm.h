@@ -502,6 +502,48 @@ int ghmm_stats_allreduce(ghmm_ctx *ctx, ghmm_stats *stats, ghmm_comm *comm);
  * all-reduced, every rank does the same cell bookkeeping and ends with the same model.
  * comm == NULL: this rank's corpus alone (= ghmm_model_init). */
 int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_comm *comm);
+/* The full-covariance trainer's initial model (creating_initial_model, TFF:731-1134) from a corpus in
+ * HBM: ghmm_init_model_full's definition (below), computed by HIP kernels and written into `fm` in
+ * place — A, c, mean, the matrix slot, det, and den / lk / log A formed on the device as
+ * ghmm_mstep_full_dev forms them.  The model's band flag is set (A is one-step left-to-right).
+ * comm == NULL: this rank's corpus alone.  Otherwise the corpus is one rank's shard: every pass's sums
+ * are all-reduced on the stream (ghmm_stats_allreduce's collective) and every rank ends with the same
+ * model, as in ghmm_model_init_comm.
+ * Stream: every pass is enqueued on the context's stream with no host round trip between them, and the
+ * call RETURNS WITHOUT WAITING for them, like ghmm_mstep_full_dev; ghmm_fmodel_get, ghmm_ctx_sync or
+ * any later call on the same context is ordered after it.
+ *   Segmentation: uniform, every utterance cut into N runs of T / N frames, the first T % N runs one
+ *     frame longer (TFF:1005-1013); state i owns run i.  A state that owns no frame gets the host's
+ *     0/0 values (NaN mean, matrix and weight, det 0).
+ *   A: init_transition_probab (TFF:772-791), a_ij = 1 / min(2, N - i) for j = i, i + 1, else 0.
+ *   Cells (init_mix_mean, TFF:970-1134): the state's mean first; while 2n < M every cell is split
+ *     x1.05 / x0.95, otherwise the M - n cells of largest distortion are split x1.005 / x0.995, in
+ *     `sorting`'s order (adjacent swaps, strict <).  Each level runs five nearest-mean passes: squared
+ *     Euclidean distance summed in coefficient order, strict < from 1e20 so the lowest cell wins a tie
+ *     and a cell whose mean is NaN is never chosen.  After every pass mean = sum / count, and empty
+ *     cells are re-seeded x1.005 / x0.995 from the cells of largest distortion, in the host's order.
+ *   Covariance (init_mix_param, TFF:810-952): one more classification against the final cells; each
+ *     cell's upper triangle around the CELL MEAN (not the mean of the frames now assigned), divided by
+ *     the count, the diagonal floored at 1e-5, mirrored; inv_cov_matrix per Gaussian as in
+ *     ghmm_mstep_full_dev (D = 1: det = var, inverse = 1 / var) WITHOUT treat_zero_det; weights =
+ *     count / (frames of the state), floored at 1e-5 and renormalised in index order; mean = the cell.
+ *   One difference: a frame farther than 1e20 from every cell takes cell 0 (the host carries the
+ *     previous frame's cell).  Not reachable on finite features of sane magnitude.
+ * Given equal sums the quotients, the inverse, det and the weights are the host's bit for bit (the
+ * shared, uncontracted bodies of the device M-step).  The sums themselves are added block by block in a
+ * fixed order, so they differ from the host's frame-order sums in the last bits; the discrete parts (A,
+ * every assignment and count, hence c where no floor applies) equal the host's wherever no frame sits
+ * within rounding of a tie between two cells.  No floating-point atomics: two calls on the same inputs
+ * give the same bits.
+ * Caps: ghmm_fmodel's (N <= 64, D <= 48), and M <= 64 — above it the call returns
+ * GHMM_ERR_UNSUPPORTED, launches nothing and leaves the model as it is (ghmm_init_model_full has no
+ * such cap).  GHMM_OPT_ROBUST set: GHMM_ERR_UNSUPPORTED.  An empty corpus, a corpus of another D, a
+ * null model or corpus: GHMM_ERR_ARG.
+ * The context's workspace (GHMM_BUF_*) is overwritten: afterwards GHMM_BUF_GAMMA and GHMM_BUF_POST hold
+ * the last classification's one-hot rows, and nothing an earlier E-step left is reused.  Counted under
+ * GHMM_K_PREPARE (the passes and the last classification), GHMM_K_REDUCE (the cell bookkeeping and
+ * the reductions), GHMM_K_MIXSTATS (the covariance sums) and GHMM_K_MSTEP (the finishing launches). */
+int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_comm *comm);
 
 /* ------------------------------------------------- host side: file formats */
 

@@ -339,12 +339,14 @@ __device__ inline void fm_tri(int q, int D, int &k, int &l)
     l = r + (q - o);
 }
 
-__global__ void __launch_bounds__(FM_THREADS)
-k_fmstep_gauss(int N, int M, int D, const double *__restrict__ stats, double *__restrict__ mean,
-               double *__restrict__ inv_cov, double *__restrict__ det)
+// INIT is ghmm_fmodel_init's variant (init_mix_param, TFF:883-930): every Gaussian is formed from the
+// sums (there is no den_c to be zero) and its mean, which is the k-means cell, is kept
+template <bool INIT>
+__device__ __forceinline__ void fm_gauss_body(int N, int M, int D, const double *__restrict__ stats,
+                                              double *__restrict__ mean, double *__restrict__ inv_cov,
+                                              double *__restrict__ det, double *fm_lds)
 {
 #pragma clang fp contract(off)
-    extern __shared__ double fm_lds[];
     const int g = blockIdx.x, i = g / M, tid = threadIdx.x, G = N * M, DS = D | 1, DT = D * (D + 1) / 2;
     const double *den_c = stats + (size_t)N * N + N, *num_c = den_c + N, *num_mu = num_c + G;
     const double *num_cov = num_mu + (size_t)G * D;
@@ -352,11 +354,12 @@ k_fmstep_gauss(int N, int M, int D, const double *__restrict__ stats, double *__
     double *cv = inv_cov + (size_t)g * D * D;
     // updating_mix_param (TFF:1951-2000); a state with den_c == 0 keeps its slot: last iteration's
     // inverse, inverted again below
-    const bool upd = den_c[i] != 0.0;
+    const bool upd = INIT || den_c[i] != 0.0;
     if (upd) {
         const double ncg = num_c[g];
         const double *nc = num_cov + (size_t)g * DT;
-        for (int k = tid; k < D; k += FM_THREADS) mean[(size_t)g * D + k] = num_mu[(size_t)g * D + k] / ncg;
+        if constexpr (!INIT)
+            for (int k = tid; k < D; k += FM_THREADS) mean[(size_t)g * D + k] = num_mu[(size_t)g * D + k] / ncg;
         for (int q = tid; q < DT; q += FM_THREADS) {
             int k, l;
             fm_tri(q, D, k, l);
@@ -437,10 +440,22 @@ k_fmstep_gauss(int N, int M, int D, const double *__restrict__ stats, double *__
 }
 
 __global__ void __launch_bounds__(FM_THREADS)
-k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double norm2pi, int delta,
-               double *__restrict__ A, double *__restrict__ c, double *mean, double *inv_cov,
-               double *__restrict__ det, double *__restrict__ den, double *__restrict__ lk,
-               double *__restrict__ logA)
+k_fmstep_gauss(int N, int M, int D, const double *__restrict__ stats, double *__restrict__ mean,
+               double *__restrict__ inv_cov, double *__restrict__ det)
+{
+    extern __shared__ double fm_lds[];
+    fm_gauss_body<false>(N, M, D, stats, mean, inv_cov, det, fm_lds);
+}
+
+// INIT is ghmm_fmodel_init's variant: the row of A is init_transition_probab's formula (TFF:772-791),
+// the weights are count / (frames of the state) (TFF:932-948; the state's frames are the sum of its
+// cells' counts, exact), and there is no treat_zero_det (TFF:918-930)
+template <bool INIT>
+__device__ __forceinline__ void fm_state_body(int N, int M, int D, const double *__restrict__ stats, double norm2pi,
+                                              int delta, double *__restrict__ A, double *__restrict__ c,
+                                              double *mean, double *inv_cov, double *__restrict__ det,
+                                              double *__restrict__ den, double *__restrict__ lk,
+                                              double *__restrict__ logA)
 {
 #pragma clang fp contract(off)
     __shared__ double cw[FM_MAXM], dl[FM_MAXM];
@@ -449,20 +464,32 @@ k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double nor
     const int i = blockIdx.x, tid = threadIdx.x;
     const double *num_a = stats, *den_a = num_a + (size_t)N * N, *den_c = den_a + N, *num_c = den_c + N;
     // updating_transition_probab (TFF:1907-1929): a row with den_a == 0 is kept; 0 outside the band
-    const double da = den_a[i];
+    const double da = INIT ? 0.0 : den_a[i];
     for (int j = tid; j < N; j += FM_THREADS) {
         const size_t q = (size_t)i * N + j;
-        double a = A[q];
-        if (da != 0.0) {
-            a = (j >= i && j - i <= delta) ? num_a[q] / da : 0.0;
+        double a;
+        if constexpr (INIT) {
+            if (j > delta + i || j < i) a = 0.0;
+            else if (delta + 1 > N - i) a = 1.0 / (double)(N - i);
+            else a = 1.0 / (double)(delta + 1);
             A[q] = a;
+        } else {
+            a = A[q];
+            if (da != 0.0) {
+                a = (j >= i && j - i <= delta) ? num_a[q] / da : 0.0;
+                A[q] = a;
+            }
         }
         logA[q] = a > 0.0 ? log(a) : -INFINITY;
     }
-    const double dc = den_c[i];
+    double dc = den_c[i];
+    if constexpr (INIT) {
+        dc = 0.0; // (whole numbers: any order gives the same sum)
+        for (int m = 0; m < M; m++) dc += num_c[(size_t)i * M + m];
+    }
     for (int m = tid; m < M; m += FM_THREADS) {
         const size_t g = (size_t)i * M + m;
-        cw[m] = dc != 0.0 ? num_c[g] / dc : c[g];
+        cw[m] = (INIT || dc != 0.0) ? num_c[g] / dc : c[g];
         dl[m] = det[g];
     }
     __syncthreads();
@@ -475,7 +502,7 @@ k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double nor
         }
         for (int k = 0; k < M; k++) cw[k] = cw[k] / sum;
         int np = 0;
-        if (D > 1) {
+        if (!INIT && D > 1) {
             // treat_zero_det (TFF:2226-2265).  sorting (TFF:1331-1356): adjacent swaps, strict '<',
             // on the determinants as inv_cov_matrix left them
             for (int k = 0; k < M; k++) idx[k] = k;
@@ -531,6 +558,249 @@ k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double nor
         den[g] = dn;
         lk[g] = log(cg) - log(dn);
     }
+}
+
+__global__ void __launch_bounds__(FM_THREADS)
+k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double norm2pi, int delta,
+               double *__restrict__ A, double *__restrict__ c, double *mean, double *inv_cov,
+               double *__restrict__ det, double *__restrict__ den, double *__restrict__ lk,
+               double *__restrict__ logA)
+{
+    fm_state_body<false>(N, M, D, stats, norm2pi, delta, A, c, mean, inv_cov, det, den, lk, logA);
+}
+
+// ------------------------------------------------ the trainer's initial model on the device (ghmm_fmodel_init)
+//
+// creating_initial_model (TFF:731-1134; csrc/ghmm_fulltrain.c ghmm_init_model_full and csrc/ghmm_init.c
+// ghmm_init_cells_) without a trip to the host.  Per k-means pass:
+//   k_finit_pass   classifies the frames and accumulates, per cell, D coefficient sums, the count and the
+//                  distortion — the E2 = D + 2 numbers a pass needs, nothing of the covariance;
+//   k_finit_cells  a block per state: adds the blocks' partials in block order, then the host loop's cell
+//                  bookkeeping (quotients, re-seeding of empty cells, the split that opens the next level).
+// The last pass (init_mix_param) is k_finit_pass once more, now writing the frames' one-hot gamma and post
+// rows (the same classification rule in every pass), k_fullstats on them — its dif is taken around the
+// model's mean, which is the cell — then k_finit_gauss / k_finit_state: the INIT variants of the M-step's
+// bodies above.
+//
+// k_finit_pass: block (k, p) = state k, utterances [p * upb, (p + 1) * upb).  Under the uniform
+// segmentation state k owns one contiguous run of every utterance (the first T % N runs one frame longer),
+// so the block walks those runs only, FI_FRAMES frames at a time through LDS (rows D | 1 doubles apart:
+// a lane per frame reads conflict-free).  Classification: wave w of the four takes cells w, w + 4, ... in
+// ascending order with the host's strict '<' from 1e20 (a NaN distance is never smaller); lane r of wave 0
+// then takes the smallest of the four candidates, the lowest cell among equals — the cell the host's one
+// ascending scan keeps.  No candidate: cell 0 (the host carries the previous frame's cell; unreachable on
+// finite features).  The distance is the host's sum, uncontracted, in coefficient order.
+// Accumulation: entry (cell c, l) of the block's [n_cells][E2] table in LDS belongs to ONE thread, the one
+// with tid % E2 == l and tid / E2 == c % (FI_THREADS / E2), which walks the staged frames in order: no
+// atomics, and a block's sums are the frames' in corpus order.  l < D: x[l]; l == D: 1; l == D + 1: the distance.
+constexpr int FI_THREADS = 256;
+constexpr int FI_FRAMES = 64;  // frames per stage: one lane of each wave per frame
+constexpr int FI_MAXM = 64;    // cells per state (ghmm.h states it)
+constexpr double FI_FAR = 1.0e20; // TFF:1179-1215
+
+__host__ __device__ inline size_t fi_pass_lds_bytes(int M, int D)
+{
+    return ((size_t)M * (D | 1) + (size_t)M * (D + 2) + (size_t)FI_FRAMES * (D | 1)) * sizeof(double);
+}
+
+__global__ void __launch_bounds__(FI_THREADS)
+k_finit_pass(int N, int M, int D, int n_cells, int classify, int U, int upb, const double *__restrict__ X,
+             const long long *__restrict__ off, const double *__restrict__ cells, double *__restrict__ part,
+             double *__restrict__ gamma, double *__restrict__ post)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double fi_lds[];
+    __shared__ double cand_d[FI_THREADS / WAVE][FI_FRAMES];
+    __shared__ int cand_c[FI_THREADS / WAVE][FI_FRAMES];
+    __shared__ double dmin[FI_FRAMES];
+    __shared__ int cid[FI_FRAMES], cgr[FI_FRAMES];
+    constexpr int NW = FI_THREADS / WAVE;
+    const int k = blockIdx.x, p = blockIdx.y, tid = threadIdx.x, DS = D | 1, E2 = D + 2;
+    const int w = tid / WAVE, lane = tid % WAVE;
+    double *cl = fi_lds;               // [n_cells][DS]
+    double *acc = cl + (size_t)M * DS; // [n_cells][E2]
+    double *xs = acc + (size_t)M * E2; // [FI_FRAMES][DS]
+    for (int e = tid; e < n_cells * D; e += FI_THREADS) {
+        const int c = e / D;
+        cl[c * DS + (e - c * D)] = cells[(size_t)k * M * D + e];
+    }
+    for (int e = tid; e < n_cells * E2; e += FI_THREADS) acc[e] = 0.0;
+    const int ngrp = FI_THREADS / E2, l = tid % E2, grp = tid / E2; // (E2 <= 50: at least five groups)
+    const int u0 = p * upb, u1 = (u0 + upb < U) ? u0 + upb : U;
+    for (int u = u0; u < u1; u++) {
+        const long long o = off[u];
+        const int T = (int)(off[u + 1] - o), q = T / N, r = T % N;
+        const int rb = k * q + (k < r ? k : r), re = rb + q + (k < r ? 1 : 0);
+        for (int s = rb; s < re; s += FI_FRAMES) {
+            const int nf = (re - s < FI_FRAMES) ? re - s : FI_FRAMES;
+            const double *src = X + (o + s) * D;
+            __syncthreads(); // (the last stage's readers, or the fills above)
+            for (int e = tid; e < nf * D; e += FI_THREADS) {
+                const int fr = e / D;
+                xs[fr * DS + (e - fr * D)] = src[e];
+            }
+            __syncthreads();
+            if (classify) {
+                if (lane < nf) {
+                    const double *x = xs + lane * DS;
+                    double best = FI_FAR;
+                    int cell = -1;
+                    for (int c = w; c < n_cells; c += NW) {
+                        const double *mu = cl + c * DS;
+                        double dist = 0.0;
+                        for (int d = 0; d < D; d++) {
+                            const double a = mu[d] - x[d];
+                            dist += a * a;
+                        }
+                        if (dist < best) {
+                            best = dist;
+                            cell = c;
+                        }
+                    }
+                    cand_d[w][lane] = best;
+                    cand_c[w][lane] = cell;
+                }
+                __syncthreads();
+                if (tid < nf) {
+                    double best = FI_FAR;
+                    int cell = -1;
+                    for (int v = 0; v < NW; v++) {
+                        const double d = cand_d[v][tid];
+                        const int c = cand_c[v][tid];
+                        if (c >= 0 && (cell < 0 || d < best || (d == best && c < cell))) {
+                            best = d;
+                            cell = c;
+                        }
+                    }
+                    if (cell < 0) cell = 0;
+                    dmin[tid] = best;
+                    cid[tid] = cell;
+                    cgr[tid] = cell % ngrp;
+                }
+            } else if (tid < nf) { // the state's mean: one cell, nothing to compare (TFF:1005-1030)
+                dmin[tid] = 0.0;
+                cid[tid] = 0;
+                cgr[tid] = 0;
+            }
+            __syncthreads();
+            if (gamma) { // the last pass: the frames' one-hot rows, each written whole by the block that owns the frame
+                const int G = N * M;
+                for (int e = tid; e < nf * N; e += FI_THREADS) {
+                    const int fr = e / N;
+                    gamma[(o + s) * N + e] = (e - fr * N) == k ? 1.0 : 0.0;
+                }
+                for (int e = tid; e < nf * G; e += FI_THREADS) {
+                    const int fr = e / G;
+                    post[(o + s) * G + e] = (e - fr * G) == k * M + cid[fr] ? 1.0 : 0.0;
+                }
+            }
+            if (grp < ngrp)
+                for (int fr = 0; fr < nf; fr++)
+                    if (cgr[fr] == grp) {
+                        const double v = l < D ? xs[fr * DS + l] : (l == D ? 1.0 : dmin[fr]);
+                        acc[cid[fr] * E2 + l] += v;
+                    }
+        }
+    }
+    __syncthreads();
+    double *out = part + ((size_t)p * N + k) * M * E2;
+    for (int e = tid; e < n_cells * E2; e += FI_THREADS) out[e] = acc[e];
+}
+
+// the blocks' partials [P][N][M][E2] in block order into one slice [N][M][E2] (a corpus sharded over
+// ranks: this slice is what is all-reduced; k_finit_cells then reads it as P = 1)
+__global__ void __launch_bounds__(256)
+k_finit_reduce(long long n, int P, const double *__restrict__ part, double *__restrict__ sums)
+{
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    double v = 0.0;
+    for (int p = 0; p < P; p++) v += part[(size_t)p * n + e];
+    sums[e] = v;
+}
+
+// The cell bookkeeping between two passes (csrc/ghmm_init.c ghmm_init_cells_, TFF:1043-1270): the host
+// loop's operations in the host loop's order, as k_init_cells has them for the diagonal layout — block =
+// state, thread = coefficient (every thread walks the same order of cells and only ever touches its own
+// coefficients).  (up1, down1) is the doubling split, (up2, down2) the split of the cells of largest
+// distortion and the re-seeding of empty cells.  M <= FI_MAXM.
+__global__ void __launch_bounds__(64)
+k_finit_cells(int N, int M, int D, int n_cells, int do_split, int first, int P, const double *__restrict__ part,
+              double up1, double down1, double up2, double down2, double *__restrict__ cells)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double fi_st[]; // [n_cells][E2]
+    __shared__ double dist[FI_MAXM];
+    __shared__ int idx[FI_MAXM];
+    const int k = blockIdx.x, tid = threadIdx.x, E2 = D + 2;
+    const size_t slice = (size_t)N * M * E2;
+    for (int e = tid; e < n_cells * E2; e += 64) {
+        double v = 0.0;
+        for (int p = 0; p < P; p++) v += part[(size_t)p * slice + (size_t)k * M * E2 + e];
+        fi_st[e] = v;
+    }
+    __syncthreads();
+    for (int j = tid; j < n_cells; j += 64) dist[j] = fi_st[j * E2 + D + 1];
+    __syncthreads();
+    double *ck = cells + (size_t)k * M * D;
+    // indices by decreasing key, adjacent-swap passes with strict '<' (TFF:1289-1315)
+    auto order_desc = [&](int n) {
+        if (tid == 0) {
+            for (int i = 0; i < n; i++) idx[i] = i;
+            bool done = false;
+            while (!done) {
+                done = true;
+                for (int i = 0; i < n - 1; i++)
+                    if (dist[idx[i]] < dist[idx[i + 1]]) {
+                        const int t = idx[i];
+                        idx[i] = idx[i + 1];
+                        idx[i + 1] = t;
+                        done = false;
+                    }
+            }
+        }
+        __syncthreads();
+    };
+    auto split_cell = [&](int from, int to, double up, double down) {
+        for (int l = tid; l < D; l += 64) {
+            const double v = ck[(size_t)from * D + l], hi = v * up;
+            ck[(size_t)to * D + l] = hi;
+            ck[(size_t)from * D + l] = (from == to ? hi : v) * down; // (a cell re-seeded from itself)
+        }
+    };
+    for (int j = 0; j < n_cells; j++)
+        for (int l = tid; l < D; l += 64) ck[(size_t)j * D + l] = fi_st[j * E2 + l] / fi_st[j * E2 + D];
+    if (!first) { // empty cells are re-seeded from the cells of largest distortion
+        order_desc(n_cells);
+        int i = 0;
+        for (int j = 0; j < n_cells; j++)
+            if (fi_st[j * E2 + D] == 0.0) split_cell(idx[i++], j, up2, down2);
+    }
+    if (do_split) {
+        if (2 * n_cells < M) {
+            for (int i = 0; i < n_cells; i++) split_cell(i, n_cells + i, up1, down1);
+        } else {
+            order_desc(n_cells);
+            for (int i = 0; i < M - n_cells; i++) split_cell(idx[i], n_cells + i, up2, down2);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(FM_THREADS)
+k_finit_gauss(int N, int M, int D, const double *__restrict__ stats, double *__restrict__ mean,
+              double *__restrict__ inv_cov, double *__restrict__ det)
+{
+    extern __shared__ double fm_lds[];
+    fm_gauss_body<true>(N, M, D, stats, mean, inv_cov, det, fm_lds);
+}
+
+__global__ void __launch_bounds__(FM_THREADS)
+k_finit_state(int N, int M, int D, const double *__restrict__ stats, double norm2pi, int delta,
+              double *__restrict__ A, double *__restrict__ c, double *mean, double *inv_cov,
+              double *__restrict__ det, double *__restrict__ den, double *__restrict__ lk,
+              double *__restrict__ logA)
+{
+    fm_state_body<true>(N, M, D, stats, norm2pi, delta, A, c, mean, inv_cov, det, den, lk, logA);
 }
 
 } // namespace ghmm

@@ -109,6 +109,9 @@ struct ghmm_ctx {
     ghmm_corpus *last_c = nullptr;
     int slots = 0;             // partial-sum slots filled by the last backward / combine pass
     double *part_mu = nullptr, *part_var = nullptr, *part_m = nullptr;
+    // ghmm_fmodel_init: the k-means partials and sums, and the last pass's full-layout statistics
+    double *finit = nullptr;
+    size_t cap_finit = 0;
     // several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     double *b_stream = nullptr;
     double *b_alloc = nullptr; // b sits B_PAD_FRAMES rows inside this allocation (grow_b)
@@ -407,7 +410,7 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
                     ctx->part_denc, ctx->part_mu, ctx->part_var,  ctx->psi,     ctx->path,
                     ctx->part_m,  ctx->sinv,      ctx->sink,      ctx->wrow,    ctx->sb,
                     ctx->lpart,   ctx->logk,      ctx->b_stream,  ctx->smask,
-                    ctx->fix_mark, ctx->fix_list, ctx->fix_cnt, ctx->wide_flag};
+                    ctx->fix_mark, ctx->fix_list, ctx->fix_cnt, ctx->wide_flag, ctx->finit};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (double *p : ctx->post_s)
@@ -2745,9 +2748,9 @@ static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)
     return GHMM_OK;
 }
 
-// calc_mix_param over every frame (k_fullstats), the ordered reduction of its partials, and the
-// utterance sums (num_a, den_a, den_c, log P, count) by k_reduce_all without its Gaussian blocks
-static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+// calc_mix_param over every frame (k_fullstats, from ctx->gamma and ctx->post) into *P_out frame-block
+// partials in ctx->part_mu
+static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, long long *P_out)
 {
     const int N = fm->N, M = fm->M, D = fm->D, G = N * M, D1 = D + 1;
     const long long E = (long long)G * fs_elems(D);
@@ -2765,7 +2768,6 @@ static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_st
     fpb = ((fpb + FSn - 1) / FSn) * FSn;
     if (fpb < FSn) fpb = FSn;
     P = c->F > 0 ? (c->F + fpb - 1) / fpb : 0;
-    double *stats_c = s->v + (size_t)N * N + 2 * (size_t)N;
     if (P > 0) {
         if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, (size_t)P * (size_t)E))) return rc;
         kscope ks(ctx, GHMM_K_MIXSTATS);
@@ -2773,11 +2775,31 @@ static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_st
                            c->F, fpb, FSn, c->X, ctx->gamma, ctx->post, fm->mean, ctx->part_mu);
         if ((rc = launch_ok("k_fullstats"))) return rc;
     }
+    *P_out = P;
+    return GHMM_OK;
+}
+
+// the ordered reduction of those partials into num_c / num_mu / num_cov at stats_c
+static int run_fullstats_reduce(ghmm_ctx *ctx, const ghmm_fmodel *fm, long long P, double *stats_c)
+{
+    const int G = fm->N * fm->M;
+    const long long E = (long long)G * fs_elems(fm->D);
+    hipLaunchKernelGGL(k_fullstats_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, G, fm->D,
+                       (int)P, (const double *)ctx->part_mu, stats_c);
+    return launch_ok("k_fullstats_reduce");
+}
+
+// the statistics of an E-step: both of the above, and the utterance sums (num_a, den_a, den_c, log P,
+// count) by k_reduce_all without its Gaussian blocks
+static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    const int N = fm->N, M = fm->M, D = fm->D;
+    int rc;
+    long long P = 0;
+    if ((rc = run_fullstats_part(ctx, fm, c, &P))) return rc;
     {
         kscope ks(ctx, GHMM_K_REDUCE);
-        hipLaunchKernelGGL(k_fullstats_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, G, D,
-                           (int)P, (const double *)ctx->part_mu, stats_c);
-        if ((rc = launch_ok("k_fullstats_reduce"))) return rc;
+        if ((rc = run_fullstats_reduce(ctx, fm, P, s->v + (size_t)N * N + 2 * (size_t)N))) return rc;
         reduce_args ra{};
         ra.N = N; ra.M = M; ra.D = D; ra.U = c->U; ra.delta = (int)ctx->delta;
         ra.S = ctx->slots;
@@ -3088,4 +3110,128 @@ extern "C" int ghmm_stats_allreduce(ghmm_ctx *ctx, ghmm_stats *s, ghmm_comm *cm)
     // in place, on the stream that carries the E-step before it and the M-step after it
     RCCL_TRY(api, api->AllReduce(s->v, s->v, s->n, ncclDouble, ncclSum, cm->comm, ctx->stream));
     return GHMM_OK;
+}
+
+// ------------------------------------------------ the full-covariance trainer's initial model
+// creating_initial_model (TFF:731-1134) from a corpus in HBM: the kernels of ghmm_fullcov.hpp
+// (k_finit_*), enqueued back to back on the context's stream; nothing is downloaded and the stream is
+// not synchronised.  ctx->finit holds, in this order, the passes' block partials [P][N][M][D + 2], one
+// slice [N][M][D + 2] of their sums (a communicator's all-reduce runs on it), and the last pass's
+// statistics in the full layout.
+extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_comm *cm)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    ARG_CHECK(c, "null corpus");
+    if ((rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(c->U > 0 && c->F > 0, "empty corpus");
+    if (fm->M > FI_MAXM) {
+        ghmm_set_error("the device initial model takes up to %d Gaussians per state (asked: %d); "
+                       "ghmm_init_model_full has no such cap", FI_MAXM, fm->M);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    const rccl_api *api = nullptr;
+    if (cm) {
+        ARG_CHECK(cm->comm, "null communicator");
+        ARG_CHECK(cm->device == ctx->device, "communicator and context are on different devices");
+        if (!(api = rccl_or_error())) return GHMM_ERR_UNSUPPORTED;
+    }
+    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, E2 = D + 2;
+    const size_t slice = (size_t)G * E2, nfull = ghmm_stats_len_full(N, M, D);
+    // about four blocks per CU in all, as run_fullstats sizes its grid: utterance ranges per state
+    int P = (4 * ctx->cus + N - 1) / N;
+    if (P > c->U) P = c->U;
+    const int upb = (c->U + P - 1) / P;
+    P = (c->U + upb - 1) / upb;
+    if ((rc = dev_grow(&ctx->finit, &ctx->cap_finit, (size_t)(P + 1) * slice + nfull))) return rc;
+    if ((rc = dev_grow(&ctx->gamma, &ctx->cap_gamma, (size_t)c->F * N))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * G))) return rc;
+    double *part = ctx->finit, *sums = part + (size_t)P * slice, *full = sums + slice;
+    double *full_c = full + (size_t)N * N + 2 * (size_t)N;
+    const size_t pass_lds = fi_pass_lds_bytes(M, D);
+    if (pass_lds > 48 * 1024 && (rc = lds_attr(ctx, (const void *)k_finit_pass))) return rc;
+    // the workspace is rewritten (gamma and post hold the last classification's one-hot rows), and the
+    // model's parameters change: nothing an earlier pass left behind goes with either any more
+    ctx->last_m = nullptr;
+    ctx->last_c = nullptr;
+    ctx->em_m = nullptr;
+    ctx->em_c = nullptr;
+    ctx->em_epoch = -1;
+    ctx->own_bwd_done = false;
+    ctx->beta_valid = false;
+    ctx->loglik_pieces = false;
+    ctx->F = c->F;
+    ctx->U = c->U;
+    ctx->N = N;
+    ctx->G = G;
+    fm->rec.banded = true; // init_transition_probab's A: j = i or i + 1
+
+    auto pass = [&](int n_cells, int do_split, bool first) -> int {
+        int r;
+        {
+            kscope ks(ctx, GHMM_K_PREPARE);
+            hipLaunchKernelGGL(k_finit_pass, dim3((unsigned)N, (unsigned)P), dim3(FI_THREADS), pass_lds, ctx->stream,
+                               N, M, D, n_cells, first ? 0 : 1, c->U, upb, c->X, c->off, fm->mean, part,
+                               (double *)nullptr, (double *)nullptr);
+        }
+        if ((r = launch_ok("k_finit_pass"))) return r;
+        const double *src = part;
+        int np = P;
+        if (cm) { // the sums of all shards: every rank then does the same bookkeeping on the same numbers
+            {
+                kscope ks(ctx, GHMM_K_REDUCE);
+                hipLaunchKernelGGL(k_finit_reduce, dim3((unsigned)((slice + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   (long long)slice, P, (const double *)part, sums);
+            }
+            if ((r = launch_ok("k_finit_reduce"))) return r;
+            RCCL_TRY(api, api->AllReduce(sums, sums, slice, ncclDouble, ncclSum, cm->comm, ctx->stream));
+            src = sums;
+            np = 1;
+        }
+        {
+            kscope ks(ctx, GHMM_K_REDUCE);
+            hipLaunchKernelGGL(k_finit_cells, dim3((unsigned)N), dim3(64), (size_t)n_cells * E2 * sizeof(double),
+                               ctx->stream, N, M, D, n_cells, do_split, first ? 1 : 0, np, src, 1.05, 0.95, 1.005,
+                               0.995, fm->mean);
+        }
+        return launch_ok("k_finit_cells");
+    };
+    // init_mix_mean (TFF:970-1134): the state's mean, then five passes per level
+    if ((rc = pass(1, 1 < M ? 1 : 0, true))) return rc;
+    int nc = 1;
+    while (nc < M) {
+        nc = (2 * nc < M) ? 2 * nc : M;
+        for (int it = 0; it < 5; it++)
+            if ((rc = pass(nc, (it == 4 && nc < M) ? 1 : 0, false))) return rc;
+    }
+    // init_mix_param (TFF:810-952): one more classification, its one-hot rows into gamma and post;
+    // k_fullstats takes dif around the model's mean, which is the cell
+    {
+        kscope ks(ctx, GHMM_K_PREPARE);
+        hipLaunchKernelGGL(k_finit_pass, dim3((unsigned)N, (unsigned)P), dim3(FI_THREADS), pass_lds, ctx->stream, N, M,
+                           D, M, 1, c->U, upb, c->X, c->off, fm->mean, part, ctx->gamma, ctx->post);
+    }
+    long long PF = 0;
+    if ((rc = launch_ok("k_finit_pass")) || (rc = run_fullstats_part(ctx, fm, c, &PF))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_REDUCE);
+        if ((rc = run_fullstats_reduce(ctx, fm, PF, full_c))) return rc;
+    }
+    if (cm)
+        RCCL_TRY(api, api->AllReduce(full_c, full_c, (size_t)G * fs_elems(D), ncclDouble, ncclSum, cm->comm,
+                                     ctx->stream));
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_finit_gauss, dim3((unsigned)G), dim3(FM_THREADS), fm_gauss_lds_bytes(D), ctx->stream, N,
+                           M, D, (const double *)full, fm->mean, fm->inv_cov, fm->det);
+    }
+    if ((rc = launch_ok("k_finit_gauss"))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_finit_state, dim3((unsigned)N), dim3(FM_THREADS), 0, ctx->stream, N, M, D,
+                           (const double *)full, pow(2.0 * M_PI, D / 2.0), 1, fm->A, fm->c, fm->mean, fm->inv_cov,
+                           fm->det, fm->den, fm->lk, fm->logA);
+    }
+    return launch_ok("k_finit_state");
 }

@@ -22,7 +22,11 @@
  * iteration (finite where a frame's linear densities underflow) and says so in one line of output;
  * the report is the same.  GHMM_DEV_MSTEP=1 takes ghmm_mstep_full_dev for every iteration (the
  * M-step stays on the stream) and says so in one line; above that call's cap on M it says so and
- * goes back to ghmm_mstep_full.  The two variables combine freely.
+ * goes back to ghmm_mstep_full.  GHMM_DEV_INIT=1 uploads the corpus first and builds the initial model
+ * from it on the device (ghmm_fmodel_init), fetching the host copy the writer needs, and says so in one
+ * line; above that call's cap on M it says so and goes back to ghmm_init_model_full; an
+ * [initial_model] argument still wins.  The three variables combine freely; without them nothing
+ * changes.
  *
  * Several GPUs: start one process per GPU with
  *     GHMM_WORLD=<ranks> GHMM_RANK=<0..ranks-1> GHMM_COMM_ID=<a path unique to the job>
@@ -149,6 +153,8 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
     ghmm_host_fmodel hfm;
     memset(&hfm, 0, sizeof hfm);
     int rc;
+    /* GHMM_DEV_INIT=1: the initial model on the device (ghmm_fmodel_init); an [initial_model] wins */
+    int dev_init = !initial && env_int("GHMM_DEV_INIT", 0) != 0;
     if (initial) {
         if ((rc = ghmm_hmm_read_full(initial, &hfm))) die("initial model", rc);
         if (hfm.D != D) {
@@ -157,10 +163,9 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
         }
         N = hfm.N;
         M = hfm.M;
-    } else if ((rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) {
+    } else if (!dev_init && (rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) {
         die("creating initial model", rc);
     }
-    snprintf(hfm.word, sizeof hfm.word, "%s", word);
     ghmm_ctx *ctx;
     ghmm_fmodel *fm;
     ghmm_corpus *corpus;
@@ -168,7 +173,23 @@ static int train_full(const char *word, int N, int M, int D, const double *X, co
     if ((rc = ghmm_ctx_create(device, NULL, &ctx))) die("GPU context", rc);
     if ((rc = ghmm_corpus_create(ctx, X, len, n_utt, D, &corpus))) die("corpus", rc);
     if ((rc = ghmm_fmodel_create(ctx, N, M, D, &fm))) die("model", rc);
-    if ((rc = ghmm_fmodel_set(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
+    if (dev_init) {
+        /* the corpus is uploaded: the initial model from it where it lies; the host copy (the writer's)
+           is fetched.  Above the call's cap on M: the host route, as without the variable */
+        if ((rc = ghmm_fmodel_init(ctx, fm, corpus, NULL)) == GHMM_ERR_UNSUPPORTED) {
+            printf("\r\nInitial model on the host: %s", ghmm_last_error());
+            dev_init = 0;
+            if ((rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) die("creating initial model", rc);
+        } else if (rc) {
+            die("creating initial model", rc);
+        } else {
+            printf("\r\nInitial model on the device (GHMM_DEV_INIT)");
+            if ((rc = ghmm_host_fmodel_alloc(&hfm, N, M, D))) die("creating initial model", rc);
+            if ((rc = ghmm_fmodel_get(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
+        }
+    }
+    snprintf(hfm.word, sizeof hfm.word, "%s", word);
+    if (!dev_init && (rc = ghmm_fmodel_set(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
     if ((rc = ghmm_stats_create_full(ctx, N, M, D, &stats))) die("statistics", rc);
     double lp[2] = {0.0, 0.0};
 

@@ -121,6 +121,7 @@ SYMBOLS = {
     "ghmm_estep_full_log": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_mstep_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_mstep_full_dev": (C.c_int, [_vp, _vp, _vp], True),
+    "ghmm_fmodel_init": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -776,6 +777,15 @@ class FullModel:
         _check(self.ctx.lib.ghmm_fmodel_get(self.ctx.h, self.h, _d(A), _d(c), _d(mu), _d(ic),
                                             _d(det)), self.ctx.lib)
         return HostFullModel(A, c, mu, ic, det)
+
+    def init_from(self, corpus, comm=None, fetch=True):
+        """creating_initial_model (TFF:731) on the device (ghmm_fmodel_init): asynchronous on the
+        stream; returns the model as HostFullModel (fetch=False: leaves it on the device, nothing is
+        downloaded or waited for).  `comm`: the corpus is one rank's shard, every pass's sums are
+        all-reduced."""
+        _check(self.ctx.lib.ghmm_fmodel_init(self.ctx.h, self.h, corpus.h,
+                                             comm.h if comm is not None else None), self.ctx.lib)
+        return self.get() if fetch else None
 
     def dims(self):
         n, m, d = C.c_int(), C.c_int(), C.c_int()
