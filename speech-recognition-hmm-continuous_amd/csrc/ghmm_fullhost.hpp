@@ -1,0 +1,673 @@
+// ghmm_fullhost.hpp — the host side of the full-covariance entry points (recogniser RC, trainer TFF):
+// models, checks, launches of the kernels in ghmm_fullcov.hpp.  Part of ghmm_hip.hip's translation
+// unit, included once at its end: it uses that file's context, workspace and vocabulary helpers and
+// the RCCL table resolved there.
+
+// ------------------------------------------------ the full-covariance recogniser (RC)
+
+struct ghmm_fmodel {
+    int N = 0, M = 0, D = 0;
+    double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
+    double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
+    // ghmm_viterbi_full: log(c) - log(den) per Gaussian, and A > 0 ? log(A) : -inf, both formed on
+    // the host (the oracle's expressions, evaluated by the same libm)
+    double *lk = nullptr, *logA = nullptr;
+    // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
+    // run_scan_combine): N, and A (aliases the A above, owned there) with its band flag.  Nothing
+    // else of it is set; it is never passed to ghmm_model_destroy.
+    ghmm_model rec;
+};
+
+// any N (the concatenated vocabulary of ghmm_score_full_batch has hundreds of states)
+static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
+{
+    ghmm_fmodel *fm = new (std::nothrow) ghmm_fmodel();
+    if (!fm) return GHMM_ERR_ALLOC;
+    fm->N = N; fm->M = M; fm->D = D;
+    fm->rec.N = N; fm->rec.M = M; fm->rec.D = D;
+    const size_t G = (size_t)N * M;
+    // mean and inv_cov with FC_SLACK doubles behind them: the kernel's padded columns read there
+    const size_t nmean = G * D + FC_SLACK, ncov = G * D * D + FC_SLACK;
+    int rc;
+    if ((rc = dev_alloc(&fm->A, (size_t)N * N)) || (rc = dev_alloc(&fm->c, G)) ||
+        (rc = dev_alloc(&fm->mean, nmean)) || (rc = dev_alloc(&fm->inv_cov, ncov)) ||
+        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G)) || (rc = dev_alloc(&fm->lk, G)) ||
+        (rc = dev_alloc(&fm->logA, (size_t)N * N))) {
+        ghmm_fmodel_destroy(ctx, fm);
+        return rc;
+    }
+    fm->rec.A = fm->A;
+    if (hipMemsetAsync(fm->mean, 0, nmean * 8, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(fm->inv_cov, 0, ncov * 8, ctx->stream) != hipSuccess) {
+        ghmm_fmodel_destroy(ctx, fm);
+        ghmm_set_error("hipMemsetAsync failed");
+        return GHMM_ERR_HIP;
+    }
+    *out = fm;
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(out, "null output");
+    *out = nullptr;
+    ARG_CHECK(N > 0 && M > 0 && D > 0, "N, M and D must be positive");
+    if (N > 64 || D > FC_DMAX) {
+        ghmm_set_error("full-covariance models take up to 64 states and %d coefficients (asked: %d states, "
+                       "%d coefficients)", FC_DMAX, N, D);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return fmodel_alloc(ctx, N, M, D, out);
+}
+
+extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
+{
+    if (!fm) return;
+    if (ctx && ctx->last_m == &fm->rec) ctx->last_m = nullptr;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den, fm->lk, fm->logA};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    delete fm;
+}
+
+extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
+                               const double *mean, const double *inv_cov, const double *det)
+{
+    int rc = use(ctx);
+    if (ctx && fm && ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
+    if (rc) return rc;
+    ARG_CHECK(fm && A && c && mean && inv_cov && det, "null argument");
+    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
+    fm->rec.banded = true; // (as ghmm_model_set decides it: the paired scans' band-diagonal forms)
+    for (int i = 0; i < fm->N; i++)
+        for (int j = 0; j < fm->N; j++)
+            if (A[(size_t)i * fm->N + j] != 0.0 && j != i && j != i + 1) fm->rec.banded = false;
+    // calc_gaus's normaliser as the reference forms it: aux1 = pow(2 pi, D/2.0), aux2 = pow(|det|, 0.5)
+    std::vector<double> den(G), lk(G), logA(NN);
+    const double aux1 = pow(2.0 * M_PI, fm->D / 2.0);
+    for (size_t g = 0; g < G; g++) {
+        den[g] = aux1 * pow(fabs(det[g]), 0.5);
+        lk[g] = log(c[g]) - log(den[g]);
+    }
+    for (size_t k = 0; k < NN; k++) logA[k] = A[k] > 0.0 ? log(A[k]) : -INFINITY;
+    HIP_TRY(hipMemcpyAsync(fm->A, A, NN * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->c, c, G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->mean, mean, G * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->inv_cov, inv_cov, G * fm->D * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->det, det, G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->den, den.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->lk, lk.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fm->logA, logA.data(), NN * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(stream_sync(ctx)); // (pageable sources)
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_get(ghmm_ctx *ctx, ghmm_fmodel *fm, double *A, double *c, double *mean,
+                               double *inv_cov, double *det)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
+    if (A) HIP_TRY(hipMemcpyAsync(A, fm->A, NN * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c) HIP_TRY(hipMemcpyAsync(c, fm->c, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, fm->mean, G * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (inv_cov)
+        HIP_TRY(hipMemcpyAsync(inv_cov, fm->inv_cov, G * fm->D * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (det) HIP_TRY(hipMemcpyAsync(det, fm->det, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_fmodel_dims(const ghmm_fmodel *fm, int *N, int *M, int *D)
+{
+    ARG_CHECK(fm, "null model");
+    if (N) *N = fm->N;
+    if (M) *M = fm->M;
+    if (D) *D = fm->D;
+    return GHMM_OK;
+}
+
+static int check_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+{
+    if (!fm || !c) {
+        ghmm_set_error("null model or corpus");
+        return GHMM_ERR_ARG;
+    }
+    if (fm->D != c->D) {
+        ghmm_set_error("model has %d coefficients per frame, corpus has %d", fm->D, c->D);
+        return GHMM_ERR_ARG;
+    }
+    if (ctx->robust) {
+        ghmm_set_error("GHMM_OPT_ROBUST is not available with full-covariance models");
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return GHMM_OK;
+}
+
+// one k_emission_full launch; post only where MODE writes posteriors, lk only where it works in logs
+template <int DB, int MODE>
+static void launch_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+{
+    constexpr bool POST = MODE == FC_POST || MODE == FC_LOGPOST, LOG = MODE == FC_LOG || MODE == FC_LOGPOST;
+    const int nch = (fm->N + FC_SC - 1) / FC_SC;
+    const dim3 grid((unsigned)((c->F + WAVE - 1) / WAVE), (unsigned)((nch + FC_WAVES - 1) / FC_WAVES));
+    const size_t lds = (size_t)fc_lds_doubles(fm->D) * sizeof(double);
+    hipLaunchKernelGGL((k_emission_full<DB, MODE>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M,
+                       fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,
+                       POST ? ctx->post : (double *)nullptr, LOG ? fm->lk : (const double *)nullptr);
+}
+
+template <int DB>
+static void emission_full_by_mode(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode)
+{
+    switch (mode) {
+    case FC_POST: launch_emission_full<DB, FC_POST>(ctx, fm, c); break;
+    case FC_LOGPOST: launch_emission_full<DB, FC_LOGPOST>(ctx, fm, c); break;
+    case FC_LOG: launch_emission_full<DB, FC_LOG>(ctx, fm, c); break;
+    default: launch_emission_full<DB, FC_LIN>(ctx, fm, c); break;
+    }
+}
+
+// mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b), FC_LOGPOST (log b and
+// the mixture posteriors)
+static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN)
+{
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
+    if (c->F == 0) return GHMM_OK;
+    kscope ks(ctx, GHMM_K_EMISSION);
+    switch ((fm->D + 7) / 8 * 8) {
+    case 8: emission_full_by_mode<8>(ctx, fm, c, mode); break;
+    case 16: emission_full_by_mode<16>(ctx, fm, c, mode); break;
+    case 24: emission_full_by_mode<24>(ctx, fm, c, mode); break;
+    case 32: emission_full_by_mode<32>(ctx, fm, c, mode); break;
+    case 40: emission_full_by_mode<40>(ctx, fm, c, mode); break;
+    default: emission_full_by_mode<48>(ctx, fm, c, mode); break;
+    }
+    return launch_ok("k_emission_full");
+}
+
+extern "C" int ghmm_emission_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
+    return run_emission_full(ctx, fm, c);
+}
+
+extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    // calc_alpha + calc_probability without the final-state term: k_scan_pair's only = 3
+    const lane_grid lg(fm->N, c->U);
+    {
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_scan_pair<LL>, dim3(lg.blocks, 1u), dim3(WAVE), 0, ctx->stream, fm->N,
+                                               c->U, 3, fm->A, ctx->b, c->off, ctx->alpha, ctx->scale, ctx->sinv,
+                                               (const double *)nullptr, ctx->loglik, ctx->wrow, ctx->sb, ctx->sink,
+                                               c->order));
+    }
+    if ((rc = launch_ok("k_scan_pair"))) return rc;
+    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+// A vocabulary call up to its one launch: the checks (`what` = the entry point's name in their
+// texts), then, unless the corpus is empty (the caller returns), the concatenated vocabulary (NS
+// states, transitions unused; kept in the context between calls) with every word's Gaussians gathered
+// into it by one launch, the table of the words' recursions (dtab[k].A = word k's A under FC_LIN, its
+// log A under FC_LOG) and the vocabulary's b or log b in the workspace.  The launch writes bt_ll.
+struct fvocab {
+    int NS = 0, Nmax = 0; // the vocabulary's states, the largest word's
+    const fwd_model *dtab = nullptr;
+};
+
+static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, const ghmm_corpus *c,
+                        const double *dest_host, int mode, const char *what, fvocab *v)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK_AS(what, models && n_models > 0 && c, "null argument");
+    ARG_CHECK_AS(what, dest_host || c->U == 0, "null destination");
+    for (int k = 0; k < n_models; k++) ARG_CHECK_AS(what, models[k], "null model");
+    if ((rc = vocab_shape(models, n_models, what, &v->NS, &v->Nmax)) || (rc = check_full(ctx, models[0], c)))
+        return rc;
+    if (c->U == 0) return GHMM_OK;
+    const int M = models[0]->M, D = models[0]->D;
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    if (ctx->fbt_cat && (ctx->fbt_cat->N != v->NS || ctx->fbt_cat->M != M || ctx->fbt_cat->D != D)) {
+        ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
+        ctx->fbt_cat = nullptr;
+    }
+    if (!ctx->fbt_cat && (rc = fmodel_alloc(ctx, v->NS, M, D, &ctx->fbt_cat))) return rc;
+    ghmm_fmodel *cat = ctx->fbt_cat;
+    const fgather_src *dsrc;
+    const auto fill = [mode](const ghmm_fmodel *m, fwd_model &t, fgather_src &s) {
+        t.A = mode == FC_LOG ? m->logA : m->A;
+        s.c = m->c; s.mean = m->mean; s.inv_cov = m->inv_cov; s.den = m->den; s.lk = m->lk;
+    };
+    if ((rc = vocab_tables(ctx, models, n_models, &ctx->fbt_tab, &ctx->cap_fbt_tab, fill, &v->dtab, &dsrc)))
+        return rc;
+    hipLaunchKernelGGL(k_gather_fmodels, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
+                       cat->mean, cat->inv_cov, cat->den, cat->lk);
+    if ((rc = launch_ok("k_gather_fmodels"))) return rc;
+    if ((rc = ws_full(ctx, v->NS, M, c))) return rc;
+    return run_emission_full(ctx, cat, c, mode);
+}
+
+extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                     double *loglik_host)
+{
+    fvocab v;
+    int rc = fvocab_begin(ctx, models, n_models, c, loglik_host, FC_LIN, __func__, &v);
+    if (rc || c->U == 0) return rc;
+    {
+        const lane_grid lg(v.Nmax, c->U);
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                               0, ctx->stream, c->U, v.NS, c->F, v.dtab, ctx->b, c->off, ctx->sink,
+                                               ctx->sink, ctx->bt_ll, ctx->sink, c->order, 0));
+    }
+    if ((rc = launch_ok("k_forward_multi"))) return rc;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
+}
+
+// ------------------------------------------------ the full-covariance Viterbi
+
+extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *path_host,
+                                 double *score_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    if (c->U == 0) return GHMM_OK;
+    const lane_grid lg(fm->N, c->U);
+    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
+    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
+    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
+                                               c->U, fm->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
+                                               ctx->sink, c->order));
+    }
+    if ((rc = launch_ok("k_viterbi"))) return rc;
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                       double *score_host)
+{
+    fvocab v;
+    int rc = fvocab_begin(ctx, models, n_models, c, score_host, FC_LOG, __func__, &v);
+    if (rc || c->U == 0) return rc;
+    {
+        const lane_grid lg(v.Nmax, c->U);
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                               0, ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off, ctx->bt_ll,
+                                               ctx->sink, c->order));
+    }
+    if ((rc = launch_ok("k_viterbi_multi"))) return rc;
+    return vocab_scores_out(ctx, n_models, c, score_host);
+}
+
+// ------------------------------------------------ the full-covariance log-domain forward score
+
+// k_logforward_multi over the n_models entries of dtab on the log b in the workspace; scores to the host
+static int run_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
+                          const ghmm_corpus *c, int final_state, double *loglik_host)
+{
+    int rc;
+    {
+        const lane_grid lg(Nmax, c->U);
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(lg.blocks, (unsigned)n_models),
+                                               dim3(WAVE), 0, ctx->stream, c->U, NS, dtab, ctx->b, c->off,
+                                               ctx->bt_ll, ctx->sink, c->order, final_state));
+    }
+    if ((rc = launch_ok("k_logforward_multi"))) return rc;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
+}
+
+extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
+                                  double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if (c->U == 0) return GHMM_OK;
+    // the batch call's lattice launch on a table of one word
+    const fwd_model one = {fm->logA, fm->N, 0};
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
+    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
+    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
+}
+
+extern "C" int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
+                                        int final_state, double *loglik_host)
+{
+    fvocab v;
+    int rc = fvocab_begin(ctx, models, n_models, c, loglik_host, FC_LOG, __func__, &v);
+    if (rc || c->U == 0) return rc;
+    return run_logforward(ctx, v.dtab, n_models, v.NS, v.Nmax, c, final_state, loglik_host);
+}
+
+// ------------------------------------------------ the full-covariance trainer (TFF)
+
+static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)
+{
+    if (!s || !s->full || s->N != fm->N || s->M != fm->M || s->D != fm->D) {
+        ghmm_set_error("statistics vector is not a full-covariance one of the model's shape "
+                       "(ghmm_stats_create_full)");
+        return GHMM_ERR_ARG;
+    }
+    return GHMM_OK;
+}
+
+// calc_mix_param over every frame (k_fullstats, from ctx->gamma and ctx->post) into *P_out frame-block
+// partials in ctx->part_mu
+static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, long long *P_out)
+{
+    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, D1 = D + 1;
+    const long long E = (long long)G * fs_elems(D);
+    const int NB = (int)((E + FS_THREADS * FS_EPT - 1) / (FS_THREADS * FS_EPT));
+    int rc;
+    // frame-block partials: about four blocks per CU in all, as k_mixstats
+    long long P = ctx->partials > 0 ? ctx->partials : (4LL * ctx->cus + NB - 1) / NB;
+    if (P < 1) P = 1;
+    int GWmax = (FS_THREADS * FS_EPT) / fs_elems(D) + 2;
+    if (GWmax > G) GWmax = G;
+    int FSn = FS_FRAMES;
+    while (FSn > 1 && (size_t)FSn * (D1 + GWmax) * sizeof(double) > 48 * 1024) FSn /= 2;
+    const size_t lds = (size_t)FSn * (D1 + GWmax) * sizeof(double);
+    long long fpb = (c->F + P - 1) / P;
+    fpb = ((fpb + FSn - 1) / FSn) * FSn;
+    if (fpb < FSn) fpb = FSn;
+    P = c->F > 0 ? (c->F + fpb - 1) / fpb : 0;
+    if (P > 0) {
+        if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, (size_t)P * (size_t)E))) return rc;
+        kscope ks(ctx, GHMM_K_MIXSTATS);
+        hipLaunchKernelGGL(k_fullstats, dim3((unsigned)P, (unsigned)NB), dim3(FS_THREADS), lds, ctx->stream, N, M, D,
+                           c->F, fpb, FSn, c->X, ctx->gamma, ctx->post, fm->mean, ctx->part_mu);
+        if ((rc = launch_ok("k_fullstats"))) return rc;
+    }
+    *P_out = P;
+    return GHMM_OK;
+}
+
+// the ordered reduction of those partials into num_c / num_mu / num_cov at stats_c
+static int run_fullstats_reduce(ghmm_ctx *ctx, const ghmm_fmodel *fm, long long P, double *stats_c)
+{
+    const int G = fm->N * fm->M;
+    const long long E = (long long)G * fs_elems(fm->D);
+    hipLaunchKernelGGL(k_fullstats_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, G, fm->D,
+                       (int)P, (const double *)ctx->part_mu, stats_c);
+    return launch_ok("k_fullstats_reduce");
+}
+
+// the statistics of an E-step: both of the above, and the utterance sums (num_a, den_a, den_c, log P,
+// count) by k_reduce_all without its Gaussian blocks
+static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    const int N = fm->N, M = fm->M, D = fm->D;
+    int rc;
+    long long P = 0;
+    if ((rc = run_fullstats_part(ctx, fm, c, &P))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_REDUCE);
+        if ((rc = run_fullstats_reduce(ctx, fm, P, s->v + (size_t)N * N + 2 * (size_t)N))) return rc;
+        reduce_args ra{};
+        ra.N = N; ra.M = M; ra.D = D; ra.U = c->U; ra.delta = (int)ctx->delta;
+        ra.S = ctx->slots;
+        ra.lpart = ctx->loglik_pieces ? ctx->lpart : nullptr;
+        ra.logk = ctx->logk;
+        ra.part_xi = ctx->part_xi; ra.part_dena = ctx->part_dena; ra.part_denc = ctx->part_denc;
+        ra.loglik = ctx->loglik; ra.stats = s->v;
+        ra.no_mix = 1;
+        ra.tail = s->v + (s->n - 2);
+        ra.mbox = (s->mbox_slot >= 0 && ctx->mbox_page_dev) ? ctx->mbox_page_dev + 4 * s->mbox_slot : nullptr;
+        ra.mbox_seq = ++ctx->mbox_seq;
+        s->mbox_expect = ra.mbox_seq;
+        s->mbox_mark = ctx->launch_mark;
+        s->mbox_valid = ra.mbox != nullptr;
+        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)(N * N + 2 * N + 1)), dim3(RD_THREADS), 0, ctx->stream, ra);
+    }
+    return launch_ok("k_reduce_all");
+}
+
+extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
+    ghmm_model *rm = &fm->rec;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, rm, c))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_POST))) return rc;
+    // calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
+    // diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this
+    // model's A and the densities above
+    bool fused = false;
+    if ((rc = run_scan_combine(ctx, rm, c, &fused))) return rc;
+    if (!fused) {
+        if ((rc = run_forward(ctx, rm, c, true))) return rc;
+        if ((rc = run_backward(ctx, rm, c, false))) return rc;
+    }
+    return run_fullstats(ctx, fm, c, s);
+}
+
+// The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
+// and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
+// (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
+extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
+    if (c->U) {
+        const lane_grid lg(fm->N, c->U);
+        kscope ks(ctx, GHMM_K_FORWARD);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_fwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
+                                               c->U, fm->logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk,
+                                               ctx->sink, c->order));
+        if ((rc = launch_ok("k_logfb_fwd"))) return rc;
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_bwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
+                                               c->U, (int)ctx->delta, fm->logA, ctx->b, c->off, ctx->alpha, ctx->logk,
+                                               ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena, ctx->part_denc,
+                                               ctx->sink, c->order));
+        if ((rc = launch_ok("k_logfb_bwd"))) return rc;
+        ctx->beta_valid = true; // ctx->beta holds lbe: ghmm_fetch starts no linear pass on these buffers
+    }
+    ctx->slots = c->U; // one partial per utterance
+    ctx->loglik_pieces = false;
+    return run_fullstats(ctx, fm, c, s);
+}
+
+extern "C" int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    if ((rc = check_stats_full(fm, s))) return rc;
+    std::vector<double> v(s->n);
+    if ((rc = ghmm_stats_download(ctx, s, v.data()))) return rc;
+    ghmm_host_fmodel h;
+    memset(&h, 0, sizeof h);
+    if ((rc = ghmm_host_fmodel_alloc(&h, fm->N, fm->M, fm->D))) return rc;
+    if (!(rc = ghmm_fmodel_get(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det)) &&
+        !(rc = ghmm_mstep_full_host(v.data(), (int)ctx->delta, &h)))
+        rc = ghmm_fmodel_set(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det);
+    ghmm_host_fmodel_free(&h);
+    return rc;
+}
+
+// The M-step's two launches on full-layout statistics in HBM: k_fmstep_gauss and k_fmstep_state, or
+// (INIT) the initial model's k_finit_gauss and k_finit_state
+template <bool INIT>
+static int run_fmstep(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *stats, int delta)
+{
+    constexpr auto k_gauss = INIT ? k_finit_gauss : k_fmstep_gauss;
+    constexpr auto k_state = INIT ? k_finit_state : k_fmstep_state;
+    const int N = fm->N, M = fm->M, D = fm->D;
+    int rc;
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_gauss, dim3((unsigned)(N * M)), dim3(FM_THREADS), fm_gauss_lds_bytes(D), ctx->stream, N,
+                           M, D, stats, fm->mean, fm->inv_cov, fm->det);
+    }
+    if ((rc = launch_ok(INIT ? "k_finit_gauss" : "k_fmstep_gauss"))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_state, dim3((unsigned)N), dim3(FM_THREADS), 0, ctx->stream, N, M, D, stats,
+                           pow(2.0 * M_PI, D / 2.0), delta, fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den,
+                           fm->lk, fm->logA);
+    }
+    return launch_ok(INIT ? "k_finit_state" : "k_fmstep_state");
+}
+
+// The same M-step by k_fmstep_gauss and k_fmstep_state (ghmm_fullcov.hpp), where the statistics lie:
+// nothing is downloaded and the stream is not synchronised.
+extern "C" int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    if ((rc = check_stats_full(fm, s))) return rc;
+    if (fm->M > FM_MAXM) {
+        ghmm_set_error("the device M-step takes up to %d Gaussians per state (asked: %d); ghmm_mstep_full "
+                       "has no such cap", FM_MAXM, fm->M);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    if (ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
+    // transitions are re-estimated inside the band i <= j <= i + delta only: a band-diagonal A stays
+    // band-diagonal exactly when that band is i, i + 1.  The new A is not seen here, so a model set
+    // with a wider A stays on the general recursions even if its new A happens to be band-diagonal.
+    fm->rec.banded = fm->rec.banded && ctx->delta <= 1;
+    return run_fmstep<false>(ctx, fm, s->v, (int)ctx->delta);
+}
+
+// ------------------------------------------------ the full-covariance trainer's initial model
+// creating_initial_model (TFF:731-1134) from a corpus in HBM: the kernels of ghmm_fullcov.hpp
+// (k_finit_*), enqueued back to back on the context's stream; nothing is downloaded and the stream is
+// not synchronised.  ctx->finit holds, in this order, the passes' block partials [P][N][M][D + 2], one
+// slice [N][M][D + 2] of their sums (a communicator's all-reduce runs on it), and the last pass's
+// statistics in the full layout.
+extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_comm *cm)
+{
+    int rc = use(ctx);
+    if (rc) return rc;
+    ARG_CHECK(fm, "null model");
+    ARG_CHECK(c, "null corpus");
+    if ((rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(c->U > 0 && c->F > 0, "empty corpus");
+    if (fm->M > FI_MAXM) {
+        ghmm_set_error("the device initial model takes up to %d Gaussians per state (asked: %d); "
+                       "ghmm_init_model_full has no such cap", FI_MAXM, fm->M);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    const rccl_api *api = nullptr;
+    if (cm) {
+        ARG_CHECK(cm->comm, "null communicator");
+        ARG_CHECK(cm->device == ctx->device, "communicator and context are on different devices");
+        if (!(api = rccl_or_error())) return GHMM_ERR_UNSUPPORTED;
+    }
+    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, E2 = D + 2;
+    const size_t slice = (size_t)G * E2, nfull = ghmm_stats_len_full(N, M, D);
+    // about four blocks per CU in all, as run_fullstats sizes its grid: utterance ranges per state
+    int P = (4 * ctx->cus + N - 1) / N;
+    if (P > c->U) P = c->U;
+    const int upb = (c->U + P - 1) / P;
+    P = (c->U + upb - 1) / upb;
+    if ((rc = dev_grow(&ctx->finit, &ctx->cap_finit, (size_t)(P + 1) * slice + nfull))) return rc;
+    if ((rc = dev_grow(&ctx->gamma, &ctx->cap_gamma, (size_t)c->F * N))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * G))) return rc;
+    double *part = ctx->finit, *sums = part + (size_t)P * slice, *full = sums + slice;
+    double *full_c = full + (size_t)N * N + 2 * (size_t)N;
+    const size_t pass_lds = fi_pass_lds_bytes(M, D);
+    if (pass_lds > 48 * 1024 && (rc = lds_attr(ctx, (const void *)k_finit_pass))) return rc;
+    // the workspace is rewritten (gamma and post hold the last classification's one-hot rows), and the
+    // model's parameters change: nothing an earlier pass left behind goes with either any more
+    ws_disown(ctx);
+    ctx->F = c->F;
+    ctx->U = c->U;
+    ctx->N = N;
+    ctx->G = G;
+    fm->rec.banded = true; // init_transition_probab's A: j = i or i + 1
+
+    // one classification of every frame against n_cells cells per state, the cells' sums into part;
+    // gamma / post: where the one-hot rows go (the last pass's)
+    auto finit_pass = [&](int n_cells, int classify, double *gamma, double *post) -> int {
+        {
+            kscope ks(ctx, GHMM_K_PREPARE);
+            hipLaunchKernelGGL(k_finit_pass, dim3((unsigned)N, (unsigned)P), dim3(FI_THREADS), pass_lds, ctx->stream,
+                               N, M, D, n_cells, classify, c->U, upb, c->X, c->off, fm->mean, part, gamma, post);
+        }
+        return launch_ok("k_finit_pass");
+    };
+    auto pass = [&](int n_cells, int do_split, bool first) -> int {
+        int r;
+        if ((r = finit_pass(n_cells, first ? 0 : 1, nullptr, nullptr))) return r;
+        const double *src = part;
+        int np = P;
+        if (cm) { // the sums of all shards: every rank then does the same bookkeeping on the same numbers
+            {
+                kscope ks(ctx, GHMM_K_REDUCE);
+                hipLaunchKernelGGL(k_finit_reduce, dim3((unsigned)((slice + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   (long long)slice, P, (const double *)part, sums);
+            }
+            if ((r = launch_ok("k_finit_reduce"))) return r;
+            RCCL_TRY(api, api->AllReduce(sums, sums, slice, ncclDouble, ncclSum, cm->comm, ctx->stream));
+            src = sums;
+            np = 1;
+        }
+        {
+            kscope ks(ctx, GHMM_K_REDUCE);
+            hipLaunchKernelGGL(k_finit_cells, dim3((unsigned)N), dim3(64), (size_t)n_cells * E2 * sizeof(double),
+                               ctx->stream, N, M, D, n_cells, do_split, first ? 1 : 0, np, src, 1.05, 0.95, 1.005,
+                               0.995, fm->mean);
+        }
+        return launch_ok("k_finit_cells");
+    };
+    // init_mix_mean (TFF:970-1134): the state's mean, then five passes per level
+    if ((rc = pass(1, 1 < M ? 1 : 0, true))) return rc;
+    int nc = 1;
+    while (nc < M) {
+        nc = (2 * nc < M) ? 2 * nc : M;
+        for (int it = 0; it < 5; it++)
+            if ((rc = pass(nc, (it == 4 && nc < M) ? 1 : 0, false))) return rc;
+    }
+    // init_mix_param (TFF:810-952): one more classification, its one-hot rows into gamma and post;
+    // k_fullstats takes dif around the model's mean, which is the cell
+    long long PF = 0;
+    if ((rc = finit_pass(M, 1, ctx->gamma, ctx->post)) || (rc = run_fullstats_part(ctx, fm, c, &PF))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_REDUCE);
+        if ((rc = run_fullstats_reduce(ctx, fm, PF, full_c))) return rc;
+    }
+    if (cm)
+        RCCL_TRY(api, api->AllReduce(full_c, full_c, (size_t)G * fs_elems(D), ncclDouble, ncclSum, cm->comm,
+                                     ctx->stream));
+    return run_fmstep<true>(ctx, fm, full, 1);
+}

@@ -3,7 +3,8 @@
 // Host logic only: contexts, device buffers, launch geometry, HIP-event timing.
 // All arithmetic of the path happens in the kernels (ghmm_kernels.hpp,
 // ghmm_mfma.hpp, ghmm_pair.hpp).  No CPU fallback: without a gfx950 device every entry point that
-// needs one fails with GHMM_ERR_NODEVICE.
+// needs one fails with GHMM_ERR_NODEVICE.  The full-covariance entry points are in ghmm_fullhost.hpp,
+// included at the end of this file: one translation unit.
 #include "ghmm.h"
 
 #include <hip/hip_runtime.h>
@@ -37,13 +38,15 @@ using namespace ghmm;
         }                                                                                 \
     } while (0)
 
-#define ARG_CHECK(cond, msg)                                                              \
+// (what: the public entry point's name, for a check that lives in a helper of several of them)
+#define ARG_CHECK_AS(what, cond, msg)                                                     \
     do {                                                                                  \
         if (!(cond)) {                                                                    \
-            ghmm_set_error("%s: %s", __func__, msg);                                      \
+            ghmm_set_error("%s: %s", what, msg);                                          \
             return GHMM_ERR_ARG;                                                          \
         }                                                                                 \
     } while (0)
+#define ARG_CHECK(cond, msg) ARG_CHECK_AS(__func__, cond, msg)
 
 struct ktimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -1056,25 +1059,50 @@ static int grow_b(ghmm_ctx *ctx, size_t F, size_t N)
     return GHMM_OK;
 }
 
-static int ws_frames(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c, bool want_post)
+// b[F][N] (N = the model's states, or a vocabulary's) plus what the forward launch needs: all a
+// full-covariance call takes of the per-frame workspace
+static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
 {
     int rc;
-    size_t F = (size_t)c->F, N = (size_t)m->N, G = (size_t)m->N * m->M;
-    if ((rc = grow_b(ctx, F, N))) return rc;
-    if (want_post && (rc = dev_grow(&ctx->post, &ctx->cap_post, F * G))) return rc;
+    const size_t F = (size_t)c->F;
+    if ((rc = grow_b(ctx, F, (size_t)N))) return rc;
     if ((rc = dev_grow(&ctx->scale, &ctx->cap_scale, F))) return rc;
     if ((rc = dev_grow(&ctx->sinv, &ctx->cap_sinv, F))) return rc;
     if (!ctx->sink) {
         if ((rc = dev_grow(&ctx->sink, &ctx->cap_sink, (size_t)2 * WAVE * SINK_WAVES))) return rc;
         HIP_TRY(hipMemsetAsync(ctx->sink, 0, (size_t)2 * WAVE * SINK_WAVES * sizeof(double), ctx->stream));
     }
-    if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, F))) return rc;
     if ((rc = dev_grow(&ctx->loglik, &ctx->cap_loglik, (size_t)c->U))) return rc;
     ctx->F = c->F;
     ctx->U = c->U;
-    ctx->N = m->N;
-    ctx->G = (int)G;
+    ctx->N = N;
+    ctx->G = N * M;
     return GHMM_OK;
+}
+
+// the same for a diagonal model, with the robust tier's log normalisers and, on request, the posteriors
+static int ws_frames(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c, bool want_post)
+{
+    int rc;
+    const size_t F = (size_t)c->F;
+    if ((rc = ws_full(ctx, m->N, m->M, c))) return rc;
+    if (want_post && (rc = dev_grow(&ctx->post, &ctx->cap_post, F * m->N * m->M))) return rc;
+    return dev_grow(&ctx->lognorm, &ctx->cap_lognorm, F);
+}
+
+// The workspace is about to be rewritten by something no diagonal model owns: the row API refuses
+// it (need_emission), and alpha^ / W / beta^ / the pieces of log P of an earlier pass no longer go
+// with it.  The caller then sets what it does own (em_c, b_is_log).
+static void ws_disown(ghmm_ctx *ctx)
+{
+    ctx->last_m = nullptr;
+    ctx->last_c = nullptr;
+    ctx->em_m = nullptr;
+    ctx->em_c = nullptr;
+    ctx->em_epoch = -1;
+    ctx->own_bwd_done = false;
+    ctx->beta_valid = false;
+    ctx->loglik_pieces = false;
 }
 
 static int ws_fb(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c)
@@ -1254,11 +1282,17 @@ extern "C" int ghmm_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int w
         else { constexpr int LL = 64; __VA_ARGS__; }                                               \
     } while (0)
 
+// The kernels that hold one state per lane (N <= 64; of a vocabulary, its largest word): L lanes per
+// utterance, WAVE / L utterances per one-wave block, `blocks` of them for U utterances
+struct lane_grid {
+    int L;
+    unsigned blocks;
+    lane_grid(int N, int U) : L(N <= 16 ? 16 : N <= 32 ? 32 : 64), blocks((unsigned)((U + WAVE / L - 1) / (WAVE / L))) {}
+};
+
 static int fb_lanes(const ghmm_model *m, int *L)
 {   // L = 0: more states than lanes, the one-wave-per-utterance kernels of ghmm_wide.hpp
-    if (m->N <= 16) *L = 16;
-    else if (m->N <= 32) *L = 32;
-    else if (m->N <= 64) *L = 64;
+    if (m->N <= 64) *L = lane_grid(m->N, 0).L;
     else if (m->N <= WIDE_MAX) *L = 0;
     else {
         ghmm_set_error("%d states: the forward / backward / Viterbi kernels take models of up to %d",
@@ -2073,6 +2107,42 @@ extern "C" int ghmm_score(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, double *
     return GHMM_OK;
 }
 
+extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
+                            double *score_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_pair(m, c))) return rc;
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(m, &L))) return rc;
+    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
+    if ((rc = ws_frames(ctx, m, c, false))) return rc;
+    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
+    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = run_emission(ctx, m, c, 2, false))) return rc;
+    if (c->U) {
+        if (L == 0) { // one wave per utterance
+            if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
+            kscope ks(ctx, GHMM_K_VITERBI);
+            hipLaunchKernelGGL(k_viterbi_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)2 * m->N * sizeof(double),
+                               ctx->stream, m->N, c->U, m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
+                               c->order, ctx->wide_flag);
+        } else {
+            const unsigned blocks = lane_grid(m->N, c->U).blocks;
+            kscope ks(ctx, GHMM_K_VITERBI);
+            GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, m->N, c->U,
+                                                m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
+                                                ctx->sink, c->order));
+        }
+        if ((rc = launch_ok("k_viterbi"))) return rc;
+        HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost,
+                               ctx->stream));
+        if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    }
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
 // ------------------------------------------------------ several feature streams
 
 static int check_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P)
@@ -2179,6 +2249,65 @@ extern "C" int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
     return GHMM_OK;
 }
 
+// ------------------------------------------------ a vocabulary in one pass
+// What the batch calls share, diagonal (ghmm_score_batch) and full-covariance (ghmm_fullhost.hpp).
+
+// every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
+template <class MODEL>
+static int vocab_shape(MODEL *const *models, int n_models, const char *what, int *NS, int *Nmax)
+{
+    const int M = models[0]->M, D = models[0]->D;
+    *NS = *Nmax = 0;
+    for (int k = 0; k < n_models; k++) {
+        if (models[k]->M != M || models[k]->D != D) {
+            ghmm_set_error("%s: every model must have the same M and D", what);
+            return GHMM_ERR_UNSUPPORTED;
+        }
+        *NS += models[k]->N;
+        *Nmax = models[k]->N > *Nmax ? models[k]->N : *Nmax;
+    }
+    return GHMM_OK;
+}
+
+// The pass's two tables, built on the host and uploaded into one context buffer (*buf, grown on
+// demand): the words' recursions (N and the offset of the word's states in b; fill() adds A or log A)
+// and the gather kernel's sources (the word's Gaussians g0 .. g0 + ng of the concatenated model;
+// fill() adds the parameter pointers).
+template <class SRC, class MODEL, class FILL>
+static int vocab_tables(ghmm_ctx *ctx, MODEL *const *models, int n_models, char **buf, size_t *cap, FILL fill,
+                        const fwd_model **dtab, const SRC **dsrc)
+{
+    int rc;
+    std::vector<fwd_model> tab((size_t)n_models);
+    std::vector<SRC> src((size_t)n_models);
+    int go = 0, so = 0;
+    for (int k = 0; k < n_models; k++) {
+        const MODEL *m = models[k];
+        fill(m, tab[k], src[k]);
+        tab[k].N = m->N;
+        tab[k].bo = so;
+        src[k].g0 = go; src[k].ng = m->N * m->M;
+        go += m->N * m->M;
+        so += m->N;
+    }
+    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(SRC);
+    if ((rc = dev_grow(buf, cap, tab_bytes + src_bytes + 16))) return rc;
+    *dtab = (const fwd_model *)*buf;
+    *dsrc = (const SRC *)(*buf + ((tab_bytes + 15) / 16) * 16);
+    // (the tables leave pageable host vectors: the copies complete before the call returns them)
+    HIP_TRY(hipMemcpyAsync(*buf, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((void *)*dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return GHMM_OK;
+}
+
+// the pass's scores, bt_ll[n_models][U], to the host; waits for the stream
+static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, double *host)
+{
+    HIP_TRY(hipMemcpyAsync(host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
 extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                                 ghmm_corpus *c, double *loglik_host)
 {
@@ -2188,15 +2317,8 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
     ARG_CHECK(loglik_host || c->U == 0, "null destination");
     for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
     const int M = models[0]->M, D = models[0]->D;
-    int NS = 0, Nmax = 0;
-    for (int k = 0; k < n_models; k++) {
-        if (models[k]->M != M || models[k]->D != D) {
-            ghmm_set_error("ghmm_score_batch: every model must have the same M and D");
-            return GHMM_ERR_UNSUPPORTED;
-        }
-        NS += models[k]->N;
-        if (models[k]->N > Nmax) Nmax = models[k]->N;
-    }
+    int NS, Nmax;
+    if ((rc = vocab_shape(models, n_models, __func__, &NS, &Nmax))) return rc;
     if (D != c->D) {
         ghmm_set_error("models have %d coefficients per frame, corpus has %d", D, c->D);
         return GHMM_ERR_ARG;
@@ -2226,32 +2348,17 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
         HIP_TRY(hipMemsetAsync(ctx->bt_cat->A, 0, (size_t)NS * NS * 8, ctx->stream));
     }
     ghmm_model *cat = ctx->bt_cat;
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<gather_src> src((size_t)n_models);
-    {
-        int go = 0, so = 0;
-        for (int k = 0; k < n_models; k++) {
-            const ghmm_model *m = models[k];
-            tab[k].A = m->A;
-            tab[k].N = m->N;
-            tab[k].bo = so;
-            src[k].c = m->c; src[k].mean = m->mean; src[k].inv_var = m->inv_var; src[k].det = m->det;
-            src[k].g0 = go; src[k].ng = m->N * M;
-            go += m->N * M;
-            so += m->N;
-        }
-    }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(gather_src);
-    if ((rc = dev_grow(&ctx->bt_tab, &ctx->cap_bt_tab, tab_bytes + src_bytes + 16))) return rc;
-    fwd_model *dtab = (fwd_model *)ctx->bt_tab;
-    gather_src *dsrc = (gather_src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
     if ((rc = dev_grow(&ctx->bt_scale, &ctx->cap_bt_scale, (size_t)n_models * c->F + 1)) ||
         (rc = dev_grow(&ctx->bt_sinv, &ctx->cap_bt_sinv, (size_t)n_models * c->F + 1)) ||
         (rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U)))
         return rc;
-    // (the tables leave pageable host vectors: the copies complete before the call returns them)
-    HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const fwd_model *dtab;
+    const gather_src *dsrc;
+    const auto fill = [](const ghmm_model *m, fwd_model &t, gather_src &s) {
+        t.A = m->A;
+        s.c = m->c; s.mean = m->mean; s.inv_var = m->inv_var; s.det = m->det;
+    };
+    if ((rc = vocab_tables(ctx, models, n_models, &ctx->bt_tab, &ctx->cap_bt_tab, fill, &dtab, &dsrc))) return rc;
     hipLaunchKernelGGL(k_gather_models, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
                        cat->mean, cat->inv_var, cat->det);
     if ((rc = launch_ok("k_gather_models"))) return rc;
@@ -2261,702 +2368,14 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
         (rc = run_emission(ctx, cat, c, 0, false)))
         return rc;
     {
-        const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
+        const lane_grid lg(Nmax, c->U);
         kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                            ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->bt_scale,
-                                            ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                               0, ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->bt_scale,
+                                               ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
     }
-    if ((rc = launch_ok("k_forward_multi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(stream_sync(ctx));
+    if ((rc = launch_ok("k_forward_multi")) || (rc = vocab_scores_out(ctx, n_models, c, loglik_host))) return rc;
     ctx->b_is_log = true; // the workspace b belongs to the concatenated model: not reusable
-    return GHMM_OK;
-}
-
-// ------------------------------------------------ the full-covariance recogniser (RC)
-
-struct ghmm_fmodel {
-    int N = 0, M = 0, D = 0;
-    double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
-    double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
-    // ghmm_viterbi_full: log(c) - log(den) per Gaussian, and A > 0 ? log(A) : -inf, both formed on
-    // the host (the oracle's expressions, evaluated by the same libm)
-    double *lk = nullptr, *logA = nullptr;
-    // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
-    // run_scan_combine): N, and A (aliases the A above, owned there) with its band flag.  Nothing
-    // else of it is set; it is never passed to ghmm_model_destroy.
-    ghmm_model rec;
-};
-
-// any N (the concatenated vocabulary of ghmm_score_full_batch has hundreds of states)
-static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
-{
-    ghmm_fmodel *fm = new (std::nothrow) ghmm_fmodel();
-    if (!fm) return GHMM_ERR_ALLOC;
-    fm->N = N; fm->M = M; fm->D = D;
-    fm->rec.N = N; fm->rec.M = M; fm->rec.D = D;
-    const size_t G = (size_t)N * M;
-    // mean and inv_cov with FC_SLACK doubles behind them: the kernel's padded columns read there
-    const size_t nmean = G * D + FC_SLACK, ncov = G * D * D + FC_SLACK;
-    int rc;
-    if ((rc = dev_alloc(&fm->A, (size_t)N * N)) || (rc = dev_alloc(&fm->c, G)) ||
-        (rc = dev_alloc(&fm->mean, nmean)) || (rc = dev_alloc(&fm->inv_cov, ncov)) ||
-        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G)) || (rc = dev_alloc(&fm->lk, G)) ||
-        (rc = dev_alloc(&fm->logA, (size_t)N * N))) {
-        ghmm_fmodel_destroy(ctx, fm);
-        return rc;
-    }
-    fm->rec.A = fm->A;
-    if (hipMemsetAsync(fm->mean, 0, nmean * 8, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(fm->inv_cov, 0, ncov * 8, ctx->stream) != hipSuccess) {
-        ghmm_fmodel_destroy(ctx, fm);
-        ghmm_set_error("hipMemsetAsync failed");
-        return GHMM_ERR_HIP;
-    }
-    *out = fm;
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_fmodel_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(out, "null output");
-    *out = nullptr;
-    ARG_CHECK(N > 0 && M > 0 && D > 0, "N, M and D must be positive");
-    if (N > 64 || D > FC_DMAX) {
-        ghmm_set_error("full-covariance models take up to 64 states and %d coefficients (asked: %d states, "
-                       "%d coefficients)", FC_DMAX, N, D);
-        return GHMM_ERR_UNSUPPORTED;
-    }
-    return fmodel_alloc(ctx, N, M, D, out);
-}
-
-extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
-{
-    if (!fm) return;
-    if (ctx && ctx->last_m == &fm->rec) ctx->last_m = nullptr;
-    if (ctx) {
-        (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den, fm->lk, fm->logA};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    delete fm;
-}
-
-extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
-                               const double *mean, const double *inv_cov, const double *det)
-{
-    int rc = use(ctx);
-    if (ctx && fm && ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
-    if (rc) return rc;
-    ARG_CHECK(fm && A && c && mean && inv_cov && det, "null argument");
-    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
-    fm->rec.banded = true; // (as ghmm_model_set decides it: the paired scans' band-diagonal forms)
-    for (int i = 0; i < fm->N; i++)
-        for (int j = 0; j < fm->N; j++)
-            if (A[(size_t)i * fm->N + j] != 0.0 && j != i && j != i + 1) fm->rec.banded = false;
-    // calc_gaus's normaliser as the reference forms it: aux1 = pow(2 pi, D/2.0), aux2 = pow(|det|, 0.5)
-    std::vector<double> den(G), lk(G), logA(NN);
-    const double aux1 = pow(2.0 * M_PI, fm->D / 2.0);
-    for (size_t g = 0; g < G; g++) {
-        den[g] = aux1 * pow(fabs(det[g]), 0.5);
-        lk[g] = log(c[g]) - log(den[g]);
-    }
-    for (size_t k = 0; k < NN; k++) logA[k] = A[k] > 0.0 ? log(A[k]) : -INFINITY;
-    HIP_TRY(hipMemcpyAsync(fm->A, A, NN * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->c, c, G * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->mean, mean, G * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->inv_cov, inv_cov, G * fm->D * fm->D * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->det, det, G * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->den, den.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->lk, lk.data(), G * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fm->logA, logA.data(), NN * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(stream_sync(ctx)); // (pageable sources)
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_fmodel_get(ghmm_ctx *ctx, ghmm_fmodel *fm, double *A, double *c, double *mean,
-                               double *inv_cov, double *det)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(fm, "null model");
-    const size_t G = (size_t)fm->N * fm->M, NN = (size_t)fm->N * fm->N;
-    if (A) HIP_TRY(hipMemcpyAsync(A, fm->A, NN * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (c) HIP_TRY(hipMemcpyAsync(c, fm->c, G * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mean) HIP_TRY(hipMemcpyAsync(mean, fm->mean, G * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (inv_cov)
-        HIP_TRY(hipMemcpyAsync(inv_cov, fm->inv_cov, G * fm->D * fm->D * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (det) HIP_TRY(hipMemcpyAsync(det, fm->det, G * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_fmodel_dims(const ghmm_fmodel *fm, int *N, int *M, int *D)
-{
-    ARG_CHECK(fm, "null model");
-    if (N) *N = fm->N;
-    if (M) *M = fm->M;
-    if (D) *D = fm->D;
-    return GHMM_OK;
-}
-
-static int check_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
-{
-    if (!fm || !c) {
-        ghmm_set_error("null model or corpus");
-        return GHMM_ERR_ARG;
-    }
-    if (fm->D != c->D) {
-        ghmm_set_error("model has %d coefficients per frame, corpus has %d", fm->D, c->D);
-        return GHMM_ERR_ARG;
-    }
-    if (ctx->robust) {
-        ghmm_set_error("GHMM_OPT_ROBUST is not available with full-covariance models");
-        return GHMM_ERR_UNSUPPORTED;
-    }
-    return GHMM_OK;
-}
-
-// b[F][N] (N = the model's states, or the vocabulary's) plus what the forward launch needs
-static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
-{
-    int rc;
-    const size_t F = (size_t)c->F;
-    if ((rc = grow_b(ctx, F, (size_t)N))) return rc;
-    if ((rc = dev_grow(&ctx->scale, &ctx->cap_scale, F))) return rc;
-    if ((rc = dev_grow(&ctx->sinv, &ctx->cap_sinv, F))) return rc;
-    if (!ctx->sink) {
-        if ((rc = dev_grow(&ctx->sink, &ctx->cap_sink, (size_t)2 * WAVE * SINK_WAVES))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->sink, 0, (size_t)2 * WAVE * SINK_WAVES * sizeof(double), ctx->stream));
-    }
-    if ((rc = dev_grow(&ctx->loglik, &ctx->cap_loglik, (size_t)c->U))) return rc;
-    ctx->F = c->F;
-    ctx->U = c->U;
-    ctx->N = N;
-    ctx->G = N * M;
-    return GHMM_OK;
-}
-
-// mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b), FC_LOGPOST (log b and
-// the mixture posteriors)
-static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN)
-{
-    // the workspace now holds densities no diagonal model owns: the row API refuses them
-    // (need_emission), and alpha^ / W / log P of an earlier pass no longer go with b
-    ctx->last_m = nullptr;
-    ctx->last_c = nullptr;
-    ctx->em_m = nullptr;
-    ctx->em_c = c;
-    ctx->em_epoch = -1;
-    ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
-    ctx->own_bwd_done = false;
-    ctx->beta_valid = false;
-    ctx->loglik_pieces = false;
-    if (c->F == 0) return GHMM_OK;
-    const int nch = (fm->N + FC_SC - 1) / FC_SC;
-    const dim3 grid((unsigned)((c->F + WAVE - 1) / WAVE), (unsigned)((nch + FC_WAVES - 1) / FC_WAVES));
-    const size_t lds = (size_t)fc_lds_doubles(fm->D) * sizeof(double);
-    const int DB = (fm->D + 7) / 8 * 8;
-    kscope ks(ctx, GHMM_K_EMISSION);
-#define GHMM_FCK(DBV)                                                                                         \
-    do {                                                                                                      \
-        if (mode == FC_POST)                                                                                  \
-            hipLaunchKernelGGL((k_emission_full<DBV, FC_POST>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,     \
-                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
-                               ctx->post, (const double *)nullptr);                                           \
-        else if (mode == FC_LOGPOST)                                                                          \
-            hipLaunchKernelGGL((k_emission_full<DBV, FC_LOGPOST>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,  \
-                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
-                               ctx->post, fm->lk);                                                            \
-        else if (mode == FC_LOG)                                                                              \
-            hipLaunchKernelGGL((k_emission_full<DBV, FC_LOG>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream,      \
-                               fm->N, fm->M, fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,    \
-                               (double *)nullptr, fm->lk);                                                    \
-        else                                                                                                  \
-            hipLaunchKernelGGL(k_emission_full<DBV>, grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M, \
-                               fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b, (double *)nullptr, \
-                               (const double *)nullptr);                                                      \
-    } while (0)
-    switch (DB) {
-    case 8: GHMM_FCK(8); break;
-    case 16: GHMM_FCK(16); break;
-    case 24: GHMM_FCK(24); break;
-    case 32: GHMM_FCK(32); break;
-    case 40: GHMM_FCK(40); break;
-    default: GHMM_FCK(48); break;
-    }
-#undef GHMM_FCK
-    return launch_ok("k_emission_full");
-}
-
-extern "C" int ghmm_emission_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c))) return rc;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
-    return run_emission_full(ctx, fm, c);
-}
-
-extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c))) return rc;
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    // calc_alpha + calc_probability without the final-state term: k_scan_pair's only = 3
-    const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
-    const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-    {
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_scan_pair<LL>, dim3(blocks, 1u), dim3(WAVE), 0, ctx->stream, fm->N, c->U, 3,
-                                            fm->A, ctx->b, c->off, ctx->alpha, ctx->scale, ctx->sinv,
-                                            (const double *)nullptr, ctx->loglik, ctx->wrow, ctx->sb, ctx->sink,
-                                            c->order));
-    }
-    if ((rc = launch_ok("k_scan_pair"))) return rc;
-    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-// the checks of the full batch calls past their null arguments: every model shares M and D, the
-// corpus has that D; NS = the vocabulary's states, Nmax = the largest model's
-static int fvocab_check(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, const ghmm_corpus *c,
-                        const char *what, int *NS, int *Nmax)
-{
-    const int M = models[0]->M, D = models[0]->D;
-    *NS = *Nmax = 0;
-    for (int k = 0; k < n_models; k++) {
-        if (models[k]->M != M || models[k]->D != D) {
-            ghmm_set_error("%s: every model must have the same M and D", what);
-            return GHMM_ERR_UNSUPPORTED;
-        }
-        *NS += models[k]->N;
-        *Nmax = models[k]->N > *Nmax ? models[k]->N : *Nmax;
-    }
-    return check_full(ctx, models[0], c);
-}
-
-// The concatenated vocabulary (NS states, transitions unused), kept in the context between calls:
-// every word's Gaussians gathered into it by one launch, and the table of the words' recursions
-// (tab[k].A = word k's A, or its log A for the Viterbi lattice).
-static int fvocab_gather(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, int NS, bool log_a,
-                         ghmm_fmodel **cat_out, const fwd_model **tab_out)
-{
-    int rc;
-    const int M = models[0]->M, D = models[0]->D;
-    if (ctx->fbt_cat && (ctx->fbt_cat->N != NS || ctx->fbt_cat->M != M || ctx->fbt_cat->D != D)) {
-        ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
-        ctx->fbt_cat = nullptr;
-    }
-    if (!ctx->fbt_cat && (rc = fmodel_alloc(ctx, NS, M, D, &ctx->fbt_cat))) return rc;
-    ghmm_fmodel *cat = ctx->fbt_cat;
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<fgather_src> src((size_t)n_models);
-    {
-        int go = 0, so = 0;
-        for (int k = 0; k < n_models; k++) {
-            const ghmm_fmodel *m = models[k];
-            tab[k].A = log_a ? m->logA : m->A;
-            tab[k].N = m->N;
-            tab[k].bo = so;
-            src[k].c = m->c; src[k].mean = m->mean; src[k].inv_cov = m->inv_cov; src[k].den = m->den;
-            src[k].lk = m->lk;
-            src[k].g0 = go; src[k].ng = m->N * M;
-            go += m->N * M;
-            so += m->N;
-        }
-    }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(fgather_src);
-    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, tab_bytes + src_bytes + 16))) return rc;
-    fwd_model *dtab = (fwd_model *)ctx->fbt_tab;
-    fgather_src *dsrc = (fgather_src *)(ctx->fbt_tab + ((tab_bytes + 15) / 16) * 16);
-    HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_fmodels, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
-                       cat->mean, cat->inv_cov, cat->den, cat->lk);
-    if ((rc = launch_ok("k_gather_fmodels"))) return rc;
-    *cat_out = cat;
-    *tab_out = dtab;
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
-                                     double *loglik_host)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(models && n_models > 0 && c, "null argument");
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
-    int NS, Nmax;
-    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_score_full_batch", &NS, &Nmax))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    ghmm_fmodel *cat;
-    const fwd_model *dtab;
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
-    if ((rc = fvocab_gather(ctx, models, n_models, NS, false, &cat, &dtab))) return rc;
-    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c))) return rc;
-    {
-        const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                            ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->sink,
-                                            ctx->sink, ctx->bt_ll, ctx->sink, c->order, 0));
-    }
-    if ((rc = launch_ok("k_forward_multi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-// ------------------------------------------------ the full-covariance Viterbi
-
-extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *path_host,
-                                 double *score_host)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c))) return rc;
-    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
-    if (c->U == 0) return GHMM_OK;
-    const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * L + 16))) return rc; // rows of L bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
-    if ((rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
-    {
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-        kscope ks(ctx, GHMM_K_VITERBI);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
-                                            fm->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik, ctx->sink,
-                                            c->order));
-    }
-    if ((rc = launch_ok("k_viterbi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
-                                       double *score_host)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(models && n_models > 0 && c, "null argument");
-    ARG_CHECK(score_host || c->U == 0, "null destination");
-    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
-    int NS, Nmax;
-    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_viterbi_full_batch", &NS, &Nmax))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    ghmm_fmodel *cat;
-    const fwd_model *dtab;
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
-    if ((rc = fvocab_gather(ctx, models, n_models, NS, true, &cat, &dtab))) return rc;
-    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c, FC_LOG))) return rc;
-    {
-        const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-        kscope ks(ctx, GHMM_K_VITERBI);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                            ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
-                                            c->order));
-    }
-    if ((rc = launch_ok("k_viterbi_multi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-// ------------------------------------------------ the full-covariance log-domain forward score
-
-// k_logforward_multi over the n_models entries of dtab on the log b in the workspace; scores to the host
-static int run_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
-                          const ghmm_corpus *c, int final_state, double *loglik_host)
-{
-    int rc;
-    const int L = Nmax <= 16 ? 16 : Nmax <= 32 ? 32 : 64, gpw = WAVE / L;
-    const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-    {
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                            ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
-                                            c->order, final_state));
-    }
-    if ((rc = launch_ok("k_logforward_multi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
-
-extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
-                                  double *loglik_host)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c))) return rc;
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    if (c->U == 0) return GHMM_OK;
-    // the batch call's lattice launch on a table of one word
-    const fwd_model one = {fm->logA, fm->N, 0};
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
-    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
-    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
-}
-
-extern "C" int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
-                                        int final_state, double *loglik_host)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(models && n_models > 0 && c, "null argument");
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
-    int NS, Nmax;
-    if ((rc = fvocab_check(ctx, models, n_models, c, "ghmm_logscore_full_batch", &NS, &Nmax))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    ghmm_fmodel *cat;
-    const fwd_model *dtab;
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
-    if ((rc = fvocab_gather(ctx, models, n_models, NS, true, &cat, &dtab))) return rc;
-    if ((rc = ws_full(ctx, NS, cat->M, c)) || (rc = run_emission_full(ctx, cat, c, FC_LOG))) return rc;
-    return run_logforward(ctx, dtab, n_models, NS, Nmax, c, final_state, loglik_host);
-}
-
-// ------------------------------------------------ the full-covariance trainer (TFF)
-
-static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)
-{
-    if (!s || !s->full || s->N != fm->N || s->M != fm->M || s->D != fm->D) {
-        ghmm_set_error("statistics vector is not a full-covariance one of the model's shape "
-                       "(ghmm_stats_create_full)");
-        return GHMM_ERR_ARG;
-    }
-    return GHMM_OK;
-}
-
-// calc_mix_param over every frame (k_fullstats, from ctx->gamma and ctx->post) into *P_out frame-block
-// partials in ctx->part_mu
-static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, long long *P_out)
-{
-    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, D1 = D + 1;
-    const long long E = (long long)G * fs_elems(D);
-    const int NB = (int)((E + FS_THREADS * FS_EPT - 1) / (FS_THREADS * FS_EPT));
-    int rc;
-    // frame-block partials: about four blocks per CU in all, as k_mixstats
-    long long P = ctx->partials > 0 ? ctx->partials : (4LL * ctx->cus + NB - 1) / NB;
-    if (P < 1) P = 1;
-    int GWmax = (FS_THREADS * FS_EPT) / fs_elems(D) + 2;
-    if (GWmax > G) GWmax = G;
-    int FSn = FS_FRAMES;
-    while (FSn > 1 && (size_t)FSn * (D1 + GWmax) * sizeof(double) > 48 * 1024) FSn /= 2;
-    const size_t lds = (size_t)FSn * (D1 + GWmax) * sizeof(double);
-    long long fpb = (c->F + P - 1) / P;
-    fpb = ((fpb + FSn - 1) / FSn) * FSn;
-    if (fpb < FSn) fpb = FSn;
-    P = c->F > 0 ? (c->F + fpb - 1) / fpb : 0;
-    if (P > 0) {
-        if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, (size_t)P * (size_t)E))) return rc;
-        kscope ks(ctx, GHMM_K_MIXSTATS);
-        hipLaunchKernelGGL(k_fullstats, dim3((unsigned)P, (unsigned)NB), dim3(FS_THREADS), lds, ctx->stream, N, M, D,
-                           c->F, fpb, FSn, c->X, ctx->gamma, ctx->post, fm->mean, ctx->part_mu);
-        if ((rc = launch_ok("k_fullstats"))) return rc;
-    }
-    *P_out = P;
-    return GHMM_OK;
-}
-
-// the ordered reduction of those partials into num_c / num_mu / num_cov at stats_c
-static int run_fullstats_reduce(ghmm_ctx *ctx, const ghmm_fmodel *fm, long long P, double *stats_c)
-{
-    const int G = fm->N * fm->M;
-    const long long E = (long long)G * fs_elems(fm->D);
-    hipLaunchKernelGGL(k_fullstats_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, G, fm->D,
-                       (int)P, (const double *)ctx->part_mu, stats_c);
-    return launch_ok("k_fullstats_reduce");
-}
-
-// the statistics of an E-step: both of the above, and the utterance sums (num_a, den_a, den_c, log P,
-// count) by k_reduce_all without its Gaussian blocks
-static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
-{
-    const int N = fm->N, M = fm->M, D = fm->D;
-    int rc;
-    long long P = 0;
-    if ((rc = run_fullstats_part(ctx, fm, c, &P))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_REDUCE);
-        if ((rc = run_fullstats_reduce(ctx, fm, P, s->v + (size_t)N * N + 2 * (size_t)N))) return rc;
-        reduce_args ra{};
-        ra.N = N; ra.M = M; ra.D = D; ra.U = c->U; ra.delta = (int)ctx->delta;
-        ra.S = ctx->slots;
-        ra.lpart = ctx->loglik_pieces ? ctx->lpart : nullptr;
-        ra.logk = ctx->logk;
-        ra.part_xi = ctx->part_xi; ra.part_dena = ctx->part_dena; ra.part_denc = ctx->part_denc;
-        ra.loglik = ctx->loglik; ra.stats = s->v;
-        ra.no_mix = 1;
-        ra.tail = s->v + (s->n - 2);
-        ra.mbox = (s->mbox_slot >= 0 && ctx->mbox_page_dev) ? ctx->mbox_page_dev + 4 * s->mbox_slot : nullptr;
-        ra.mbox_seq = ++ctx->mbox_seq;
-        s->mbox_expect = ra.mbox_seq;
-        s->mbox_mark = ctx->launch_mark;
-        s->mbox_valid = ra.mbox != nullptr;
-        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)(N * N + 2 * N + 1)), dim3(RD_THREADS), 0, ctx->stream, ra);
-    }
-    return launch_ok("k_reduce_all");
-}
-
-extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
-    ghmm_model *rm = &fm->rec;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, rm, c))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
-    if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
-    if ((rc = run_emission_full(ctx, fm, c, FC_POST))) return rc;
-    // calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
-    // diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this
-    // model's A and the densities above
-    bool fused = false;
-    if ((rc = run_scan_combine(ctx, rm, c, &fused))) return rc;
-    if (!fused) {
-        if ((rc = run_forward(ctx, rm, c, true))) return rc;
-        if ((rc = run_backward(ctx, rm, c, false))) return rc;
-    }
-    return run_fullstats(ctx, fm, c, s);
-}
-
-// The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
-// and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
-// (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
-extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
-    if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
-    if (c->U) {
-        const int L = fm->N <= 16 ? 16 : fm->N <= 32 ? 32 : 64, gpw = WAVE / L;
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logfb_fwd<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
-                                            fm->logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk, ctx->sink,
-                                            c->order));
-        if ((rc = launch_ok("k_logfb_fwd"))) return rc;
-        GHMM_BY_LANES(L, hipLaunchKernelGGL(k_logfb_bwd<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, fm->N, c->U,
-                                            (int)ctx->delta, fm->logA, ctx->b, c->off, ctx->alpha, ctx->logk,
-                                            ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena, ctx->part_denc,
-                                            ctx->sink, c->order));
-        if ((rc = launch_ok("k_logfb_bwd"))) return rc;
-        ctx->beta_valid = true; // ctx->beta holds lbe: ghmm_fetch starts no linear pass on these buffers
-    }
-    ctx->slots = c->U; // one partial per utterance
-    ctx->loglik_pieces = false;
-    return run_fullstats(ctx, fm, c, s);
-}
-
-extern "C" int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(fm, "null model");
-    if ((rc = check_stats_full(fm, s))) return rc;
-    std::vector<double> v(s->n);
-    if ((rc = ghmm_stats_download(ctx, s, v.data()))) return rc;
-    ghmm_host_fmodel h;
-    memset(&h, 0, sizeof h);
-    if ((rc = ghmm_host_fmodel_alloc(&h, fm->N, fm->M, fm->D))) return rc;
-    if (!(rc = ghmm_fmodel_get(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det)) &&
-        !(rc = ghmm_mstep_full_host(v.data(), (int)ctx->delta, &h)))
-        rc = ghmm_fmodel_set(ctx, fm, h.A, h.c, h.mean, h.inv_cov, h.det);
-    ghmm_host_fmodel_free(&h);
-    return rc;
-}
-
-// The same M-step by k_fmstep_gauss and k_fmstep_state (ghmm_fullcov.hpp), where the statistics lie:
-// nothing is downloaded and the stream is not synchronised.
-extern "C" int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(fm, "null model");
-    if ((rc = check_stats_full(fm, s))) return rc;
-    if (fm->M > FM_MAXM) {
-        ghmm_set_error("the device M-step takes up to %d Gaussians per state (asked: %d); ghmm_mstep_full "
-                       "has no such cap", FM_MAXM, fm->M);
-        return GHMM_ERR_UNSUPPORTED;
-    }
-    if (ctx->last_m == &fm->rec) ctx->last_m = nullptr; // alpha^ / W belong to the old parameters
-    // transitions are re-estimated inside the band i <= j <= i + delta only: a band-diagonal A stays
-    // band-diagonal exactly when that band is i, i + 1.  The new A is not seen here, so a model set
-    // with a wider A stays on the general recursions even if its new A happens to be band-diagonal.
-    fm->rec.banded = fm->rec.banded && ctx->delta <= 1;
-    const int N = fm->N, M = fm->M, D = fm->D;
-    const size_t lds = fm_gauss_lds_bytes(D);
-    {
-        kscope ks(ctx, GHMM_K_MSTEP);
-        hipLaunchKernelGGL(k_fmstep_gauss, dim3((unsigned)(N * M)), dim3(FM_THREADS), lds, ctx->stream, N, M, D,
-                           s->v, fm->mean, fm->inv_cov, fm->det);
-    }
-    if ((rc = launch_ok("k_fmstep_gauss"))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_MSTEP);
-        hipLaunchKernelGGL(k_fmstep_state, dim3((unsigned)N), dim3(FM_THREADS), 0, ctx->stream, N, M, D, s->v,
-                           pow(2.0 * M_PI, D / 2.0), (int)ctx->delta, fm->A, fm->c, fm->mean, fm->inv_cov,
-                           fm->det, fm->den, fm->lk, fm->logA);
-    }
-    return launch_ok("k_fmstep_state");
-}
-
-extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
-                            double *score_host)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_pair(m, c))) return rc;
-    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
-    int L;
-    if ((rc = fb_lanes(m, &L))) return rc;
-    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
-    if ((rc = ws_frames(ctx, m, c, false))) return rc;
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
-    if ((rc = run_emission(ctx, m, c, 2, false))) return rc;
-    if (c->U) {
-        const int gpw = L ? WAVE / L : 1;
-        const unsigned blocks = (unsigned)((c->U + gpw - 1) / gpw);
-        if (L == 0) {
-            if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
-            kscope ks(ctx, GHMM_K_VITERBI);
-            hipLaunchKernelGGL(k_viterbi_wide, dim3(blocks), dim3(WAVE), (size_t)2 * m->N * sizeof(double),
-                               ctx->stream, m->N, c->U, m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
-                               c->order, ctx->wide_flag);
-        } else {
-            kscope ks(ctx, GHMM_K_VITERBI);
-            GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, m->N, c->U,
-                                                m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
-                                                ctx->sink, c->order));
-        }
-        if ((rc = launch_ok("k_viterbi"))) return rc;
-        HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
-    }
-    HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
 
@@ -3112,126 +2531,5 @@ extern "C" int ghmm_stats_allreduce(ghmm_ctx *ctx, ghmm_stats *s, ghmm_comm *cm)
     return GHMM_OK;
 }
 
-// ------------------------------------------------ the full-covariance trainer's initial model
-// creating_initial_model (TFF:731-1134) from a corpus in HBM: the kernels of ghmm_fullcov.hpp
-// (k_finit_*), enqueued back to back on the context's stream; nothing is downloaded and the stream is
-// not synchronised.  ctx->finit holds, in this order, the passes' block partials [P][N][M][D + 2], one
-// slice [N][M][D + 2] of their sums (a communicator's all-reduce runs on it), and the last pass's
-// statistics in the full layout.
-extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_comm *cm)
-{
-    int rc = use(ctx);
-    if (rc) return rc;
-    ARG_CHECK(fm, "null model");
-    ARG_CHECK(c, "null corpus");
-    if ((rc = check_full(ctx, fm, c))) return rc;
-    ARG_CHECK(c->U > 0 && c->F > 0, "empty corpus");
-    if (fm->M > FI_MAXM) {
-        ghmm_set_error("the device initial model takes up to %d Gaussians per state (asked: %d); "
-                       "ghmm_init_model_full has no such cap", FI_MAXM, fm->M);
-        return GHMM_ERR_UNSUPPORTED;
-    }
-    const rccl_api *api = nullptr;
-    if (cm) {
-        ARG_CHECK(cm->comm, "null communicator");
-        ARG_CHECK(cm->device == ctx->device, "communicator and context are on different devices");
-        if (!(api = rccl_or_error())) return GHMM_ERR_UNSUPPORTED;
-    }
-    const int N = fm->N, M = fm->M, D = fm->D, G = N * M, E2 = D + 2;
-    const size_t slice = (size_t)G * E2, nfull = ghmm_stats_len_full(N, M, D);
-    // about four blocks per CU in all, as run_fullstats sizes its grid: utterance ranges per state
-    int P = (4 * ctx->cus + N - 1) / N;
-    if (P > c->U) P = c->U;
-    const int upb = (c->U + P - 1) / P;
-    P = (c->U + upb - 1) / upb;
-    if ((rc = dev_grow(&ctx->finit, &ctx->cap_finit, (size_t)(P + 1) * slice + nfull))) return rc;
-    if ((rc = dev_grow(&ctx->gamma, &ctx->cap_gamma, (size_t)c->F * N))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * G))) return rc;
-    double *part = ctx->finit, *sums = part + (size_t)P * slice, *full = sums + slice;
-    double *full_c = full + (size_t)N * N + 2 * (size_t)N;
-    const size_t pass_lds = fi_pass_lds_bytes(M, D);
-    if (pass_lds > 48 * 1024 && (rc = lds_attr(ctx, (const void *)k_finit_pass))) return rc;
-    // the workspace is rewritten (gamma and post hold the last classification's one-hot rows), and the
-    // model's parameters change: nothing an earlier pass left behind goes with either any more
-    ctx->last_m = nullptr;
-    ctx->last_c = nullptr;
-    ctx->em_m = nullptr;
-    ctx->em_c = nullptr;
-    ctx->em_epoch = -1;
-    ctx->own_bwd_done = false;
-    ctx->beta_valid = false;
-    ctx->loglik_pieces = false;
-    ctx->F = c->F;
-    ctx->U = c->U;
-    ctx->N = N;
-    ctx->G = G;
-    fm->rec.banded = true; // init_transition_probab's A: j = i or i + 1
-
-    auto pass = [&](int n_cells, int do_split, bool first) -> int {
-        int r;
-        {
-            kscope ks(ctx, GHMM_K_PREPARE);
-            hipLaunchKernelGGL(k_finit_pass, dim3((unsigned)N, (unsigned)P), dim3(FI_THREADS), pass_lds, ctx->stream,
-                               N, M, D, n_cells, first ? 0 : 1, c->U, upb, c->X, c->off, fm->mean, part,
-                               (double *)nullptr, (double *)nullptr);
-        }
-        if ((r = launch_ok("k_finit_pass"))) return r;
-        const double *src = part;
-        int np = P;
-        if (cm) { // the sums of all shards: every rank then does the same bookkeeping on the same numbers
-            {
-                kscope ks(ctx, GHMM_K_REDUCE);
-                hipLaunchKernelGGL(k_finit_reduce, dim3((unsigned)((slice + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (long long)slice, P, (const double *)part, sums);
-            }
-            if ((r = launch_ok("k_finit_reduce"))) return r;
-            RCCL_TRY(api, api->AllReduce(sums, sums, slice, ncclDouble, ncclSum, cm->comm, ctx->stream));
-            src = sums;
-            np = 1;
-        }
-        {
-            kscope ks(ctx, GHMM_K_REDUCE);
-            hipLaunchKernelGGL(k_finit_cells, dim3((unsigned)N), dim3(64), (size_t)n_cells * E2 * sizeof(double),
-                               ctx->stream, N, M, D, n_cells, do_split, first ? 1 : 0, np, src, 1.05, 0.95, 1.005,
-                               0.995, fm->mean);
-        }
-        return launch_ok("k_finit_cells");
-    };
-    // init_mix_mean (TFF:970-1134): the state's mean, then five passes per level
-    if ((rc = pass(1, 1 < M ? 1 : 0, true))) return rc;
-    int nc = 1;
-    while (nc < M) {
-        nc = (2 * nc < M) ? 2 * nc : M;
-        for (int it = 0; it < 5; it++)
-            if ((rc = pass(nc, (it == 4 && nc < M) ? 1 : 0, false))) return rc;
-    }
-    // init_mix_param (TFF:810-952): one more classification, its one-hot rows into gamma and post;
-    // k_fullstats takes dif around the model's mean, which is the cell
-    {
-        kscope ks(ctx, GHMM_K_PREPARE);
-        hipLaunchKernelGGL(k_finit_pass, dim3((unsigned)N, (unsigned)P), dim3(FI_THREADS), pass_lds, ctx->stream, N, M,
-                           D, M, 1, c->U, upb, c->X, c->off, fm->mean, part, ctx->gamma, ctx->post);
-    }
-    long long PF = 0;
-    if ((rc = launch_ok("k_finit_pass")) || (rc = run_fullstats_part(ctx, fm, c, &PF))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_REDUCE);
-        if ((rc = run_fullstats_reduce(ctx, fm, PF, full_c))) return rc;
-    }
-    if (cm)
-        RCCL_TRY(api, api->AllReduce(full_c, full_c, (size_t)G * fs_elems(D), ncclDouble, ncclSum, cm->comm,
-                                     ctx->stream));
-    {
-        kscope ks(ctx, GHMM_K_MSTEP);
-        hipLaunchKernelGGL(k_finit_gauss, dim3((unsigned)G), dim3(FM_THREADS), fm_gauss_lds_bytes(D), ctx->stream, N,
-                           M, D, (const double *)full, fm->mean, fm->inv_cov, fm->det);
-    }
-    if ((rc = launch_ok("k_finit_gauss"))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_MSTEP);
-        hipLaunchKernelGGL(k_finit_state, dim3((unsigned)N), dim3(FM_THREADS), 0, ctx->stream, N, M, D,
-                           (const double *)full, pow(2.0 * M_PI, D / 2.0), 1, fm->A, fm->c, fm->mean, fm->inv_cov,
-                           fm->det, fm->den, fm->lk, fm->logA);
-    }
-    return launch_ok("k_finit_state");
-}
+// ------------------------------------------------ full-covariance models
+#include "ghmm_fullhost.hpp"

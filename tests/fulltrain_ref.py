@@ -341,7 +341,7 @@ def build(G, name):
 
 
 def fs_geometry(N, M, D):
-    """run_fullstats' launch geometry (ghmm_hip.hip): frames staged per pass and the Gaussians
+    """run_fullstats' launch geometry (ghmm_fullhost.hpp): frames staged per pass and the Gaussians
     [g0, g1] of every element batch"""
     G_, E1 = N * M, 1 + D + D * (D + 1) // 2
     batch = 256 * 8                                  # FS_THREADS * FS_EPT
