@@ -464,6 +464,52 @@ int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
  * A keeps the general recursions).  Both launches count under GHMM_K_MSTEP. */
 int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
 
+/* ---------------------- the full-covariance trainer and recogniser on several feature streams */
+
+/* TFF and RC both take param_number = P feature streams: every recursion runs on the product over the
+ * streams of the emission densities, taken in stream order from 1.0 (TFF:1436-1442, TFF:1460-1465,
+ * RC:760-789), while calc_symbol_probab, calc_mix_param and the mixture update run once per stream
+ * with that stream's own mixtures (TFF:256-297, TFF:316-342).  The three calls below mirror
+ * ghmm_estep_streams / ghmm_score_streams:
+ *   1 <= n_streams <= GHMM_MAX_STREAMS;  models[p] / corpora[p] = stream p;
+ *   every stream has the same N, the same utterance count and the same lengths;
+ *   every stream has its own M_p and D_p, within ghmm_fmodel's caps;
+ *   the transitions (A, log A, the band flag) are models[0]'s;
+ *   n_streams == 1 is the single-stream call itself (ghmm_estep_full, or with log_domain
+ *   ghmm_estep_full_log; ghmm_score_full; ghmm_logscore_full): the same bits.
+ * The product is formed by the emission launches: stream 0 writes b, the launch of every later stream
+ * multiplies its density into it with one IEEE multiply, the earlier streams' product on the left, so
+ * b = ((b^0 * b^1) * b^2)..., which is the reference's `product = 1.0; product *= ...` since
+ * 1.0 * b^0 == b^0.  In the log domain log b = ((log b^0 + log b^1) + log b^2)...; NaN and +-inf
+ * propagate as the multiplication or addition gives them.  Each stream's mixture posteriors are formed
+ * from that stream's own density, and TFF's 1e20 clamp applies per stream (TFF:1775-1887).
+ * Asynchrony, reproducibility, GHMM_OPT_DELTA and GHMM_OPT_PARTIALS are the single-stream calls'.
+ * Afterwards GHMM_BUF_B holds the product (or the sum of logs) and GHMM_BUF_GAMMA / _ALPHA / _BETA /
+ * _LOGLIK are as after the single-stream call; GHMM_BUF_POST is not part of the contract when
+ * n_streams > 1.  The workspace is owned as after ghmm_emission_full: the diagonal row API refuses it.
+ * Refusals, each before anything is launched: GHMM_OPT_ROBUST set gives GHMM_ERR_UNSUPPORTED; a null
+ * array or entry, n_streams outside the range, streams that differ in N, in the utterance count or in
+ * a length, a corpus of another D than its model, or a statistics vector that is diagonal or not of its
+ * stream's shape gives GHMM_ERR_ARG.
+ * Out of scope: Viterbi over several streams, and the batched vocabulary calls (*_full_batch) for
+ * several streams; a recogniser scores model by model when P > 1, as the diagonal one does. */
+/* One E-step over the whole corpus.  stats[p] is a ghmm_stats_create_full(N, M_p, D_p) vector.
+ * log_domain == 0: every stream's emission as in ghmm_estep_full, ghmm_estep_full's recursion launches
+ * on the product, then calc_mix_param and the reductions once per stream with that stream's
+ * posteriors, frames and means (TFF:289-297).  log_domain != 0: ghmm_estep_full_log's definition with
+ * log b = sum_p log b^p in stream order and per-stream post.  The common sums (num_a, den_a, den_c,
+ * loglik, n_utt) go into every vector, so ghmm_mstep_full(models[p], stats[p]) or ghmm_mstep_full_dev
+ * for every p is the M-step of TFF:313-342; all of them write the same A. */
+int ghmm_estep_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                            int n_streams, ghmm_stats *const *stats, int log_domain);
+/* ghmm_score_full on the product: no final-state term (RC:822-836).  Synchronises. */
+int ghmm_score_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                            int n_streams, double *loglik_host);
+/* ghmm_logscore_full on the sum of the streams' log b, with both final_state conventions: finite
+ * where the linear product underflows to 0.  Synchronises. */
+int ghmm_logscore_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                               int n_streams, int final_state, double *loglik_host);
+
 /* -------------------------------------- several GPUs: the one collective */
 
 /* Utterances shard data-parallel over ranks (one rank = one process or host thread with
@@ -599,6 +645,15 @@ int ghmm_host_fmodel_alloc(ghmm_host_fmodel *hfm, int N, int M, int D);
 void ghmm_host_fmodel_free(ghmm_host_fmodel *hfm);
 int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm);
 int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_bytes);
+/* The same for full-covariance models of several feature streams (writer TFF:2278-2400, reader
+ * RC:591-707): length-prefixed word, int N, int P, int M[P], int D[P], A[N][N], then per stream, per
+ * state c[M_p] and per mixture mean[D_p], det, inv_cov[D_p][D_p].  hfm[p] = stream p with its own M
+ * and D; word, N and A are common (the reader fills them into every hfm[p]).  The reader takes up to
+ * max_streams (<= GHMM_MAX_STREAMS) and reports the file's count (more: GHMM_ERR_UNSUPPORTED); a
+ * diagonal file, or anything else that does not fit, gives GHMM_ERR_FORMAT; 4- or 8-byte length
+ * prefix, told apart by the exact file size.  ghmm_hmm_read_full keeps refusing P > 1. */
+int ghmm_hmm_read_full_streams(const char *path, ghmm_host_fmodel *hfm, int max_streams, int *n_streams);
+int ghmm_hmm_write_full_streams(const char *path, const ghmm_host_fmodel *hfm, int n_streams, int len_bytes);
 
 /* creating_initial_model TF:732-1317 (uniform segmentation, LBG splitting with
  * factors 1.005/0.995, three k-means passes, per-cell variance floored at 1e-5)

@@ -66,7 +66,15 @@ __host__ __device__ inline int fc_lds_doubles(int D) { return WAVE * (D | 1) + F
 //     divide): post = (c * gaus) / b, or 0 where b == 0.
 // The weighted densities go to post as they are formed and are divided in place once b is known
 // (each lane rereads only what it wrote itself).
-template <int DB, int MODE = FC_LIN>
+//
+// FOLD is the variant for the second and later feature streams of a model of several streams
+// (ghmm_estep_full_streams and the score calls, TFF:1436-1442, RC:760-789): everything up to the store
+// epilogue is the stream's own, the 1e20 clamp and the posteriors (formed from the stream's own bi)
+// included; the epilogue then combines with what b holds from the streams before instead of
+// overwriting it: b = b_old * bt, one multiply with the earlier streams' product on the left (linear
+// modes), or log b = logb_old + bt (log modes).  Stream 0 is launched without FOLD, so b ends as
+// ((b0 * b1) * b2)..., the reference's `product = 1.0; product *= ...` (1.0 * b0 == b0).
+template <int DB, int MODE = FC_LIN, bool FOLD = false>
 __global__ void __launch_bounds__(FC_WAVES * WAVE)
 k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
                 const double *__restrict__ mean, const double *__restrict__ inv_cov,
@@ -150,7 +158,12 @@ k_emission_full(int NS, int M, int D, long long F, const double *__restrict__ X,
     __syncthreads();
     for (int k = lane; k < nf * ns; k += WAVE) {
         const int r = k / ns, col = k - r * ns;
-        b[(f0 + r) * NS + s0 + col] = bt[r * SS + col];
+        if constexpr (FOLD) {
+            double *dst = b + (f0 + r) * NS + s0 + col;
+            *dst = LOG ? *dst + bt[r * SS + col] : *dst * bt[r * SS + col];
+        } else {
+            b[(f0 + r) * NS + s0 + col] = bt[r * SS + col];
+        }
     }
 }
 

@@ -151,47 +151,60 @@ static int check_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c
     return GHMM_OK;
 }
 
-// one k_emission_full launch; post only where MODE writes posteriors, lk only where it works in logs
-template <int DB, int MODE>
-static void launch_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+// one k_emission_full launch; post only where MODE writes posteriors, lk only where it works in logs.
+// FOLD: a later feature stream's launch, which combines with the b of the streams before it
+template <int DB, int MODE, bool FOLD>
+static void launch_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, double *post)
 {
     constexpr bool POST = MODE == FC_POST || MODE == FC_LOGPOST, LOG = MODE == FC_LOG || MODE == FC_LOGPOST;
     const int nch = (fm->N + FC_SC - 1) / FC_SC;
     const dim3 grid((unsigned)((c->F + WAVE - 1) / WAVE), (unsigned)((nch + FC_WAVES - 1) / FC_WAVES));
     const size_t lds = (size_t)fc_lds_doubles(fm->D) * sizeof(double);
-    hipLaunchKernelGGL((k_emission_full<DB, MODE>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M,
+    hipLaunchKernelGGL((k_emission_full<DB, MODE, FOLD>), grid, dim3(FC_WAVES * WAVE), lds, ctx->stream, fm->N, fm->M,
                        fm->D, c->F, c->X, fm->mean, fm->inv_cov, fm->den, fm->c, ctx->b,
-                       POST ? ctx->post : (double *)nullptr, LOG ? fm->lk : (const double *)nullptr);
+                       POST ? post : (double *)nullptr, LOG ? fm->lk : (const double *)nullptr);
 }
 
-template <int DB>
-static void emission_full_by_mode(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode)
+template <int DB, bool FOLD>
+static void emission_full_by_mode(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode, double *post)
 {
     switch (mode) {
-    case FC_POST: launch_emission_full<DB, FC_POST>(ctx, fm, c); break;
-    case FC_LOGPOST: launch_emission_full<DB, FC_LOGPOST>(ctx, fm, c); break;
-    case FC_LOG: launch_emission_full<DB, FC_LOG>(ctx, fm, c); break;
-    default: launch_emission_full<DB, FC_LIN>(ctx, fm, c); break;
+    case FC_POST: launch_emission_full<DB, FC_POST, FOLD>(ctx, fm, c, post); break;
+    case FC_LOGPOST: launch_emission_full<DB, FC_LOGPOST, FOLD>(ctx, fm, c, post); break;
+    case FC_LOG: launch_emission_full<DB, FC_LOG, FOLD>(ctx, fm, c, post); break;
+    default: launch_emission_full<DB, FC_LIN, FOLD>(ctx, fm, c, post); break;
+    }
+}
+
+template <bool FOLD>
+static void emission_full_by_db(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode, double *post)
+{
+    switch ((fm->D + 7) / 8 * 8) {
+    case 8: emission_full_by_mode<8, FOLD>(ctx, fm, c, mode, post); break;
+    case 16: emission_full_by_mode<16, FOLD>(ctx, fm, c, mode, post); break;
+    case 24: emission_full_by_mode<24, FOLD>(ctx, fm, c, mode, post); break;
+    case 32: emission_full_by_mode<32, FOLD>(ctx, fm, c, mode, post); break;
+    case 40: emission_full_by_mode<40, FOLD>(ctx, fm, c, mode, post); break;
+    default: emission_full_by_mode<48, FOLD>(ctx, fm, c, mode, post); break;
     }
 }
 
 // mode: FC_LIN (b), FC_POST (b and the mixture posteriors), FC_LOG (log b), FC_LOGPOST (log b and
-// the mixture posteriors)
-static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN)
+// the mixture posteriors).  stream_post: a model of several feature streams (emission_full_streams);
+// stream p's posteriors go there, and p > 0 (`fold`) multiplies into, or adds onto, the b in the workspace
+static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int mode = FC_LIN,
+                             bool fold = false, double *stream_post = nullptr)
 {
-    ws_disown(ctx);
-    ctx->em_c = c;
-    ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
+    if (!fold) {
+        ws_disown(ctx);
+        ctx->em_c = c;
+        ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
+    }
     if (c->F == 0) return GHMM_OK;
     kscope ks(ctx, GHMM_K_EMISSION);
-    switch ((fm->D + 7) / 8 * 8) {
-    case 8: emission_full_by_mode<8>(ctx, fm, c, mode); break;
-    case 16: emission_full_by_mode<16>(ctx, fm, c, mode); break;
-    case 24: emission_full_by_mode<24>(ctx, fm, c, mode); break;
-    case 32: emission_full_by_mode<32>(ctx, fm, c, mode); break;
-    case 40: emission_full_by_mode<40>(ctx, fm, c, mode); break;
-    default: emission_full_by_mode<48>(ctx, fm, c, mode); break;
-    }
+    double *post = stream_post ? stream_post : ctx->post;
+    if (fold) emission_full_by_db<true>(ctx, fm, c, mode, post);
+    else emission_full_by_db<false>(ctx, fm, c, mode, post);
     return launch_ok("k_emission_full");
 }
 
@@ -203,14 +216,11 @@ extern "C" int ghmm_emission_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c
     return run_emission_full(ctx, fm, c);
 }
 
-extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host)
+// calc_alpha + calc_probability without the final-state term (RC:733-836) on the b in the workspace:
+// k_scan_pair's only = 3; the scores to the host
+static int run_score_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, double *loglik_host)
 {
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c))) return rc;
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c))) return rc;
-    if (c->U == 0) return GHMM_OK;
-    // calc_alpha + calc_probability without the final-state term: k_scan_pair's only = 3
+    int rc;
     const lane_grid lg(fm->N, c->U);
     {
         kscope ks(ctx, GHMM_K_FORWARD);
@@ -223,6 +233,16 @@ extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, d
     HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
+}
+
+extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    return run_score_full(ctx, fm, c, loglik_host);
 }
 
 // A vocabulary call up to its one launch: the checks (`what` = the entry point's name in their
@@ -347,6 +367,17 @@ static int run_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, in
     return vocab_scores_out(ctx, n_models, c, loglik_host);
 }
 
+// the batch call's lattice launch on a table of one word: that table (fm's log A) into ctx->fbt_tab
+static int logforward_one_word(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+{
+    int rc;
+    const fwd_model one = {fm->logA, fm->N, 0};
+    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
+    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    return GHMM_OK;
+}
+
 extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
                                   double *loglik_host)
 {
@@ -354,11 +385,7 @@ extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c
     if (rc || (rc = check_full(ctx, fm, c))) return rc;
     ARG_CHECK(loglik_host || c->U == 0, "null destination");
     if (c->U == 0) return GHMM_OK;
-    // the batch call's lattice launch on a table of one word
-    const fwd_model one = {fm->logA, fm->N, 0};
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
-    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = logforward_one_word(ctx, fm, c))) return rc;
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
     return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
 }
@@ -455,6 +482,22 @@ static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_st
     return launch_ok("k_reduce_all");
 }
 
+// calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
+// diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this model's A
+// and the densities in the workspace
+static int run_recursions_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
+{
+    int rc;
+    ghmm_model *rm = &fm->rec;
+    bool fused = false;
+    if ((rc = run_scan_combine(ctx, rm, c, &fused))) return rc;
+    if (!fused) {
+        if ((rc = run_forward(ctx, rm, c, true))) return rc;
+        if ((rc = run_backward(ctx, rm, c, false))) return rc;
+    }
+    return GHMM_OK;
+}
+
 extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
 {
     int rc = use(ctx);
@@ -464,28 +507,15 @@ extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, g
     if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
     if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_POST))) return rc;
-    // calc_alpha / calc_beta / calc_transition_probab / calc_den_mix_coef / calc_probability are the
-    // diagonal trainer's, final-state term included (TFF:274-299): the same launches, on this
-    // model's A and the densities above
-    bool fused = false;
-    if ((rc = run_scan_combine(ctx, rm, c, &fused))) return rc;
-    if (!fused) {
-        if ((rc = run_forward(ctx, rm, c, true))) return rc;
-        if ((rc = run_backward(ctx, rm, c, false))) return rc;
-    }
+    if ((rc = run_recursions_full(ctx, fm, c))) return rc;
     return run_fullstats(ctx, fm, c, s);
 }
 
-// The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
-// and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
-// (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
-extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+// the log-domain lattice and its utterance sums (k_logfb_fwd / k_logfb_bwd) on fm's log A and the
+// log b in the workspace
+static int run_log_lattice_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
 {
-    int rc = use(ctx);
-    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
-    if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
+    int rc;
     if (c->U) {
         const lane_grid lg(fm->N, c->U);
         kscope ks(ctx, GHMM_K_FORWARD);
@@ -502,6 +532,20 @@ extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *
     }
     ctx->slots = c->U; // one partial per utterance
     ctx->loglik_pieces = false;
+    return GHMM_OK;
+}
+
+// The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
+// and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
+// (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
+extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
+    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
+    if ((rc = run_log_lattice_full(ctx, fm, c))) return rc;
     return run_fullstats(ctx, fm, c, s);
 }
 
@@ -670,4 +714,114 @@ extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, 
         RCCL_TRY(api, api->AllReduce(full_c, full_c, (size_t)G * fs_elems(D), ncclDouble, ncclSum, cm->comm,
                                      ctx->stream));
     return run_fmstep<true>(ctx, fm, full, 1);
+}
+
+// ------------------------------------------------ several feature streams (TFF, RC: param_number P > 1)
+// Every recursion runs on the product over the streams of the emission densities, taken in stream
+// order (TFF:1436-1442, TFF:1460-1465, RC:760-789); the mixtures are each stream's own (TFF:256-297,
+// TFF:316-342).  The product is formed by the emission launches themselves: stream 0 writes b, every
+// later stream's launch (k_emission_full's FOLD) multiplies into it, or adds onto log b.  There is no
+// second b and no pass of its own for the product.
+
+// `stats` may be null (the score calls); nothing is launched before every check has passed
+static int check_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora, int P,
+                              ghmm_stats *const *stats, bool want_stats)
+{
+    if (!models || !corpora || (want_stats && !stats) || P < 1 || P > GHMM_MAX_STREAMS) {
+        ghmm_set_error("bad stream arguments (1 to %d feature streams, no null array)", GHMM_MAX_STREAMS);
+        return GHMM_ERR_ARG;
+    }
+    for (int p = 0; p < P; p++) {
+        int rc = check_full(ctx, models[p], corpora[p]);
+        if (rc) return rc;
+        if (models[p]->N != models[0]->N) {
+            ghmm_set_error("stream %d has %d states, stream 0 has %d", p, models[p]->N, models[0]->N);
+            return GHMM_ERR_ARG;
+        }
+        if (corpora[p]->U != corpora[0]->U || corpora[p]->len != corpora[0]->len) {
+            ghmm_set_error("stream %d: utterance count or lengths differ from stream 0", p);
+            return GHMM_ERR_ARG;
+        }
+        if (want_stats && (rc = check_stats_full(models[p], stats[p]))) return rc;
+    }
+    return GHMM_OK;
+}
+
+// the workspace of stream 0's shape, then every stream's emission in stream order: ctx->b ends up
+// holding the product (log modes: the sum of logs), ctx->post_s[p] stream p's posteriors
+static int emission_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora, int P,
+                                 int mode)
+{
+    int rc;
+    const bool want_post = mode == FC_POST || mode == FC_LOGPOST;
+    if ((rc = ws_full(ctx, models[0]->N, models[0]->M, corpora[0]))) return rc;
+    if (want_post) {
+        if ((int)ctx->post_s.size() < P) {
+            ctx->post_s.resize((size_t)P, nullptr);
+            ctx->cap_post_s.resize((size_t)P, 0);
+        }
+        for (int p = 0; p < P; p++)
+            if ((rc = dev_grow(&ctx->post_s[p], &ctx->cap_post_s[p],
+                               (size_t)corpora[p]->F * models[p]->N * models[p]->M)))
+                return rc;
+    }
+    for (int p = 0; p < P; p++)
+        if ((rc = run_emission_full(ctx, models[p], corpora[p], mode, p > 0, want_post ? ctx->post_s[p] : nullptr)))
+            return rc;
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_estep_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                                       int P, ghmm_stats *const *stats, int log_domain)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full_streams(ctx, models, corpora, P, stats, true))) return rc;
+    if (P == 1)
+        return log_domain ? ghmm_estep_full_log(ctx, models[0], corpora[0], stats[0])
+                          : ghmm_estep_full(ctx, models[0], corpora[0], stats[0]);
+    ghmm_fmodel *fm = models[0];
+    ghmm_corpus *c = corpora[0];
+    if ((rc = ws_fb(ctx, &fm->rec, c))) return rc;
+    if (!log_domain && (rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
+    if ((rc = emission_full_streams(ctx, models, corpora, P, log_domain ? FC_LOGPOST : FC_POST))) return rc;
+    // the single-stream calls' recursion launches, on models[0]'s transitions and the product
+    if ((rc = log_domain ? run_log_lattice_full(ctx, fm, c) : run_recursions_full(ctx, fm, c))) return rc;
+    // calc_mix_param per stream (TFF:289-297) with the common gamma; the transition sums, den_c, log P
+    // and the exemplar count go into every stream's vector
+    double *const post_own = ctx->post;
+    for (int p = 0; p < P && !rc; p++) {
+        ctx->post = ctx->post_s[p];
+        rc = run_fullstats(ctx, models[p], corpora[p], stats[p]);
+    }
+    ctx->post = post_own;
+    return rc;
+}
+
+extern "C" int ghmm_score_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                                       int P, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full_streams(ctx, models, corpora, P, nullptr, false))) return rc;
+    if (P == 1) return ghmm_score_full(ctx, models[0], corpora[0], loglik_host);
+    ghmm_corpus *c = corpora[0];
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LIN))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    return run_score_full(ctx, models[0], c, loglik_host);
+}
+
+extern "C" int ghmm_logscore_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models,
+                                          ghmm_corpus *const *corpora, int P, int final_state,
+                                          double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_full_streams(ctx, models, corpora, P, nullptr, false))) return rc;
+    if (P == 1) return ghmm_logscore_full(ctx, models[0], corpora[0], final_state, loglik_host);
+    ghmm_fmodel *fm = models[0];
+    ghmm_corpus *c = corpora[0];
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    if (c->U == 0) return GHMM_OK;
+    if ((rc = logforward_one_word(ctx, fm, c))) return rc;
+    if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG))) return rc;
+    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
 }

@@ -372,8 +372,10 @@ void ghmm_host_fmodel_free(ghmm_host_fmodel *hfm)
     hfm->A = hfm->c = hfm->mean = hfm->det = hfm->inv_cov = NULL;
 }
 
-/* the full-covariance layout with an `lb`-byte length prefix; 0 = fits the file exactly */
-static int fhmm_try(FILE *f, long size, int lb, ghmm_host_fmodel *hfm, const char *path)
+/* the full-covariance layout with an `lb`-byte length prefix; 0 = fits the file exactly.  Up to
+   `max_p` feature streams (TFF:2278-2400): hfm[p] = stream p, each with its own copy of the word, N
+   and A; *P_out = the file's stream count. */
+static int fhmm_try(FILE *f, long size, int lb, ghmm_host_fmodel *hfm, int max_p, int *P_out, const char *path)
 {
     unsigned char raw[8] = {0};
     rewind(f);
@@ -393,43 +395,54 @@ static int fhmm_try(FILE *f, long size, int lb, ghmm_host_fmodel *hfm, const cha
         expect += 8L * (long)N * ((long)M[p] + (long)M[p] * ((long)D[p] * D[p] + D[p] + 1));
     }
     if (expect != size) return GHMM_ERR_FORMAT;
-    if (P > 1) {
-        ghmm_set_error("%s: %d feature streams, the full-covariance reader takes one", path, P);
+    if (P > max_p) {
+        if (max_p == 1)
+            ghmm_set_error("%s: %d feature streams, the full-covariance reader takes one", path, P);
+        else
+            ghmm_set_error("%s: %d feature streams, the caller takes %d", path, P, max_p);
         return GHMM_ERR_UNSUPPORTED;
     }
-    int rc = ghmm_host_fmodel_alloc(hfm, N, M[0], D[0]);
-    if (rc) return rc;
-    memcpy(hfm->word, word, GHMM_MAX_WORD);
-    const size_t DD = (size_t)D[0] * D[0];
-    int ok = fread(hfm->A, 8, (size_t)N * N, f) == (size_t)N * N;
-    for (int i = 0; ok && i < N; i++) {
-        ok = fread(hfm->c + (size_t)i * M[0], 8, (size_t)M[0], f) == (size_t)M[0];
-        for (int k = 0; ok && k < M[0]; k++) {
-            size_t g = (size_t)i * M[0] + k;
-            ok = fread(hfm->mean + g * D[0], 8, (size_t)D[0], f) == (size_t)D[0] &&
-                 fread(hfm->det + g, 8, 1, f) == 1 &&
-                 fread(hfm->inv_cov + g * DD, 8, DD, f) == DD;
+    int rc = GHMM_OK, ok = 1;
+    for (int p = 0; p < P; p++) memset(&hfm[p], 0, sizeof hfm[p]);
+    for (int p = 0; p < P && !rc; p++) {
+        rc = ghmm_host_fmodel_alloc(&hfm[p], N, M[p], D[p]);
+        if (!rc) memcpy(hfm[p].word, word, GHMM_MAX_WORD);
+    }
+    if (!rc) {
+        ok = fread(hfm[0].A, 8, (size_t)N * N, f) == (size_t)N * N;
+        for (int p = 1; p < P; p++) memcpy(hfm[p].A, hfm[0].A, sizeof(double) * (size_t)N * N);
+        for (int p = 0; ok && p < P; p++) {
+            const size_t DD = (size_t)D[p] * D[p];
+            for (int i = 0; ok && i < N; i++) {
+                ok = fread(hfm[p].c + (size_t)i * M[p], 8, (size_t)M[p], f) == (size_t)M[p];
+                for (int k = 0; ok && k < M[p]; k++) {
+                    size_t g = (size_t)i * M[p] + k;
+                    ok = fread(hfm[p].mean + g * D[p], 8, (size_t)D[p], f) == (size_t)D[p] &&
+                         fread(hfm[p].det + g, 8, 1, f) == 1 &&
+                         fread(hfm[p].inv_cov + g * DD, 8, DD, f) == DD;
+                }
+            }
         }
     }
-    if (!ok) {
-        ghmm_host_fmodel_free(hfm);
-        return GHMM_ERR_IO;
+    if (rc || !ok) {
+        for (int p = 0; p < P; p++) ghmm_host_fmodel_free(&hfm[p]);
+        return rc ? rc : GHMM_ERR_IO;
     }
+    *P_out = P;
     return GHMM_OK;
 }
 
-int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm)
+int ghmm_hmm_read_full_streams(const char *path, ghmm_host_fmodel *hfm, int max_streams, int *n_streams)
 {
-    if (!path || !hfm) return GHMM_ERR_ARG;
-    memset(hfm, 0, sizeof *hfm);
+    if (!path || !hfm || !n_streams || max_streams <= 0) return GHMM_ERR_ARG;
     FILE *f = fopen(path, "rb");
     if (!f) {
         ghmm_set_error("file %s not found", path);
         return GHMM_ERR_IO;
     }
     long size = file_size(f);
-    int rc = fhmm_try(f, size, 8, hfm, path);
-    if (rc == GHMM_ERR_FORMAT) rc = fhmm_try(f, size, 4, hfm, path);
+    int rc = fhmm_try(f, size, 8, hfm, max_streams, n_streams, path);
+    if (rc == GHMM_ERR_FORMAT) rc = fhmm_try(f, size, 4, hfm, max_streams, n_streams, path);
     fclose(f);
     if (rc == GHMM_ERR_FORMAT)
         ghmm_set_error("%s: not a full-covariance .hmm file (4- or 8-byte header)", path);
@@ -438,30 +451,52 @@ int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm)
     return rc;
 }
 
-int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_bytes)
+int ghmm_hmm_read_full(const char *path, ghmm_host_fmodel *hfm)
 {
-    if (!path || !hfm || hfm->N <= 0 || hfm->M <= 0 || hfm->D <= 0 || (len_bytes != 4 && len_bytes != 8))
+    if (!path || !hfm) return GHMM_ERR_ARG;
+    memset(hfm, 0, sizeof *hfm);
+    int P = 0;
+    return ghmm_hmm_read_full_streams(path, hfm, 1, &P);
+}
+
+int ghmm_hmm_write_full_streams(const char *path, const ghmm_host_fmodel *hfm, int n_streams, int len_bytes)
+{
+    if (!path || !hfm || n_streams <= 0 || n_streams > GHMM_MAX_STREAMS || (len_bytes != 4 && len_bytes != 8))
         return GHMM_ERR_ARG;
+    const int N = hfm[0].N, P = n_streams;
+    for (int p = 0; p < P; p++) {
+        if (hfm[p].N <= 0 || hfm[p].M <= 0 || hfm[p].D <= 0) return GHMM_ERR_ARG;
+        if (hfm[p].N != N) {
+            ghmm_set_error("ghmm_hmm_write_full_streams: the streams differ in their number of states");
+            return GHMM_ERR_ARG;
+        }
+    }
     FILE *f = fopen(path, "wb");
     if (!f) {
         ghmm_set_error("can't open file %s", path);
         return GHMM_ERR_IO;
     }
-    const int N = hfm->N, M = hfm->M, D = hfm->D;
-    const size_t DD = (size_t)D * D;
-    int32_t hdr[4] = {N, 1, M, D};
-    uint64_t len = strnlen(hfm->word, GHMM_MAX_WORD - 1);
+    int32_t hdr[2] = {N, P}, MD[2 * GHMM_MAX_STREAMS];
+    for (int p = 0; p < P; p++) {
+        MD[p] = hfm[p].M;
+        MD[P + p] = hfm[p].D;
+    }
+    uint64_t len = strnlen(hfm[0].word, GHMM_MAX_WORD - 1);
     int ok = fwrite(&len, 1, (size_t)len_bytes, f) == (size_t)len_bytes; /* little-endian */
-    ok = ok && fwrite(hfm->word, 1, (size_t)len, f) == (size_t)len;
-    ok = ok && fwrite(hdr, 4, 4, f) == 4;
-    ok = ok && fwrite(hfm->A, 8, (size_t)N * N, f) == (size_t)N * N;
-    for (int i = 0; ok && i < N; i++) {
-        ok = fwrite(hfm->c + (size_t)i * M, 8, (size_t)M, f) == (size_t)M;
-        for (int k = 0; ok && k < M; k++) {
-            size_t g = (size_t)i * M + k;
-            ok = fwrite(hfm->mean + g * D, 8, (size_t)D, f) == (size_t)D &&
-                 fwrite(hfm->det + g, 8, 1, f) == 1 &&
-                 fwrite(hfm->inv_cov + g * DD, 8, DD, f) == DD;
+    ok = ok && fwrite(hfm[0].word, 1, (size_t)len, f) == (size_t)len;
+    ok = ok && fwrite(hdr, 4, 2, f) == 2 && fwrite(MD, 4, 2 * (size_t)P, f) == 2 * (size_t)P;
+    ok = ok && fwrite(hfm[0].A, 8, (size_t)N * N, f) == (size_t)N * N;
+    for (int p = 0; ok && p < P; p++) {
+        const int M = hfm[p].M, D = hfm[p].D;
+        const size_t DD = (size_t)D * D;
+        for (int i = 0; ok && i < N; i++) {
+            ok = fwrite(hfm[p].c + (size_t)i * M, 8, (size_t)M, f) == (size_t)M;
+            for (int k = 0; ok && k < M; k++) {
+                size_t g = (size_t)i * M + k;
+                ok = fwrite(hfm[p].mean + g * D, 8, (size_t)D, f) == (size_t)D &&
+                     fwrite(hfm[p].det + g, 8, 1, f) == 1 &&
+                     fwrite(hfm[p].inv_cov + g * DD, 8, DD, f) == DD;
+            }
         }
     }
     if (fclose(f) != 0) ok = 0;
@@ -470,4 +505,10 @@ int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_b
         return GHMM_ERR_IO;
     }
     return GHMM_OK;
+}
+
+int ghmm_hmm_write_full(const char *path, const ghmm_host_fmodel *hfm, int len_bytes)
+{
+    if (!path || !hfm) return GHMM_ERR_ARG;
+    return ghmm_hmm_write_full_streams(path, hfm, 1, len_bytes);
 }

@@ -19,8 +19,10 @@
  * Built with -DGHMM_FULL_COV this is recognition-continuous-test-full-fs, the full-covariance
  * recogniser RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c: the same
  * argv, lists and bookkeeping (RC:283-412), its usage text and header (RC:1019-1033), models read
- * with ghmm_hmm_read_full (RC:591-707, one stream) and scored with ghmm_score_full_batch, whose
- * log P has no final-state term (calc_probability, RC:822-836).  With GHMM_LOG_SCORE=1 in the
+ * with ghmm_hmm_read_full_streams (RC:591-707) and scored with ghmm_score_full_batch, whose
+ * log P has no final-state term (calc_probability, RC:822-836); a set whose models hold several
+ * feature streams is scored model by model with ghmm_score_full_streams (GHMM_LOG_SCORE=1:
+ * ghmm_logscore_full_streams).  With GHMM_LOG_SCORE=1 in the
  * environment that program scores in the log domain instead (ghmm_logscore_full_batch, final_state
  * = 0: the same quantity, finite where the linear densities underflow) and says so in the report's
  * second line; without the variable nothing changes.
@@ -141,7 +143,7 @@ int main(int argc, char **argv)
 
     /* models: one list per set, the same vocabulary in every set */
 #ifdef GHMM_FULL_COV
-    ghmm_host_fmodel *fhm[MAX_SETS]; /* fhm[j][k]: set j, word k (one stream) */
+    ghmm_host_fmodel *fhm[MAX_SETS]; /* fhm[j][k * GHMM_MAX_STREAMS + p]: set j, word k, stream p */
 #else
     ghmm_host_model *hm[MAX_SETS]; /* hm[j][k * GHMM_MAX_STREAMS + p]: set j, word k, stream p */
 #endif
@@ -154,15 +156,22 @@ int main(int argc, char **argv)
         int n = 0, cap = 0;
 #ifdef GHMM_FULL_COV
         fhm[j] = NULL;
-        Pj[j] = 1;
         while (fscanf(fl, "%4095s", name) == 1) {
             printf("Model: %s\r\n", name);
             if (n == cap) {
                 cap = cap ? 2 * cap : 32;
-                fhm[j] = (ghmm_host_fmodel *)realloc(fhm[j], (size_t)cap * sizeof(ghmm_host_fmodel));
+                fhm[j] = (ghmm_host_fmodel *)realloc(fhm[j], (size_t)cap * GHMM_MAX_STREAMS * sizeof(ghmm_host_fmodel));
                 if (!fhm[j]) die("memory", GHMM_ERR_ALLOC);
             }
-            if ((rc = ghmm_hmm_read_full(name, &fhm[j][n]))) die("reading model", rc);
+            /* the file says how many feature streams the model has (RC:591-707) */
+            int pn = 0;
+            if ((rc = ghmm_hmm_read_full_streams(name, &fhm[j][(size_t)n * GHMM_MAX_STREAMS], GHMM_MAX_STREAMS, &pn)))
+                die("reading model", rc);
+            if (n == 0) Pj[j] = pn;
+            if (pn != Pj[j]) {
+                printf("model %s has %d parameters, the first model of %s has %d \n", name, pn, argv[2 + j], Pj[j]);
+                exit(1);
+            }
             n++;
         }
 #else
@@ -198,7 +207,7 @@ int main(int argc, char **argv)
     }
     char **word = (char **)malloc((size_t)word_number * sizeof(char *));
 #ifdef GHMM_FULL_COV
-    for (int k = 0; k < word_number; k++) word[k] = fhm[K - 1][k].word; /* RC:229 */
+    for (int k = 0; k < word_number; k++) word[k] = fhm[K - 1][(size_t)k * GHMM_MAX_STREAMS].word; /* RC:229 */
 #else
     for (int k = 0; k < word_number; k++) word[k] = hm[K - 1][(size_t)k * GHMM_MAX_STREAMS].word; /* RF:229 */
 #endif
@@ -304,44 +313,56 @@ int main(int argc, char **argv)
         if ((rc = ghmm_ctx_create(0, NULL, &ctx))) die("GPU context", rc);
 #ifdef GHMM_FULL_COV
         for (int j = 0; j < K; j++) {
-            /* the whole vocabulary in one batched call when the models share M (ghmm_score_full_batch),
-               model by model otherwise (ghmm_score_full); GHMM_LOG_SCORE=1: their log-domain
-               counterparts without the final-state term */
-            ghmm_corpus *corpus;
-            if ((rc = ghmm_corpus_create(ctx, X[j][0], len[j], n_utt, D[j][0], &corpus))) die("corpus", rc);
-            ghmm_fmodel **fm = (ghmm_fmodel **)calloc((size_t)word_number, sizeof(ghmm_fmodel *));
+            /* one stream: the whole vocabulary in one batched call when the models share M
+               (ghmm_score_full_batch), model by model otherwise (ghmm_score_full); several streams: model
+               by model on the product of the streams' densities (ghmm_score_full_streams, RC:760-789);
+               GHMM_LOG_SCORE=1: their log-domain counterparts without the final-state term */
+            const int P = Pj[j];
+            ghmm_corpus *corpus[GHMM_MAX_STREAMS];
+            for (int p = 0; p < P; p++)
+                if ((rc = ghmm_corpus_create(ctx, X[j][p], len[j], n_utt, D[j][p], &corpus[p]))) die("corpus", rc);
+            ghmm_fmodel **fm = (ghmm_fmodel **)calloc((size_t)word_number * GHMM_MAX_STREAMS, sizeof(ghmm_fmodel *));
             double *all = (double *)malloc((size_t)word_number * (size_t)n_utt * sizeof(double));
             if (!fm || !all) die("memory", GHMM_ERR_ALLOC);
             int same = 1;
-            for (int k = 0; k < word_number; k++) {
-                ghmm_host_fmodel *m = &fhm[j][k];
-                if (m->D != D[j][0]) {
-                    printf("model %s has %d coefficients, data has %d \n", m->word, m->D, D[j][0]);
-                    exit(1);
+            for (int k = 0; k < word_number; k++)
+                for (int p = 0; p < P; p++) {
+                    ghmm_host_fmodel *m = &fhm[j][(size_t)k * GHMM_MAX_STREAMS + p];
+                    if (m->D != D[j][p]) {
+                        printf("model %s has %d coefficients, data has %d \n", m->word, m->D, D[j][p]);
+                        exit(1);
+                    }
+                    if (m->M != fhm[j][p].M) same = 0;
+                    ghmm_fmodel **slot = &fm[(size_t)k * GHMM_MAX_STREAMS + p];
+                    if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, slot))) die("model", rc);
+                    if ((rc = ghmm_fmodel_set(ctx, *slot, m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
                 }
-                if (m->M != fhm[j][0].M) same = 0;
-                if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, &fm[k]))) die("model", rc);
-                if ((rc = ghmm_fmodel_set(ctx, fm[k], m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
-            }
-            if (log_score && same) {
-                if ((rc = ghmm_logscore_full_batch(ctx, fm, word_number, corpus, 0, all))) die("scoring", rc);
-            } else if (log_score) {
-                for (int k = 0; k < word_number; k++)
-                    if ((rc = ghmm_logscore_full(ctx, fm[k], corpus, 0, all + (size_t)k * n_utt))) die("scoring", rc);
-            } else if (same) {
-                if ((rc = ghmm_score_full_batch(ctx, fm, word_number, corpus, all))) die("scoring", rc);
+            if (P == 1 && same) {
+                ghmm_fmodel **flat = (ghmm_fmodel **)malloc((size_t)word_number * sizeof(ghmm_fmodel *));
+                if (!flat) die("memory", GHMM_ERR_ALLOC);
+                for (int k = 0; k < word_number; k++) flat[k] = fm[(size_t)k * GHMM_MAX_STREAMS];
+                if ((rc = log_score ? ghmm_logscore_full_batch(ctx, flat, word_number, corpus[0], 0, all)
+                                    : ghmm_score_full_batch(ctx, flat, word_number, corpus[0], all)))
+                    die("scoring", rc);
+                free(flat);
             } else {
-                for (int k = 0; k < word_number; k++)
-                    if ((rc = ghmm_score_full(ctx, fm[k], corpus, all + (size_t)k * n_utt))) die("scoring", rc);
+                /* (one stream: ghmm_logscore_full / ghmm_score_full themselves) */
+                for (int k = 0; k < word_number; k++) {
+                    ghmm_fmodel **mk = &fm[(size_t)k * GHMM_MAX_STREAMS];
+                    double *dst = all + (size_t)k * n_utt;
+                    if ((rc = log_score ? ghmm_logscore_full_streams(ctx, mk, corpus, P, 0, dst)
+                                        : ghmm_score_full_streams(ctx, mk, corpus, P, dst)))
+                        die("scoring", rc);
+                }
             }
             for (int k = 0; k < word_number; k++) {
                 for (int u = 0; u < n_utt; u++)
                     score[(size_t)k * n_utt + u] += coef_model[j] * all[(size_t)k * n_utt + u];
-                ghmm_fmodel_destroy(ctx, fm[k]);
+                for (int p = 0; p < P; p++) ghmm_fmodel_destroy(ctx, fm[(size_t)k * GHMM_MAX_STREAMS + p]);
             }
             free(fm);
             free(all);
-            ghmm_corpus_destroy(ctx, corpus);
+            for (int p = 0; p < P; p++) ghmm_corpus_destroy(ctx, corpus[p]);
         }
 #else
         for (int j = 0; j < K; j++) {
@@ -469,7 +490,8 @@ int main(int argc, char **argv)
     }
     for (int j = 0; j < K; j++) {
 #ifdef GHMM_FULL_COV
-        for (int k = 0; k < word_number; k++) ghmm_host_fmodel_free(&fhm[j][k]);
+        for (int k = 0; k < word_number; k++)
+            for (int p = 0; p < Pj[j]; p++) ghmm_host_fmodel_free(&fhm[j][(size_t)k * GHMM_MAX_STREAMS + p]);
         free(fhm[j]);
 #else
         for (int k = 0; k < word_number; k++)

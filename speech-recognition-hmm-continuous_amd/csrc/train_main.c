@@ -15,10 +15,13 @@
  *
  * Built with -DGHMM_FULL_COV it is bin/hmm-continuous-train-full-fs, the full-covariance trainer
  * (TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c, main TFF:106-378): same argv, usage
- * text, stopping rule and report, one feature stream.  The initial model is built on the host
- * (ghmm_init_model_full) or read with ghmm_hmm_read_full, each iteration is ghmm_estep_full on the
- * GPU and ghmm_mstep_full, and the model is written with ghmm_hmm_write_full (8-byte prefix).
- * P > 1 and GHMM_WORLD > 1 are refused.  GHMM_LOG_TRAIN=1 takes ghmm_estep_full_log for every
+ * text, stopping rule and report.  The initial model is built on the host (ghmm_init_model_full) or
+ * read with ghmm_hmm_read_full_streams, each iteration is ghmm_estep_full on the GPU and
+ * ghmm_mstep_full, and the model is written with ghmm_hmm_write_full_streams (8-byte prefix).
+ * Several feature streams (P > 1, TFF's loop over P lists: the initial model, the mixtures and their
+ * M-step per stream, the recursions on the product of the streams' densities by
+ * ghmm_estep_full_streams) are taken with GHMM_FULL_STREAMS=1 in the environment and refused without
+ * it; the variables below then apply stream by stream.  GHMM_WORLD > 1 is refused.  GHMM_LOG_TRAIN=1 takes ghmm_estep_full_log for every
  * iteration (finite where a frame's linear densities underflow) and says so in one line of output;
  * the report is the same.  GHMM_DEV_MSTEP=1 takes ghmm_mstep_full_dev for every iteration (the
  * M-step stays on the stream) and says so in one line; above that call's cap on M it says so and
@@ -145,97 +148,122 @@ static void write_report(const char *text_file, const char *first_line, const ch
 }
 
 #ifdef GHMM_FULL_COV
-/* main's EM loop of TFF (TFF:202-376) over the utterances already in memory */
-static int train_full(const char *word, int N, int M, int D, const double *X, const int32_t *len, int n_utt,
-                      size_t frames, const char *initial, const char *output, const char *list,
+/* main's EM loop of TFF (TFF:202-376) over the utterances already in memory: P feature streams, each
+   with its own mixtures, one A (TFF:256-342) */
+static int train_full(const char *word, int N, int P, int *M, const int *D, double *const *X, const int32_t *len,
+                      int n_utt, size_t frames, const char *initial, const char *output, const char *const *list,
                       const char *text_file, const char *t_start, int device)
 {
-    ghmm_host_fmodel hfm;
-    memset(&hfm, 0, sizeof hfm);
+    ghmm_host_fmodel hfm[GHMM_MAX_STREAMS];
+    memset(hfm, 0, sizeof hfm);
     int rc;
     /* GHMM_DEV_INIT=1: the initial model on the device (ghmm_fmodel_init); an [initial_model] wins */
-    int dev_init = !initial && env_int("GHMM_DEV_INIT", 0) != 0;
+    const int dev_init = !initial && env_int("GHMM_DEV_INIT", 0) != 0;
     if (initial) {
-        if ((rc = ghmm_hmm_read_full(initial, &hfm))) die("initial model", rc);
-        if (hfm.D != D) {
-            printf("initial model %s has %d coefficients, data has %d \n", initial, hfm.D, D);
+        int Pf = 0;
+        if ((rc = ghmm_hmm_read_full_streams(initial, hfm, P, &Pf))) die("initial model", rc);
+        if (Pf != P) {
+            printf("initial model %s has %d parameters, the command line has %d \n", initial, Pf, P);
             exit(1);
         }
-        N = hfm.N;
-        M = hfm.M;
-    } else if (!dev_init && (rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) {
-        die("creating initial model", rc);
-    }
-    ghmm_ctx *ctx;
-    ghmm_fmodel *fm;
-    ghmm_corpus *corpus;
-    ghmm_stats *stats;
-    if ((rc = ghmm_ctx_create(device, NULL, &ctx))) die("GPU context", rc);
-    if ((rc = ghmm_corpus_create(ctx, X, len, n_utt, D, &corpus))) die("corpus", rc);
-    if ((rc = ghmm_fmodel_create(ctx, N, M, D, &fm))) die("model", rc);
-    if (dev_init) {
-        /* the corpus is uploaded: the initial model from it where it lies; the host copy (the writer's)
-           is fetched.  Above the call's cap on M: the host route, as without the variable */
-        if ((rc = ghmm_fmodel_init(ctx, fm, corpus, NULL)) == GHMM_ERR_UNSUPPORTED) {
-            printf("\r\nInitial model on the host: %s", ghmm_last_error());
-            dev_init = 0;
-            if ((rc = ghmm_init_model_full(X, len, n_utt, N, M, D, &hfm))) die("creating initial model", rc);
-        } else if (rc) {
-            die("creating initial model", rc);
-        } else {
-            printf("\r\nInitial model on the device (GHMM_DEV_INIT)");
-            if ((rc = ghmm_host_fmodel_alloc(&hfm, N, M, D))) die("creating initial model", rc);
-            if ((rc = ghmm_fmodel_get(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
+        N = hfm[0].N;
+        for (int p = 0; p < P; p++) {
+            if (hfm[p].D != D[p]) {
+                printf("initial model %s has %d coefficients, data has %d \n", initial, hfm[p].D, D[p]);
+                exit(1);
+            }
+            M[p] = hfm[p].M;
         }
     }
-    snprintf(hfm.word, sizeof hfm.word, "%s", word);
-    if (!dev_init && (rc = ghmm_fmodel_set(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
-    if ((rc = ghmm_stats_create_full(ctx, N, M, D, &stats))) die("statistics", rc);
+    ghmm_ctx *ctx;
+    ghmm_fmodel *fm[GHMM_MAX_STREAMS];
+    ghmm_corpus *corpus[GHMM_MAX_STREAMS];
+    ghmm_stats *stats[GHMM_MAX_STREAMS];
+    if ((rc = ghmm_ctx_create(device, NULL, &ctx))) die("GPU context", rc);
+    /* creating_initial_model is init_mix_param once per stream (TFF:747-750); every stream gets the same A */
+    for (int p = 0; p < P; p++) {
+        int on_dev = dev_init;
+        if (!initial && !dev_init && (rc = ghmm_init_model_full(X[p], len, n_utt, N, M[p], D[p], &hfm[p])))
+            die("creating initial model", rc);
+        if ((rc = ghmm_corpus_create(ctx, X[p], len, n_utt, D[p], &corpus[p]))) die("corpus", rc);
+        if ((rc = ghmm_fmodel_create(ctx, N, M[p], D[p], &fm[p]))) die("model", rc);
+        if (on_dev) {
+            /* the corpus is uploaded: the initial model from it where it lies; the host copy (the writer's)
+               is fetched.  Above the call's cap on M: the host route, as without the variable */
+            if ((rc = ghmm_fmodel_init(ctx, fm[p], corpus[p], NULL)) == GHMM_ERR_UNSUPPORTED) {
+                printf("\r\nInitial model on the host: %s", ghmm_last_error());
+                on_dev = 0;
+                if ((rc = ghmm_init_model_full(X[p], len, n_utt, N, M[p], D[p], &hfm[p])))
+                    die("creating initial model", rc);
+            } else if (rc) {
+                die("creating initial model", rc);
+            } else {
+                printf("\r\nInitial model on the device (GHMM_DEV_INIT)");
+                if ((rc = ghmm_host_fmodel_alloc(&hfm[p], N, M[p], D[p]))) die("creating initial model", rc);
+                if ((rc = ghmm_fmodel_get(ctx, fm[p], hfm[p].A, hfm[p].c, hfm[p].mean, hfm[p].inv_cov, hfm[p].det)))
+                    die("model", rc);
+            }
+        }
+        snprintf(hfm[p].word, sizeof hfm[p].word, "%s", word);
+        if (!on_dev &&
+            (rc = ghmm_fmodel_set(ctx, fm[p], hfm[p].A, hfm[p].c, hfm[p].mean, hfm[p].inv_cov, hfm[p].det)))
+            die("model", rc);
+        if ((rc = ghmm_stats_create_full(ctx, N, M[p], D[p], &stats[p]))) die("statistics", rc);
+    }
     double lp[2] = {0.0, 0.0};
 
     /* GHMM_LOG_TRAIN=1: every iteration's E-step in the log domain (ghmm_estep_full_log) */
     const int log_train = env_int("GHMM_LOG_TRAIN", 0) != 0;
     printf("\r\nCreating HMM using Forward-Backward algorithm (Baum-Welch)");
     if (log_train) printf("\r\nE-step in the log domain (GHMM_LOG_TRAIN)");
-    /* GHMM_DEV_MSTEP=1: every iteration's M-step on the device (ghmm_mstep_full_dev) */
-    int dev_mstep = env_int("GHMM_DEV_MSTEP", 0) != 0;
-    if (dev_mstep) printf("\r\nM-step on the device (GHMM_DEV_MSTEP)");
+    /* GHMM_DEV_MSTEP=1: every iteration's M-step on the device (ghmm_mstep_full_dev), stream by stream */
+    int dev_mstep[GHMM_MAX_STREAMS];
+    for (int p = 0; p < P; p++) dev_mstep[p] = env_int("GHMM_DEV_MSTEP", 0) != 0;
+    if (dev_mstep[0]) printf("\r\nM-step on the device (GHMM_DEV_MSTEP)");
     double probab, old_probab = 1.0, variation; /* TFF:135-137 */
     int iteration = 0;
     do {
         iteration++;
         printf("\r\nStarting training sequence (%d utterances, %zu frames)", n_utt, frames);
-        if ((rc = log_train ? ghmm_estep_full_log(ctx, fm, corpus, stats) : ghmm_estep_full(ctx, fm, corpus, stats)))
-            die("E-step", rc);
-        if ((rc = ghmm_stats_loglik(ctx, stats, lp))) die("E-step", rc);
+        /* (one stream: ghmm_estep_full or ghmm_estep_full_log itself) */
+        if ((rc = ghmm_estep_full_streams(ctx, fm, corpus, P, stats, log_train))) die("E-step", rc);
+        if ((rc = ghmm_stats_loglik(ctx, stats[0], lp))) die("E-step", rc);
         probab = lp[0];
         printf("\r\nEnding training sequence");
         variation = fabs((old_probab - probab) / old_probab);
         printf("\r\nVerifying Probability: %f > Threshold: %f", variation, THRESHOLD);
         if (variation > THRESHOLD) {
             old_probab = probab;
-            if (dev_mstep && (rc = ghmm_mstep_full_dev(ctx, fm, stats)) == GHMM_ERR_UNSUPPORTED) {
-                printf("\r\nM-step on the host: %s", ghmm_last_error());
-                dev_mstep = 0;
-            } else if (dev_mstep && rc) {
-                die("M-step", rc);
+            /* updating_transition_probab once, updating_mix_param per stream (TFF:313-342): every
+               stream's M-step writes the same A from the same sums */
+            for (int p = 0; p < P; p++) {
+                if (dev_mstep[p] && (rc = ghmm_mstep_full_dev(ctx, fm[p], stats[p])) == GHMM_ERR_UNSUPPORTED) {
+                    printf("\r\nM-step on the host: %s", ghmm_last_error());
+                    dev_mstep[p] = 0;
+                } else if (dev_mstep[p] && rc) {
+                    die("M-step", rc);
+                }
+                if (!dev_mstep[p] && (rc = ghmm_mstep_full(ctx, fm[p], stats[p]))) die("M-step", rc);
             }
-            if (!dev_mstep && (rc = ghmm_mstep_full(ctx, fm, stats))) die("M-step", rc);
         }
     } while (variation > THRESHOLD);
     printf("\r\nFinal Probability = %f\r\n\r\n", variation);
     probab /= (double)n_utt;
 
-    if ((rc = ghmm_fmodel_get(ctx, fm, hfm.A, hfm.c, hfm.mean, hfm.inv_cov, hfm.det))) die("model", rc);
-    if ((rc = ghmm_hmm_write_full(output, &hfm, 8))) die("writing model", rc);
+    for (int p = 0; p < P; p++)
+        if ((rc = ghmm_fmodel_get(ctx, fm[p], hfm[p].A, hfm[p].c, hfm[p].mean, hfm[p].inv_cov, hfm[p].det)))
+            die("model", rc);
+    if ((rc = ghmm_hmm_write_full_streams(output, hfm, P, 8))) die("writing model", rc);
     write_report(text_file,
                  "Continuous HMM created using Forward Backward algorithm. It is considered full covariance matrix. It is considered a final state.",
-                 output, word, N, 1, &M, &list, n_utt, probab, iteration, t_start);
-    ghmm_stats_destroy(ctx, stats);
-    ghmm_fmodel_destroy(ctx, fm);
-    ghmm_corpus_destroy(ctx, corpus);
+                 output, word, N, P, M, list, n_utt, probab, iteration, t_start);
+    for (int p = 0; p < P; p++) {
+        ghmm_stats_destroy(ctx, stats[p]);
+        ghmm_fmodel_destroy(ctx, fm[p]);
+        ghmm_corpus_destroy(ctx, corpus[p]);
+        ghmm_host_fmodel_free(&hfm[p]);
+    }
     ghmm_ctx_destroy(ctx);
-    ghmm_host_fmodel_free(&hfm);
     return 0;
 }
 #endif
@@ -278,8 +306,10 @@ int main(int argc, char **argv)
     const int world = env_int("GHMM_WORLD", 1), rank = env_int("GHMM_RANK", 0);
     const char *comm_id = getenv("GHMM_COMM_ID");
 #ifdef GHMM_FULL_COV
-    if (P != 1) {
-        printf("param_number = %d: the full-covariance trainer takes one feature stream \n", P);
+    /* several feature streams are opt-in for now: GHMM_FULL_STREAMS=1 */
+    if (P != 1 && env_int("GHMM_FULL_STREAMS", 0) == 0) {
+        printf("param_number = %d: the full-covariance trainer takes one feature stream "
+               "(GHMM_FULL_STREAMS=1 takes several) \n", P);
         exit(1);
     }
     if (world != 1) {
@@ -390,8 +420,7 @@ int main(int argc, char **argv)
     }
     free(mine);
 #ifdef GHMM_FULL_COV
-    return train_full(word, N, M[0], D[0], X[0], len, n_utt, frames, initial, output, list[0], text_file,
-                      t_start, device);
+    return train_full(word, N, P, M, D, X, len, n_utt, frames, initial, output, list, text_file, t_start, device);
 #endif
 
     ghmm_host_model hm[GHMM_MAX_STREAMS];

@@ -122,6 +122,11 @@ SYMBOLS = {
     "ghmm_mstep_full": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_mstep_full_dev": (C.c_int, [_vp, _vp, _vp], True),
     "ghmm_fmodel_init": (C.c_int, [_vp, _vp, _vp, _vp], True),
+    "ghmm_estep_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp),
+                                          C.c_int], True),
+    "ghmm_score_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _dp], True),
+    "ghmm_logscore_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp],
+                                   True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -144,6 +149,10 @@ SYMBOLS = {
     "ghmm_host_fmodel_free": (None, [C.POINTER(HostFullModelStruct)], False),
     "ghmm_hmm_read_full": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct)], False),
     "ghmm_hmm_write_full": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct), C.c_int], False),
+    "ghmm_hmm_read_full_streams": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct), C.c_int,
+                                             C.POINTER(C.c_int)], False),
+    "ghmm_hmm_write_full_streams": (C.c_int, [C.c_char_p, C.POINTER(HostFullModelStruct), C.c_int,
+                                              C.c_int], False),
     "ghmm_init_model": (C.c_int, [_dp, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(HostModelStruct)], False),
     "ghmm_init_model_full": (C.c_int, [_dp, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -361,6 +370,23 @@ class HostFullModel:
         lib = host_lib()
         s = self._struct()
         _check(lib.ghmm_hmm_write_full(os.fsencode(path), C.byref(s), len_bytes), lib)
+
+    @staticmethod
+    def read_streams(path, max_streams=8):
+        """A full-covariance model of several feature streams (param_number P): one HostFullModel per
+        stream, each with the common word, N and A (ghmm_hmm_read_full_streams)."""
+        lib = host_lib()
+        arr = (HostFullModelStruct * max_streams)()
+        n = C.c_int()
+        _check(lib.ghmm_hmm_read_full_streams(os.fsencode(path), arr, max_streams, C.byref(n)), lib)
+        return [HostFullModel._from_struct(arr[p], lib) for p in range(n.value)]
+
+    @staticmethod
+    def write_streams(path, hfms, len_bytes=8):
+        """word, N and A are written from hfms[0] (ghmm_hmm_write_full_streams)"""
+        lib = host_lib()
+        arr = (HostFullModelStruct * len(hfms))(*[h._struct() for h in hfms])
+        _check(lib.ghmm_hmm_write_full_streams(os.fsencode(path), arr, len(hfms), len_bytes), lib)
 
 
 def inv_cov_full(cov):
@@ -710,6 +736,34 @@ class Context:
         """the same M-step by HIP kernels on the stream (ghmm_mstep_full_dev): asynchronous, nothing
         is downloaded; the model's parameters equal mstep_full's bit for bit"""
         _check(self.lib.ghmm_mstep_full_dev(self.h, fmodel.h, stats.h), self.lib)
+
+    # ---- the full-covariance calls on several feature streams (param_number P > 1)
+    @staticmethod
+    def _stream_handles(objs):
+        return (_vp * len(objs))(*[o.h for o in objs])
+
+    def estep_full_streams(self, fmodels, corpora, stats, log=False):
+        """TFF's E-step on the product of the streams' densities (ghmm_estep_full_streams), `log`: in
+        the log domain; stats[p] = stream p's stats_full vector; fetch(BUF_B) is the product (log:
+        the sum of the streams' log b)"""
+        _check(self.lib.ghmm_estep_full_streams(self.h, self._stream_handles(fmodels), self._stream_handles(corpora),
+                                                len(fmodels), self._stream_handles(stats), int(bool(log))),
+               self.lib)
+
+    def score_full_streams(self, fmodels, corpora):
+        """score_full on the product of the streams' densities"""
+        out = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_score_full_streams(self.h, self._stream_handles(fmodels), self._stream_handles(corpora),
+                                                len(fmodels), _d(out)), self.lib)
+        return out
+
+    def logscore_full_streams(self, fmodels, corpora, final_state=False):
+        """logscore_full on the sum of the streams' log b"""
+        out = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_logscore_full_streams(self.h, self._stream_handles(fmodels),
+                                                   self._stream_handles(corpora), len(fmodels),
+                                                   int(bool(final_state)), _d(out)), self.lib)
+        return out
 
     def viterbi(self, model, corpus):
         path = np.empty(corpus.frames, dtype=np.int32)
