@@ -221,13 +221,16 @@ int ghmm_forward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c);
  * calc_transition_probab TF:1577-1620 and calc_den_mix_coef TF:1642-1664 */
 int ghmm_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c);
 /* calc_mix_param TF:1691-1727 over every frame, then the ordered reduction of
- * all partial sums into `stats` */
+ * all partial sums into `stats`.  GHMM_ERR_ARG, before anything is launched, unless the emission that
+ * owns the workspace wrote its mixture posteriors there (ghmm_emission with want_post = 1). */
 int ghmm_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *stats);
 
 /* workspace buffers readable with ghmm_fetch (all double, frame-major) */
 enum {
     GHMM_BUF_B = 0,      /* b[F][N]        symbol_probab        TF:107 */
-    GHMM_BUF_POST = 1,   /* post[F][N*M]   gaus_probab_dens     TF:110 */
+    GHMM_BUF_POST = 1,   /* post[F][N*M]   gaus_probab_dens     TF:110; GHMM_ERR_ARG when the emission that
+                          * owns the workspace wrote none (want_post = 0, a score or Viterbi call) or kept
+                          * them per stream (ghmm_estep_streams, n_streams > 1) */
     GHMM_BUF_ALPHA = 2,  /* alpha^[F][N]                        TF:112 */
     GHMM_BUF_BETA = 3,   /* beta^[F][N]                         TF:114; after ghmm_estep it is formed on
                           * this call (the E-step itself only needs gamma and xi) */
@@ -271,8 +274,34 @@ int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghm
  * mixtures and posteriors.  models[p] / corpora[p] / stats[p] = stream p: same states, same
  * utterances and lengths, own M_p and D_p; the transitions are models[0]'s.  stats[p] has the
  * single-stream layout (the common sums are written into every one), so that ghmm_mstep(models[p],
- * stats[p]) for every p is the M-step (TF:332-346: all of them write the same A).  The product
- * b is what GHMM_BUF_B then holds.  GHMM_OPT_ROBUST is not available with several streams. */
+ * stats[p]) for every p is the M-step (TF:332-346: all of them write the same A).
+ *   1 <= n_streams <= GHMM_MAX_STREAMS;  n_streams == 1 is the single-stream call itself (ghmm_estep,
+ *   ghmm_score): the same bits.
+ * The product: every stream's emission is the launch ghmm_emission makes for that stream alone, stream 0
+ * into b, every later stream into a buffer of its own that one IEEE multiply per entry folds into b,
+ * the earlier streams' product on the left: b = ((b^0 * b^1) * b^2)..., which is the reference's
+ * `product = 1.0; product *= ...` since 1.0 * b^0 == b^0.  Zeros, subnormal values, NaN and inf
+ * propagate as the multiplication gives them; a frame whose product is 0 in every state ends its
+ * utterance as in the reference (c_t = 1/0, log P NaN, NaN statistics).
+ * Asynchrony, reproducibility (a second identical call repeats every vector bit for bit), GHMM_OPT_DELTA,
+ * GHMM_OPT_PARTIALS, GHMM_OPT_KERNELS and GHMM_OPT_VEC_STATS are the single-stream calls'; utterances are
+ * taken again in the reference's order as there (GHMM_OPT_REFORDER_COUNT).
+ * The common sums (num_a, den_a, den_c, loglik, n_utt) are reduced once per stream from the same partial
+ * sums in the same order: they are the same bits in every stream's vector, and every stream's ghmm_mstep
+ * writes the same A bit for bit.
+ * Afterwards GHMM_BUF_B holds the product and GHMM_BUF_ALPHA / _BETA / _SCALE / _GAMMA / _LOGLIK are as
+ * after the single-stream call on it.  The workspace belongs to stream 0's (model, corpus) pair:
+ * ghmm_forward and ghmm_backward on that pair run on the product.  The mixture posteriors lie in one
+ * buffer per stream that ghmm_fetch does not serve: ghmm_fetch / ghmm_fetch_range(GHMM_BUF_POST) and
+ * ghmm_accumulate return GHMM_ERR_ARG until a ghmm_emission(want_post = 1) or ghmm_estep has written
+ * posteriors of its own (the same holds after ghmm_emission(want_post = 0), ghmm_score, ghmm_score_batch
+ * and ghmm_viterbi: the workspace never serves the posteriors of an earlier emission).
+ * Refusals, each before anything is launched or written: GHMM_OPT_ROBUST set with n_streams > 1 gives
+ * GHMM_ERR_UNSUPPORTED; a null array or entry, n_streams outside the range, streams that differ in N, in
+ * the utterance count or in a length, a corpus of another D than its model, or a statistics vector that
+ * is full-covariance or not of its stream's shape gives GHMM_ERR_ARG.
+ * Out of scope: Viterbi over several streams, and ghmm_score_batch for several streams (a recogniser
+ * scores model by model when P > 1). */
 int ghmm_estep_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
                        int n_streams, ghmm_stats *const *stats);
 /* forward score per utterance of a P-stream model (RF:349-366) */

@@ -199,6 +199,7 @@ static int run_emission_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_co
         ws_disown(ctx);
         ctx->em_c = c;
         ctx->b_is_log = mode == FC_LOG || mode == FC_LOGPOST;
+        ctx->post_valid = !stream_post && (mode == FC_POST || mode == FC_LOGPOST);
     }
     if (c->F == 0) return GHMM_OK;
     kscope ks(ctx, GHMM_K_EMISSION);
@@ -658,6 +659,7 @@ extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, 
     ctx->U = c->U;
     ctx->N = N;
     ctx->G = G;
+    ctx->post_valid = true; // the last classification's one-hot rows, which ghmm_fetch serves
     fm->rec.banded = true; // init_transition_probab's A: j = i or i + 1
 
     // one classification of every frame against n_cells cells per state, the cells' sums into part;

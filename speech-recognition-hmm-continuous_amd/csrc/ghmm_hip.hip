@@ -135,6 +135,11 @@ struct ghmm_ctx {
     const ghmm_model *em_m = nullptr;
     const ghmm_corpus *em_c = nullptr;
     int em_epoch = -1;
+    // ctx->post holds the mixture posteriors of that emission (or what a full-covariance call put
+    // there for ghmm_fetch): only then do ghmm_accumulate and ghmm_fetch(GHMM_BUF_POST) read it.
+    // The buffer is only ever grown, so without this an emission that wrote no posteriors, or wrote
+    // them into post_s[p], would leave an earlier call's, of another shape, to be read.
+    bool post_valid = false;
     // kernels whose dynamic-LDS limit has been raised on THIS context's device (the attribute
     // is per device and per function; nothing process-wide, nothing shared between threads)
     std::vector<const void *> lds_fns;
@@ -1100,6 +1105,7 @@ static void ws_disown(ghmm_ctx *ctx)
     ctx->em_m = nullptr;
     ctx->em_c = nullptr;
     ctx->em_epoch = -1;
+    ctx->post_valid = false;
     ctx->own_bwd_done = false;
     ctx->beta_valid = false;
     ctx->loglik_pieces = false;
@@ -1154,6 +1160,11 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
     ctx->em_m = m;
     ctx->em_c = c;
     ctx->em_epoch = m->epoch;
+    // posteriors written into ctx->post's own buffer are the workspace's; streams_emission points
+    // ctx->post at post_s[p], which ghmm_fetch and ghmm_accumulate do not serve
+    ctx->post_valid = want_post;
+    for (const double *ps : ctx->post_s)
+        if (ps && ps == ctx->post) ctx->post_valid = false;
     if (c->F == 0) return GHMM_OK;
     const long long blocks = (c->F + WAVE - 1) / WAVE;
     const size_t lds = (size_t)WAVE * (m->D | 1) * sizeof(double);
@@ -1756,7 +1767,7 @@ extern "C" int ghmm_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghm
     int rc = use(ctx);
     if (rc || (rc = check_pair(m, c)) || (rc = need_emission(ctx, m, c)) || (rc = check_stats(m, s)))
         return rc;
-    if (!ctx->gamma || !ctx->post) {
+    if (!ctx->gamma || !ctx->post || !ctx->post_valid) {
         ghmm_set_error("call ghmm_emission(want_post=1), ghmm_forward and ghmm_backward first");
         return GHMM_ERR_ARG;
     }
@@ -1773,7 +1784,15 @@ static int fetch_impl(ghmm_ctx *ctx, int which, bool whole, size_t first, double
     size_t F = (size_t)ctx->F, N = (size_t)ctx->N, G = (size_t)ctx->G, U = (size_t)ctx->U;
     switch (which) {
     case GHMM_BUF_B: src = ctx->b; have = F * N; break;
-    case GHMM_BUF_POST: src = ctx->post; have = F * G; break;
+    case GHMM_BUF_POST:
+        if (!ctx->post_valid) {
+            ghmm_set_error("the workspace holds no mixture posteriors: the last emission wrote none "
+                           "(want_post = 0, a score call) or was a call on several feature streams");
+            return GHMM_ERR_ARG;
+        }
+        src = ctx->post;
+        have = F * G;
+        break;
     case GHMM_BUF_ALPHA: src = ctx->alpha; have = F * N; break;
     case GHMM_BUF_BETA:
         if (!ctx->beta_valid && ctx->beta) {
@@ -1901,6 +1920,7 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
     ARG_CHECK(c->U > 0 && c->F > 0, "empty corpus");
     const int N = m->N, M = m->M, D = m->D, G = N * M;
     if ((rc = ws_frames(ctx, m, c, true)) || (rc = ws_fb(ctx, m, c))) return rc;
+    ctx->post_valid = false; // k_init_classify's one-hot rows go there: no emission's posteriors any more
     // the utterance-level partials feed k_reduce_all too; they carry nothing here
     HIP_TRY(hipMemsetAsync(ctx->part_xi, 0, (size_t)c->U * N * (MAX_DELTA + 1) * 8, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->part_dena, 0, (size_t)c->U * N * 8, ctx->stream));
@@ -2199,7 +2219,7 @@ static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpu
         }
     }
     ctx->b = b_all;
-    ctx->post = post_own;
+    ctx->post = post_own; // (not written: run_emission has cleared post_valid)
     // the product belongs to stream 0's (model, corpus) pair as far as the row API is concerned
     ctx->em_m = models[0];
     ctx->em_c = corpora[0];

@@ -22,17 +22,12 @@ import oracle_lib as O
 from conftest import GOLDEN
 from _load import PKG_DIR
 from fullcov_support import RTOL, assert_close  # noqa: F401  (profiles/ call them through this module)
+from streams_util import (_estep_streams_vs_oracle, _golden_streams, _stream_data,  # noqa: F401  (the same)
+                          assert_frames, synth_case)
 
 pytestmark = pytest.mark.gpu
 
 NORTH_STAR_RTOL = 1e-5  # the bar
-
-
-def assert_frames(got, ref, what, rtol=RTOL):
-    """Per-frame arrays: every entry against the largest of its own frame (assert_close, rows)."""
-    ref = np.asarray(ref)
-    got = np.asarray(got).reshape(ref.shape)
-    assert_close(got, ref, rtol=rtol, what=what, rows=True)
 
 
 @pytest.fixture(scope="module")
@@ -247,17 +242,6 @@ def test_recognition_command_line(G, whole, tmp_path):
 
 
 # ------------------------------------------------------------ oracle, seeded
-
-def synth_case(G, N, M, D, lens, perturb=0.05, first=0, dense_A=False, seed=3):
-    mean, std = G.synth_truth(N, M, D)
-    X = G.synth_utterances(mean, std, lens, first_utt=first)
-    hm = G.synth_start_model(mean, std, perturb)
-    if dense_A:
-        rng = np.random.default_rng(seed)
-        A = rng.random((N, N)) + 0.05
-        hm.A[:] = A / A.sum(1, keepdims=True)
-    return hm, X, np.asarray(lens, dtype=np.int32)
-
 
 @pytest.mark.parametrize("N,M,D,lens,dense", [
     (10, 8, 39, [300, 211, 128, 77, 64, 5, 1, 2, 33, 500], False),   # ragged, T < N, T = 1
@@ -1585,45 +1569,6 @@ def test_config5_full_size_properties(G, ctx):
 @pytest.fixture(scope="module")
 def streams():
     return json.load(open(os.path.join(GOLDEN, "streams_p2.json")))
-
-
-def _stream_data(G, streams, idx):
-    from streams_util import second_stream
-    Xs = [G.perfil_read(os.path.join(GOLDEN, "perfil", streams["mean_list"][k])) for k in idx]
-    lens = np.array([len(x) for x in Xs], dtype=np.int32)
-    return [np.concatenate(Xs), np.concatenate([second_stream(x, streams["D2"]) for x in Xs])], lens
-
-
-def _golden_streams(G, rec, word=""):
-    m = rec["model"]
-    return [G.HostModel(m["A"], s["c"], s["mean"], s["inv_var"], s["det"], word=word) for s in m["streams"]]
-
-
-def _estep_streams_vs_oracle(G, ctx, hms, Xs, lens, tag):
-    models = [ctx.model(h) for h in hms]
-    corpora = [ctx.corpus(x, lens) for x in Xs]
-    stats = [ctx.stats(h.N, h.M, h.D) for h in hms]
-    ctx.estep_streams(models, corpora, stats)
-    ref_stats, ref_b, ref_ll = O.estep_streams(hms, Xs, lens)
-    F, N = int(np.sum(lens)), hms[0].N
-    assert_frames(ctx.fetch(G.BUF_B, (F, N)), ref_b, tag + " product b")
-    assert_close(ctx.fetch(G.BUF_LOGLIK, (len(lens),)), ref_ll, what=tag + " loglik")
-    for p, (s, r) in enumerate(zip(stats, ref_stats)):
-        got, ref = G.split_stats(s.download(), N, hms[p].M, hms[p].D), G.split_stats(r, N, hms[p].M, hms[p].D)
-        for k in ref:
-            assert_close(got[k], ref[k], what=f"{tag} stream {p} stats.{k}")
-    # M-step per stream (TF:332-346): every stream's call writes the same A
-    for p in range(len(hms)):
-        ctx.mstep(models[p], stats[p])
-        new, ref_new = models[p].get(), O.mstep(hms[p], ref_stats[p])
-        for nm, a, b in zip(("A", "c", "mean", "inv_var", "det"), new.arrays(), ref_new.arrays()):
-            assert_close(a, b, rtol=1e-7, what=f"{tag} stream {p} mstep.{nm}")
-    assert_close(ctx.score_streams(models, corpora),
-                 [O.score_streams([m.get() for m in models], [x[o:o + t] for x in Xs])
-                  for o, t in zip(np.concatenate([[0], np.cumsum(lens)[:-1]]), lens)],
-                 rtol=1e-9, what=tag + " score after the M-step")
-    for o in models + corpora + stats:
-        o.close()
 
 
 def test_streams_estep_against_oracle(G, ctx, streams):
