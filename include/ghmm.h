@@ -300,8 +300,9 @@ int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghm
  * GHMM_ERR_UNSUPPORTED; a null array or entry, n_streams outside the range, streams that differ in N, in
  * the utterance count or in a length, a corpus of another D than its model, or a statistics vector that
  * is full-covariance or not of its stream's shape gives GHMM_ERR_ARG.
- * Out of scope: Viterbi over several streams, and ghmm_score_batch for several streams (a recogniser
- * scores model by model when P > 1). */
+ * Viterbi and the batched vocabulary calls on several streams exist for the full-covariance models only:
+ * see "several-stream vocabularies" below (ghmm_viterbi_full_streams, ghmm_*_full_streams_batch,
+ * ghmm_recognise_full_streams). */
 int ghmm_estep_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
                        int n_streams, ghmm_stats *const *stats);
 /* forward score per utterance of a P-stream model (RF:349-366) */
@@ -520,8 +521,8 @@ int ghmm_mstep_full_dev(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *stats);
  * array or entry, n_streams outside the range, streams that differ in N, in the utterance count or in
  * a length, a corpus of another D than its model, or a statistics vector that is diagonal or not of its
  * stream's shape gives GHMM_ERR_ARG.
- * Out of scope: Viterbi over several streams, and the batched vocabulary calls (*_full_batch) for
- * several streams; a recogniser scores model by model when P > 1, as the diagonal one does. */
+ * Viterbi over several streams and the batched vocabulary calls (*_full_batch) for several streams are
+ * in the section "several-stream vocabularies" below. */
 /* One E-step over the whole corpus.  stats[p] is a ghmm_stats_create_full(N, M_p, D_p) vector.
  * log_domain == 0: every stream's emission as in ghmm_estep_full, ghmm_estep_full's recursion launches
  * on the product, then calc_mix_param and the reductions once per stream with that stream's
@@ -538,6 +539,59 @@ int ghmm_score_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corp
  * where the linear product underflows to 0.  Synchronises. */
 int ghmm_logscore_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
                                int n_streams, int final_state, double *loglik_host);
+
+/* ------------- several-stream vocabularies: Viterbi, batched scoring and word decoding (full-covariance) */
+
+/* ghmm_viterbi_full on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) as
+ * ghmm_logscore_full_streams forms it, with models[0]'s log A: path_host[F], score_host[U].
+ * n_streams == 1 is ghmm_viterbi_full itself, the same bits.  Afterwards GHMM_BUF_B holds the summed
+ * log b[F][N].  The checks and refusals are those of the three calls above, and a null destination with
+ * U > 0 gives GHMM_ERR_ARG; U = 0 touches nothing.  Synchronises. */
+int ghmm_viterbi_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
+                              int n_streams, int32_t *path_host, double *score_host);
+/* A vocabulary of n_models words on n_streams streams in one pass, for the four calls below:
+ *   models[k * n_streams + p] = stream p of word k;  corpora[p] = stream p of the utterances;
+ *   the streams of one word have the same N; for every stream p all words share M_p and D_p;
+ *   the corpora have the same utterance count and lengths, corpora[p] has D_p coefficients.
+ * Per stream one gather of the words' Gaussians into that stream's concatenated vocabulary (kept in the
+ * context between calls, rebuilt when its shape changes) and one emission launch over it, stream 0
+ * plain, every later stream folded into the same b[F][NS] (NS = the sum of the words' N) as in the
+ * calls above; then the one lattice launch of the single-stream *_full_batch call on word k's columns
+ * and stream 0's A or log A: 2 n_streams + 1 launches and one wait for the stream.
+ * out[k*U + u] is bit for bit what the matching call above gives word k alone (ghmm_score_full_streams,
+ * ghmm_logscore_full_streams, ghmm_viterbi_full_streams' score).  n_streams == 1 is the *_full_batch
+ * call, the same bits and the same cached vocabulary.  Afterwards GHMM_BUF_B holds the product (or the
+ * sum of logs) over [F][NS]; the diagonal row API refuses the workspace.  U = 0 touches nothing.
+ * Refusals, each before anything is launched or written.  GHMM_ERR_ARG: a null array or entry,
+ * n_models < 1, n_streams outside 1..GHMM_MAX_STREAMS, a null destination with U > 0, streams of one
+ * word that differ in N, corpora that differ in the utterance count or in a length, a corpus whose D is
+ * not its stream's.  GHMM_ERR_UNSUPPORTED: GHMM_OPT_ROBUST set; words that differ in M_p or D_p for
+ * some stream p. */
+int ghmm_score_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                  ghmm_corpus *const *corpora, int n_streams, double *loglik_host);
+int ghmm_logscore_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                     ghmm_corpus *const *corpora, int n_streams, int final_state,
+                                     double *loglik_host);
+int ghmm_viterbi_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                    ghmm_corpus *const *corpora, int n_streams, double *score_host);
+/* Which word was it, and how does it align (n_streams >= 1): ghmm_viterbi_full_streams_batch's score
+ * table, every utterance's winning word picked on the device, and the winner's lattice run again with
+ * back-pointers on the log b already in the workspace, all enqueued without a host round trip and
+ * ended by one wait for the stream.
+ *   score_host[n_models*U]  the batch call's table, bit for bit
+ *   word_host[U]            the winner: best = 0; for k = 1 .. n_models-1 in order, k takes over if
+ *                           score[k] > score[best], or if score[best] is NaN and score[k] is not.  Ties
+ *                           go to the lowest word, a NaN never beats a number, and all NaN or all -inf
+ *                           gives word 0
+ *   path_host[F]            over utterance u's frames, bit for bit ghmm_viterbi_full_streams' path of
+ *                           word word_host[u]
+ * T = 0 scores 0 under every word, gives word 0 and no path entries.  U = 0 touches nothing.  The
+ * vocabulary layout, GHMM_BUF_B afterwards and the refusals are the batch calls' (all three destinations
+ * are needed when U > 0).  The two extra launches count under GHMM_K_VITERBI.  A second identical call
+ * repeats every byte. */
+int ghmm_recognise_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                ghmm_corpus *const *corpora, int n_streams, int32_t *word_host,
+                                int32_t *path_host, double *score_host);
 
 /* -------------------------------------- several GPUs: the one collective */
 

@@ -85,6 +85,10 @@ struct ghmm_ctx {
     char *bt_tab = nullptr;
     // ghmm_score_full_batch: the same for the full-covariance vocabulary (the log P go to bt_ll)
     ghmm_fmodel *fbt_cat = nullptr;
+    // the *_full_streams_batch calls: fbt_cat is stream 0's vocabulary, fbt_cat_s[p] stream p's (p >= 1)
+    ghmm_fmodel *fbt_cat_s[GHMM_MAX_STREAMS] = {};
+    int *best_word = nullptr; // ghmm_recognise_full_streams: every utterance's winning word
+    size_t cap_best_word = 0;
     char *fbt_tab = nullptr;
     size_t cap_fbt_tab = 0;
     double *bt_scale = nullptr, *bt_sinv = nullptr, *bt_ll = nullptr;
@@ -413,7 +417,12 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
         ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
         ctx->fbt_cat = nullptr;
     }
-    void *bufs[] = {ctx->fbt_tab, ctx->bt_tab, ctx->bt_scale, ctx->bt_sinv, ctx->bt_ll, ctx->b_alloc, ctx->post,      ctx->alpha,     ctx->beta,    ctx->gamma,
+    for (ghmm_fmodel *&cat : ctx->fbt_cat_s)
+        if (cat) {
+            ghmm_fmodel_destroy(ctx, cat);
+            cat = nullptr;
+        }
+    void *bufs[] = {ctx->best_word, ctx->fbt_tab, ctx->bt_tab, ctx->bt_scale, ctx->bt_sinv, ctx->bt_ll, ctx->b_alloc, ctx->post,      ctx->alpha,     ctx->beta,    ctx->gamma,
                     ctx->scale,   ctx->lognorm,   ctx->loglik,    ctx->part_xi, ctx->part_dena,
                     ctx->part_denc, ctx->part_mu, ctx->part_var,  ctx->psi,     ctx->path,
                     ctx->part_m,  ctx->sinv,      ctx->sink,      ctx->wrow,    ctx->sb,
@@ -2270,7 +2279,8 @@ extern "C" int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
 }
 
 // ------------------------------------------------ a vocabulary in one pass
-// What the batch calls share, diagonal (ghmm_score_batch) and full-covariance (ghmm_fullhost.hpp).
+// ghmm_score_batch's helpers; the full-covariance batch calls (ghmm_fullhost.hpp: fvocab_begin builds the
+// same tables for several feature streams) share vocab_scores_out.
 
 // every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
 template <class MODEL>

@@ -1647,6 +1647,40 @@ __device__ __forceinline__ int psi_byte(const uint4 r, int s)
     return (int)((w >> ((s & 3) * 8)) & 0xffu);
 }
 
+// the path of one utterance from its back-pointer rows ps[T][L], from state N-1 (one lane)
+template <int L>
+__device__ __forceinline__ void viterbi_trace(int N, int T, const unsigned char *__restrict__ ps,
+                                              unsigned char *__restrict__ pu)
+{
+    int s = N - 1;
+    if (L == 16) {
+        // whole 16-byte rows, read ahead of the chain (their addresses do not depend on it):
+        // the chain itself is a byte select in registers
+        constexpr int PB = 8;
+        const uint4 *rows = (const uint4 *)ps;
+        int t = T - 1;
+        for (; t - PB + 1 >= 0; t -= PB) {
+            uint4 r[PB];
+#pragma unroll
+            for (int k = 0; k < PB; k++) r[k] = rows[t - k];
+#pragma unroll
+            for (int k = 0; k < PB; k++) {
+                pu[t - k] = (unsigned char)s;
+                s = psi_byte(r[k], s);
+            }
+        }
+        for (; t >= 0; t--) {
+            pu[t] = (unsigned char)s;
+            s = psi_byte(rows[t], s);
+        }
+    } else {
+        for (int t = T - 1; t >= 0; t--) {
+            pu[t] = (unsigned char)s;
+            s = ps[(size_t)t * L + s];
+        }
+    }
+}
+
 template <int L>
 __global__ void __launch_bounds__(WAVE)
 k_viterbi(int N, int U, const double *__restrict__ logA, const double *__restrict__ logb,
@@ -1678,34 +1712,7 @@ k_viterbi(int N, int U, const double *__restrict__ logA, const double *__restric
     __threadfence_block();
     if (j != 0) return;
     score[u] = sc;
-    int s = N - 1;
-    unsigned char *pu = path + f0;
-    if (L == 16) {
-        // whole 16-byte rows, read ahead of the chain (their addresses do not depend on it):
-        // the chain itself is a byte select in registers
-        constexpr int PB = 8;
-        const uint4 *rows = (const uint4 *)ps;
-        int t = T - 1;
-        for (; t - PB + 1 >= 0; t -= PB) {
-            uint4 r[PB];
-#pragma unroll
-            for (int k = 0; k < PB; k++) r[k] = rows[t - k];
-#pragma unroll
-            for (int k = 0; k < PB; k++) {
-                pu[t - k] = (unsigned char)s;
-                s = psi_byte(r[k], s);
-            }
-        }
-        for (; t >= 0; t--) {
-            pu[t] = (unsigned char)s;
-            s = psi_byte(rows[t], s);
-        }
-    } else {
-        for (int t = T - 1; t >= 0; t--) {
-            pu[t] = (unsigned char)s;
-            s = ps[(size_t)t * L + s];
-        }
-    }
+    viterbi_trace<L>(N, T, ps, path + f0);
 }
 
 // ghmm_viterbi_full_batch: k_viterbi's lattice for every (model, utterance) pair of a concatenated
@@ -1745,6 +1752,68 @@ k_viterbi_multi(int U, int NS, const fwd_model *__restrict__ tab, const double *
     else d = viterbi_run<L, false, false>(N, T, j, act, logA, lb, NS, nullptr, snk);
     const double sc = __shfl(d, N - 1, L);
     if (j == 0) score[(size_t)k * U + u] = sc;
+}
+
+// ghmm_recognise_full_streams: every utterance's winning word from k_viterbi_multi's table
+// score[K][U], one thread per utterance.  The rule (include/ghmm.h): best = 0; k = 1 .. K-1 in order
+// takes over when score[k] > score[best], or when score[best] is NaN and score[k] is not.  Ties stay
+// with the lowest word, a NaN never beats a number, all NaN or all -inf is word 0.
+__global__ void __launch_bounds__(256)
+k_vocab_best(int K, int U, const double *__restrict__ score, int *__restrict__ word)
+{
+    const int u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= U) return;
+    int best = 0;
+    double sb = score[u];
+    for (int k = 1; k < K; k++) {
+        const double s = score[(size_t)k * U + u];
+        if (s > sb || (sb != sb && s == s)) {
+            best = k;
+            sb = s;
+        }
+    }
+    word[u] = best;
+}
+
+// ... and the winner's lattice again with back-pointers, on the log b[F][NS] that k_viterbi_multi
+// ran on: k_viterbi's body (the same viterbi_run, the same back-trace) laid out as k_viterbi_multi,
+// blockIdx.y = word model.  A group whose utterance was won by another word leaves at once, so the
+// groups that stay in a wave all hold word blockIdx.y: N, log A and with them the banded / dense vote
+// are wave-uniform exactly as in k_viterbi, and each utterance is written by one group of one block.
+// path[f0 .. f0 + T) is bit for bit what k_viterbi gives word[u] alone (viterbi_run's arithmetic and
+// its back-pointers do not depend on L); the score is already in k_viterbi_multi's table.
+template <int L>
+__global__ void __launch_bounds__(WAVE)
+k_viterbi_pick(int U, int NS, const fwd_model *__restrict__ tab, const double *__restrict__ logb,
+               const long long *__restrict__ off, const int *__restrict__ word,
+               unsigned char *__restrict__ psi, unsigned char *__restrict__ path, double *__restrict__ sink,
+               const int *__restrict__ order)
+{
+    const int slot = blockIdx.x * (WAVE / L) + threadIdx.x / L;
+    const int j = threadIdx.x % L;
+    const int k = blockIdx.y;
+    if (slot >= U) return;
+    const int u = order[slot];
+    if (word[u] != k) return;
+    const fwd_model mk = tab[k];
+    const int N = mk.N;
+    const double *logA = mk.A;
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    if (T <= 0) return;
+    const bool act = j < N;
+    bool offband = false;
+    for (int i = 0; i < N; i++)
+        offband |= act && (logA[i * N + j] != -INFINITY && i != j && i != j - 1);
+    const bool banded = !__any(offband);
+    unsigned char *ps = psi + (size_t)f0 * L; // rows of L bytes
+    double *snk = wave_sink(sink);
+    const double *lb = logb + f0 * NS + mk.bo;
+    if (banded) (void)viterbi_run<L, true>(N, T, j, act, logA, lb, NS, ps, snk);
+    else (void)viterbi_run<L, false>(N, T, j, act, logA, lb, NS, ps, snk);
+    __threadfence_block();
+    if (j != 0) return;
+    viterbi_trace<L>(N, T, ps, path + f0);
 }
 
 // ------------------------------------------------------------------ log-domain forward

@@ -19,13 +19,14 @@
  * Built with -DGHMM_FULL_COV this is recognition-continuous-test-full-fs, the full-covariance
  * recogniser RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c: the same
  * argv, lists and bookkeeping (RC:283-412), its usage text and header (RC:1019-1033), models read
- * with ghmm_hmm_read_full_streams (RC:591-707) and scored with ghmm_score_full_batch, whose
- * log P has no final-state term (calc_probability, RC:822-836); a set whose models hold several
- * feature streams is scored model by model with ghmm_score_full_streams (GHMM_LOG_SCORE=1:
- * ghmm_logscore_full_streams).  With GHMM_LOG_SCORE=1 in the
- * environment that program scores in the log domain instead (ghmm_logscore_full_batch, final_state
- * = 0: the same quantity, finite where the linear densities underflow) and says so in the report's
- * second line; without the variable nothing changes.
+ * with ghmm_hmm_read_full_streams (RC:591-707) and scored with ghmm_score_full_streams_batch, whose
+ * log P has no final-state term (calc_probability, RC:822-836): the whole vocabulary in one pass, on
+ * one feature stream (where it is ghmm_score_full_batch) or several, as long as the words agree in
+ * every stream's M; a set whose words do not is scored model by model with ghmm_score_full_streams.
+ * With GHMM_LOG_SCORE=1 in the environment that program scores in the log domain instead
+ * (ghmm_logscore_full_streams_batch / ghmm_logscore_full_streams, final_state = 0: the same quantity,
+ * finite where the linear densities underflow) and says so in the report's second line; without the
+ * variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -313,10 +314,10 @@ int main(int argc, char **argv)
         if ((rc = ghmm_ctx_create(0, NULL, &ctx))) die("GPU context", rc);
 #ifdef GHMM_FULL_COV
         for (int j = 0; j < K; j++) {
-            /* one stream: the whole vocabulary in one batched call when the models share M
-               (ghmm_score_full_batch), model by model otherwise (ghmm_score_full); several streams: model
-               by model on the product of the streams' densities (ghmm_score_full_streams, RC:760-789);
-               GHMM_LOG_SCORE=1: their log-domain counterparts without the final-state term */
+            /* the whole vocabulary in one batched call on the product of the streams' densities (RC:760-789)
+               when the words share every stream's M (ghmm_score_full_streams_batch; with one stream that is
+               ghmm_score_full_batch), model by model otherwise (ghmm_score_full_streams; with one stream
+               ghmm_score_full); GHMM_LOG_SCORE=1: their log-domain counterparts without the final-state term */
             const int P = Pj[j];
             ghmm_corpus *corpus[GHMM_MAX_STREAMS];
             for (int p = 0; p < P; p++)
@@ -337,12 +338,14 @@ int main(int argc, char **argv)
                     if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, slot))) die("model", rc);
                     if ((rc = ghmm_fmodel_set(ctx, *slot, m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
                 }
-            if (P == 1 && same) {
-                ghmm_fmodel **flat = (ghmm_fmodel **)malloc((size_t)word_number * sizeof(ghmm_fmodel *));
+            if (same) {
+                /* flat[k * P + p]: the layout of the batched calls (P == 1: ghmm_score_full_batch's) */
+                ghmm_fmodel **flat = (ghmm_fmodel **)malloc((size_t)word_number * P * sizeof(ghmm_fmodel *));
                 if (!flat) die("memory", GHMM_ERR_ALLOC);
-                for (int k = 0; k < word_number; k++) flat[k] = fm[(size_t)k * GHMM_MAX_STREAMS];
-                if ((rc = log_score ? ghmm_logscore_full_batch(ctx, flat, word_number, corpus[0], 0, all)
-                                    : ghmm_score_full_batch(ctx, flat, word_number, corpus[0], all)))
+                for (int k = 0; k < word_number; k++)
+                    for (int p = 0; p < P; p++) flat[(size_t)k * P + p] = fm[(size_t)k * GHMM_MAX_STREAMS + p];
+                if ((rc = log_score ? ghmm_logscore_full_streams_batch(ctx, flat, word_number, corpus, P, 0, all)
+                                    : ghmm_score_full_streams_batch(ctx, flat, word_number, corpus, P, all)))
                     die("scoring", rc);
                 free(flat);
             } else {

@@ -127,6 +127,15 @@ SYMBOLS = {
     "ghmm_score_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _dp], True),
     "ghmm_logscore_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp],
                                    True),
+    "ghmm_viterbi_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _ip, _dp], True),
+    "ghmm_score_full_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp],
+                                      True),
+    "ghmm_logscore_full_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int,
+                                                   C.c_int, _dp], True),
+    "ghmm_viterbi_full_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp],
+                                        True),
+    "ghmm_recognise_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
+                                              _dp], True),
     "ghmm_perfil_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(_dp)], False),
     "ghmm_perfil_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp], False),
@@ -764,6 +773,59 @@ class Context:
                                                    self._stream_handles(corpora), len(fmodels),
                                                    int(bool(final_state)), _d(out)), self.lib)
         return out
+
+    # ---- several-stream vocabularies: vocab[k][p] = stream p of word k
+    def viterbi_full_streams(self, fmodels, corpora):
+        """viterbi_full on the sum of the streams' log b: (path, score)"""
+        path = np.empty(corpora[0].frames, dtype=np.int32)
+        score = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_full_streams(self.h, self._stream_handles(fmodels),
+                                                  self._stream_handles(corpora), len(fmodels),
+                                                  path.ctypes.data_as(_ip), _d(score)), self.lib)
+        return path, score
+
+    @staticmethod
+    def _vocab_handles(vocab):
+        P = len(vocab[0])
+        if any(len(w) != P for w in vocab):
+            raise ValueError("every word of the vocabulary needs one model per stream")
+        return (_vp * (len(vocab) * P))(*[m.h for w in vocab for m in w])
+
+    def score_full_streams_batch(self, vocab, corpora):
+        """out[k, u] = score_full_streams of word k (bit for bit), the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_score_full_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                      self._stream_handles(corpora), len(corpora), _d(out)),
+               self.lib)
+        return out
+
+    def logscore_full_streams_batch(self, vocab, corpora, final_state=False):
+        """out[k, u] = logscore_full_streams of word k (bit for bit), the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_logscore_full_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                         self._stream_handles(corpora), len(corpora),
+                                                         int(bool(final_state)), _d(out)), self.lib)
+        return out
+
+    def viterbi_full_streams_batch(self, vocab, corpora):
+        """out[k, u] = viterbi_full_streams' score of word k (bit for bit), the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_full_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                        self._stream_handles(corpora), len(corpora), _d(out)),
+               self.lib)
+        return out
+
+    def recognise_full_streams(self, vocab, corpora):
+        """(word[U], path[F], score[K, U]): every utterance's best word by Viterbi score (ties: the
+        lowest word), that word's path over the utterance's frames, and the whole score table"""
+        word = np.empty(corpora[0].n_utt, dtype=np.int32)
+        path = np.empty(corpora[0].frames, dtype=np.int32)
+        score = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_recognise_full_streams(self.h, self._vocab_handles(vocab), len(vocab),
+                                                    self._stream_handles(corpora), len(corpora),
+                                                    word.ctypes.data_as(_ip), path.ctypes.data_as(_ip),
+                                                    _d(score)), self.lib)
+        return word, path, score
 
     def viterbi(self, model, corpus):
         path = np.empty(corpus.frames, dtype=np.int32)
