@@ -5,17 +5,18 @@
 
 // ------------------------------------------------ the full-covariance recogniser (RC)
 
-struct ghmm_fmodel {
+struct GHMM_LOCAL ghmm_fmodel {
     int N = 0, M = 0, D = 0;
-    double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_cov = nullptr, *det = nullptr;
-    double *den = nullptr; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
+    // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
+    // run_scan_combine): N, and A (the model's transitions: they live here) with its band flag.
+    // Nothing else of it is set; it is never passed to ghmm_model_destroy.
+    ghmm_model rec;
+    dev_buf<double> &A = rec.A;
+    dev_buf<double> c, mean, inv_cov, det;
+    dev_buf<double> den; // pow(2 pi, D/2) * sqrt(|det|) per Gaussian (RC:921-931)
     // ghmm_viterbi_full: log(c) - log(den) per Gaussian, and A > 0 ? log(A) : -inf, both formed on
     // the host (the oracle's expressions, evaluated by the same libm)
-    double *lk = nullptr, *logA = nullptr;
-    // what the shared recursions of ghmm_estep_full read (run_forward / run_backward /
-    // run_scan_combine): N, and A (aliases the A above, owned there) with its band flag.  Nothing
-    // else of it is set; it is never passed to ghmm_model_destroy.
-    ghmm_model rec;
+    dev_buf<double> lk, logA;
 };
 
 // any N (the concatenated vocabulary of ghmm_score_full_batch has hundreds of states)
@@ -29,14 +30,13 @@ static int fmodel_alloc(ghmm_ctx *ctx, int N, int M, int D, ghmm_fmodel **out)
     // mean and inv_cov with FC_SLACK doubles behind them: the kernel's padded columns read there
     const size_t nmean = G * D + FC_SLACK, ncov = G * D * D + FC_SLACK;
     int rc;
-    if ((rc = dev_alloc(&fm->A, (size_t)N * N)) || (rc = dev_alloc(&fm->c, G)) ||
-        (rc = dev_alloc(&fm->mean, nmean)) || (rc = dev_alloc(&fm->inv_cov, ncov)) ||
-        (rc = dev_alloc(&fm->det, G)) || (rc = dev_alloc(&fm->den, G)) || (rc = dev_alloc(&fm->lk, G)) ||
-        (rc = dev_alloc(&fm->logA, (size_t)N * N))) {
+    if ((rc = fm->A.alloc((size_t)N * N)) || (rc = fm->c.alloc(G)) ||
+        (rc = fm->mean.alloc(nmean)) || (rc = fm->inv_cov.alloc(ncov)) ||
+        (rc = fm->det.alloc(G)) || (rc = fm->den.alloc(G)) || (rc = fm->lk.alloc(G)) ||
+        (rc = fm->logA.alloc((size_t)N * N))) {
         ghmm_fmodel_destroy(ctx, fm);
         return rc;
     }
-    fm->rec.A = fm->A;
     if (hipMemsetAsync(fm->mean, 0, nmean * 8, ctx->stream) != hipSuccess ||
         hipMemsetAsync(fm->inv_cov, 0, ncov * 8, ctx->stream) != hipSuccess) {
         ghmm_fmodel_destroy(ctx, fm);
@@ -70,10 +70,7 @@ extern "C" void ghmm_fmodel_destroy(ghmm_ctx *ctx, ghmm_fmodel *fm)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    void *bufs[] = {fm->A, fm->c, fm->mean, fm->inv_cov, fm->det, fm->den, fm->lk, fm->logA};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    delete fm;
+    delete fm; // (a partly built one too: its buffers free themselves)
 }
 
 extern "C" int ghmm_fmodel_set(ghmm_ctx *ctx, ghmm_fmodel *fm, const double *A, const double *c,
@@ -302,7 +299,7 @@ static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
         }
     }
     if (c->U == 0) return GHMM_OK;
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U))) return rc;
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
     // the tables, built on the host and uploaded into one context buffer: the words' recursions, then
     // every stream's gather sources (word k's Gaussians g0 .. g0 + ng of that stream's vocabulary)
     std::vector<fwd_model> tab((size_t)n_models);
@@ -320,8 +317,8 @@ static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
         }
     }
     const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(fgather_src);
-    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, tab_bytes + src_bytes + 16))) return rc;
-    v->dtab = (const fwd_model *)ctx->fbt_tab;
+    if ((rc = ctx->fbt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
+    v->dtab = (const fwd_model *)ctx->fbt_tab.p;
     const fgather_src *dsrc = (const fgather_src *)(ctx->fbt_tab + ((tab_bytes + 15) / 16) * 16);
     // (the tables leave pageable host vectors: the copies complete before the call returns them)
     HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -401,8 +398,8 @@ extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c,
     if (c->U == 0) return GHMM_OK;
     const lane_grid lg(fm->N, c->U);
     if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
+    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
     return run_viterbi_full(ctx, fm, c, path_host, score_host);
 }
@@ -451,8 +448,8 @@ static int logforward_one_word(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_
 {
     int rc;
     const fwd_model one = {fm->logA, fm->N, 0};
-    if ((rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)c->U))) return rc;
-    if ((rc = dev_grow(&ctx->fbt_tab, &ctx->cap_fbt_tab, sizeof one))) return rc;
+    if ((rc = ctx->bt_ll.grow((size_t)c->U))) return rc;
+    if ((rc = ctx->fbt_tab.grow(sizeof one))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
     return GHMM_OK;
 }
@@ -466,7 +463,7 @@ extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c
     if (c->U == 0) return GHMM_OK;
     if ((rc = logforward_one_word(ctx, fm, c))) return rc;
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
-    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
+    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab.p, 1, fm->N, fm->N, c, final_state, loglik_host);
 }
 
 extern "C" int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
@@ -490,9 +487,9 @@ static int check_stats_full(const ghmm_fmodel *fm, const ghmm_stats *s)
     return GHMM_OK;
 }
 
-// calc_mix_param over every frame (k_fullstats, from ctx->gamma and ctx->post) into *P_out frame-block
-// partials in ctx->part_mu
-static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, long long *P_out)
+// calc_mix_param over every frame (k_fullstats, from ctx->gamma and the posteriors in post) into *P_out
+// frame-block partials in ctx->part_mu
+static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, const double *post, long long *P_out)
 {
     const int N = fm->N, M = fm->M, D = fm->D, G = N * M, D1 = D + 1;
     const long long E = (long long)G * fs_elems(D);
@@ -511,10 +508,10 @@ static int run_fullstats_part(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, lo
     if (fpb < FSn) fpb = FSn;
     P = c->F > 0 ? (c->F + fpb - 1) / fpb : 0;
     if (P > 0) {
-        if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, (size_t)P * (size_t)E))) return rc;
+        if ((rc = ctx->part_mu.grow((size_t)P * (size_t)E))) return rc;
         kscope ks(ctx, GHMM_K_MIXSTATS);
         hipLaunchKernelGGL(k_fullstats, dim3((unsigned)P, (unsigned)NB), dim3(FS_THREADS), lds, ctx->stream, N, M, D,
-                           c->F, fpb, FSn, c->X, ctx->gamma, ctx->post, fm->mean, ctx->part_mu);
+                           c->F, fpb, FSn, c->X, ctx->gamma, post, fm->mean, ctx->part_mu);
         if ((rc = launch_ok("k_fullstats"))) return rc;
     }
     *P_out = P;
@@ -533,12 +530,12 @@ static int run_fullstats_reduce(ghmm_ctx *ctx, const ghmm_fmodel *fm, long long 
 
 // the statistics of an E-step: both of the above, and the utterance sums (num_a, den_a, den_c, log P,
 // count) by k_reduce_all without its Gaussian blocks
-static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s)
+static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_stats *s, const double *post)
 {
     const int N = fm->N, M = fm->M, D = fm->D;
     int rc;
     long long P = 0;
-    if ((rc = run_fullstats_part(ctx, fm, c, &P))) return rc;
+    if ((rc = run_fullstats_part(ctx, fm, c, post, &P))) return rc;
     {
         kscope ks(ctx, GHMM_K_REDUCE);
         if ((rc = run_fullstats_reduce(ctx, fm, P, s->v + (size_t)N * N + 2 * (size_t)N))) return rc;
@@ -583,11 +580,11 @@ extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, g
     if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
     ghmm_model *rm = &fm->rec;
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, rm, c))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
-    if ((rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
+    if ((rc = ctx->post.grow((size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = ctx->lognorm.grow((size_t)c->F))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_POST))) return rc;
     if ((rc = run_recursions_full(ctx, fm, c))) return rc;
-    return run_fullstats(ctx, fm, c, s);
+    return run_fullstats(ctx, fm, c, s, ctx->post);
 }
 
 // the log-domain lattice and its utterance sums (k_logfb_fwd / k_logfb_bwd) on fm's log A and the
@@ -622,10 +619,10 @@ extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *
     int rc = use(ctx);
     if (rc || (rc = check_full(ctx, fm, c)) || (rc = check_stats_full(fm, s))) return rc;
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * fm->N * fm->M))) return rc;
+    if ((rc = ctx->post.grow((size_t)c->F * fm->N * fm->M))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
     if ((rc = run_log_lattice_full(ctx, fm, c))) return rc;
-    return run_fullstats(ctx, fm, c, s);
+    return run_fullstats(ctx, fm, c, s, ctx->post);
 }
 
 extern "C" int ghmm_mstep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_stats *s)
@@ -723,9 +720,9 @@ extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, 
     if (P > c->U) P = c->U;
     const int upb = (c->U + P - 1) / P;
     P = (c->U + upb - 1) / upb;
-    if ((rc = dev_grow(&ctx->finit, &ctx->cap_finit, (size_t)(P + 1) * slice + nfull))) return rc;
-    if ((rc = dev_grow(&ctx->gamma, &ctx->cap_gamma, (size_t)c->F * N))) return rc;
-    if ((rc = dev_grow(&ctx->post, &ctx->cap_post, (size_t)c->F * G))) return rc;
+    if ((rc = ctx->finit.grow((size_t)(P + 1) * slice + nfull))) return rc;
+    if ((rc = ctx->gamma.grow((size_t)c->F * N))) return rc;
+    if ((rc = ctx->post.grow((size_t)c->F * G))) return rc;
     double *part = ctx->finit, *sums = part + (size_t)P * slice, *full = sums + slice;
     double *full_c = full + (size_t)N * N + 2 * (size_t)N;
     const size_t pass_lds = fi_pass_lds_bytes(M, D);
@@ -785,7 +782,7 @@ extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, 
     // init_mix_param (TFF:810-952): one more classification, its one-hot rows into gamma and post;
     // k_fullstats takes dif around the model's mean, which is the cell
     long long PF = 0;
-    if ((rc = finit_pass(M, 1, ctx->gamma, ctx->post)) || (rc = run_fullstats_part(ctx, fm, c, &PF))) return rc;
+    if ((rc = finit_pass(M, 1, ctx->gamma, ctx->post)) || (rc = run_fullstats_part(ctx, fm, c, ctx->post, &PF))) return rc;
     {
         kscope ks(ctx, GHMM_K_REDUCE);
         if ((rc = run_fullstats_reduce(ctx, fm, PF, full_c))) return rc;
@@ -835,16 +832,8 @@ static int emission_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm
     int rc;
     const bool want_post = mode == FC_POST || mode == FC_LOGPOST;
     if ((rc = ws_full(ctx, models[0]->N, models[0]->M, corpora[0]))) return rc;
-    if (want_post) {
-        if ((int)ctx->post_s.size() < P) {
-            ctx->post_s.resize((size_t)P, nullptr);
-            ctx->cap_post_s.resize((size_t)P, 0);
-        }
-        for (int p = 0; p < P; p++)
-            if ((rc = dev_grow(&ctx->post_s[p], &ctx->cap_post_s[p],
-                               (size_t)corpora[p]->F * models[p]->N * models[p]->M)))
-                return rc;
-    }
+    for (int p = 0; want_post && p < P; p++)
+        if ((rc = ctx->post_s[p].grow((size_t)corpora[p]->F * models[p]->N * models[p]->M))) return rc;
     for (int p = 0; p < P; p++)
         if ((rc = run_emission_full(ctx, models[p], corpora[p], mode, p > 0, want_post ? ctx->post_s[p] : nullptr)))
             return rc;
@@ -862,18 +851,13 @@ extern "C" int ghmm_estep_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models
     ghmm_fmodel *fm = models[0];
     ghmm_corpus *c = corpora[0];
     if ((rc = ws_fb(ctx, &fm->rec, c))) return rc;
-    if (!log_domain && (rc = dev_grow(&ctx->lognorm, &ctx->cap_lognorm, (size_t)c->F))) return rc;
+    if (!log_domain && (rc = ctx->lognorm.grow((size_t)c->F))) return rc;
     if ((rc = emission_full_streams(ctx, models, corpora, P, log_domain ? FC_LOGPOST : FC_POST))) return rc;
     // the single-stream calls' recursion launches, on models[0]'s transitions and the product
     if ((rc = log_domain ? run_log_lattice_full(ctx, fm, c) : run_recursions_full(ctx, fm, c))) return rc;
     // calc_mix_param per stream (TFF:289-297) with the common gamma; the transition sums, den_c, log P
     // and the exemplar count go into every stream's vector
-    double *const post_own = ctx->post;
-    for (int p = 0; p < P && !rc; p++) {
-        ctx->post = ctx->post_s[p];
-        rc = run_fullstats(ctx, models[p], corpora[p], stats[p]);
-    }
-    ctx->post = post_own;
+    for (int p = 0; p < P && !rc; p++) rc = run_fullstats(ctx, models[p], corpora[p], stats[p], ctx->post_s[p]);
     return rc;
 }
 
@@ -903,7 +887,7 @@ extern "C" int ghmm_logscore_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mod
     if (c->U == 0) return GHMM_OK;
     if ((rc = logforward_one_word(ctx, fm, c))) return rc;
     if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG))) return rc;
-    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab, 1, fm->N, fm->N, c, final_state, loglik_host);
+    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab.p, 1, fm->N, fm->N, c, final_state, loglik_host);
 }
 
 // ------------------------------------------------ several-stream vocabularies
@@ -922,8 +906,8 @@ extern "C" int ghmm_viterbi_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mode
     ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
     if (c->U == 0) return GHMM_OK;
     const lane_grid lg(fm->N, c->U);
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
+    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
     if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG))) return rc;
     return run_viterbi_full(ctx, fm, c, path_host, score_host);
 }
@@ -970,9 +954,9 @@ extern "C" int ghmm_recognise_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mo
     if (rc || corpora[0]->U == 0) return rc;
     const ghmm_corpus *c = corpora[0];
     const lane_grid lg(v.Nmax, c->U);
-    if ((rc = dev_grow(&ctx->best_word, &ctx->cap_best_word, (size_t)c->U))) return rc;
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
+    if ((rc = ctx->best_word.grow((size_t)c->U))) return rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
+    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
     if ((rc = run_viterbi_vocab(ctx, v, n_models, c))) return rc;
     {
         kscope ks(ctx, GHMM_K_VITERBI);

@@ -55,46 +55,118 @@ struct ktimer {
     int64_t launches = 0;
 };
 
+// A device allocation that frees itself: the pointer and its capacity in elements.  Reads as a T *
+// wherever one is expected (kernel arguments, copies, reduce_args).  (GHMM_LOCAL: the type's members,
+// and the destructors it gives the structs that hold one, stay out of the library's dynamic symbols.)
+#define GHMM_LOCAL __attribute__((visibility("hidden")))
+template <class T> struct GHMM_LOCAL dev_buf {
+    T *p = nullptr;
+    size_t cap = 0;
+    dev_buf() = default;
+    dev_buf(const dev_buf &) = delete;
+    dev_buf &operator=(const dev_buf &) = delete;
+    ~dev_buf() { release(); }
+    operator T *() const { return p; }
+    // workspace: room for `need` elements; grown on demand (the old contents are gone), never shrunk
+    int grow(size_t need) { return (need <= cap && p) ? GHMM_OK : renew(need ? need : 1); }
+    // a buffer of fixed size, allocated once
+    int alloc(size_t n) { return renew(n ? n : 1); }
+    int renew(size_t n)
+    {
+        if (p) HIP_TRY(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc((void **)&p, n * sizeof(T)));
+        cap = n;
+        return GHMM_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 struct ghmm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int cus = 256, dev_cus = 256; // grid sizing (GHMM_OPT_CUS) / the device's count
     int64_t delta = 1, robust = 0, kernels = 0, timing = 0, partials = 0, vec_stats = 0, nt_post = 0, fused_scan = 0;
-    // workspace (grown on demand, never shrunk)
-    size_t cap_b = 0, cap_post = 0, cap_alpha = 0, cap_beta = 0, cap_gamma = 0, cap_scale = 0,
-           cap_lognorm = 0, cap_loglik = 0, cap_pxi = 0, cap_pdena = 0, cap_pdenc = 0, cap_pmu = 0,
-           cap_pvar = 0, cap_psi = 0, cap_path = 0, cap_pm = 0, cap_sinv = 0, cap_sink = 0;
-    double *b = nullptr, *post = nullptr, *alpha = nullptr, *beta = nullptr, *gamma = nullptr;
-    double *scale = nullptr, *sinv = nullptr, *lognorm = nullptr, *loglik = nullptr;
-    double *sink = nullptr; // [0,64): idle lanes' stores land here; [64,128): zeros they read
-    double *part_xi = nullptr, *part_dena = nullptr, *part_denc = nullptr;
-    // paired scans (ghmm_pair.hpp): W rows and 1/s_t of the backward pass with its own normaliser
-    // pinned bounce buffers for large device-to-host copies into pageable memory
-    void *pin[2] = {nullptr, nullptr};
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    double *wrow = nullptr, *sb = nullptr, *lpart = nullptr, *logk = nullptr;
-    size_t cap_wrow = 0, cap_sb = 0, cap_lpart = 0, cap_logk = 0;
+
+    // ---- per-frame workspace (every buffer below: grown on demand, never shrunk)
+    dev_buf<double> b_alloc; // b sits B_PAD_FRAMES rows (b_pad doubles) inside this allocation (grow_b)
+    size_t b_pad = 0;
+    double *b = nullptr;
+    dev_buf<double> post, alpha, beta, gamma, scale, sinv, lognorm, loglik;
+    dev_buf<double> sink;     // [0,64): idle lanes' stores land here; [64,128): zeros they read
+    dev_buf<int> wide_flag;   // models of more than 64 states: A (or log A) has entries off the band
+    dev_buf<unsigned> smask;  // states occupied in each 16-frame stage (k_stage_masks)
+    // shape of what the workspace currently holds (for ghmm_fetch)
+    long long F = 0;
+    int U = 0, N = 0, G = 0;
+    bool b_is_log = false;
+    // what the emission densities in the workspace belong to (ghmm_forward / ghmm_backward /
+    // ghmm_accumulate check it): model, its preparation count, corpus
+    const ghmm_model *em_m = nullptr;
+    const ghmm_corpus *em_c = nullptr;
+    int em_epoch = -1;
+    // post holds the mixture posteriors of that emission (or what a full-covariance call put there
+    // for ghmm_fetch): only then do ghmm_accumulate and ghmm_fetch(GHMM_BUF_POST) read it.  The
+    // buffer is only ever grown, so without this an emission that wrote no posteriors, or wrote
+    // them into post_s[p], would leave an earlier call's, of another shape, to be read.
+    bool post_valid = false;
+
+    // ---- paired scans (ghmm_pair.hpp): W rows and 1/s_t of the backward pass with its own
+    // normaliser, and the pieces of log P (lpart per chunk, logk per utterance)
+    dev_buf<double> wrow, sb, lpart, logk;
     // utterances k_combine hands to k_backward_fix (ghmm_pair.hpp, RANGE): per-utterance marks
     // stamped with the pass number, the list, and two counters used alternately (the fix-up
     // kernel of pass n zeroes the counter of pass n + 1)
-    int *fix_mark = nullptr, *fix_list = nullptr, *fix_cnt = nullptr;
-    int *wide_flag = nullptr; // models of more than 64 states: A (or log A) has entries off the band
+    dev_buf<int> fix_mark, fix_list, fix_cnt;
+    int fix_stamp = 0;
+    bool loglik_pieces = false; // log P of the last E-step is in lpart / logk, loglik[] not assembled
+    int lp_nch = 0;             // chunks per utterance of those pieces
+    bool own_bwd_done = false; // k_scan_pair ran the backward direction for the current alpha
+    bool beta_valid = false;   // beta holds the reference's beta^
+    // what the last gamma / xi pass ran on, so that ghmm_fetch(GHMM_BUF_BETA) can form beta^ when
+    // ghmm_estep skipped it; cleared when that model changes or either object goes away
+    ghmm_model *last_m = nullptr;
+    ghmm_corpus *last_c = nullptr;
+
+    // ---- partial sums: per (utterance, chunk) slot from the backward / combine pass, per frame
+    // block from the statistics kernels
+    dev_buf<double> part_xi, part_dena, part_denc, part_mu, part_var, part_m;
+    int slots = 0; // partial-sum slots filled by the last backward / combine pass
+
+    // ---- Viterbi: back-pointers, and the state per frame (N <= 255): one byte on the device
+    dev_buf<unsigned char> psi, path;
+
+    // ---- vocabulary passes
     // ghmm_score_batch: the concatenated vocabulary model and the pass's tables, kept between calls
     ghmm_model *bt_cat = nullptr;
-    char *bt_tab = nullptr;
+    dev_buf<char> bt_tab;
+    dev_buf<double> bt_scale, bt_sinv, bt_ll;
     // ghmm_score_full_batch: the same for the full-covariance vocabulary (the log P go to bt_ll)
     ghmm_fmodel *fbt_cat = nullptr;
     // the *_full_streams_batch calls: fbt_cat is stream 0's vocabulary, fbt_cat_s[p] stream p's (p >= 1)
     ghmm_fmodel *fbt_cat_s[GHMM_MAX_STREAMS] = {};
-    int *best_word = nullptr; // ghmm_recognise_full_streams: every utterance's winning word
-    size_t cap_best_word = 0;
-    char *fbt_tab = nullptr;
-    size_t cap_fbt_tab = 0;
-    double *bt_scale = nullptr, *bt_sinv = nullptr, *bt_ll = nullptr;
-    size_t cap_bt_tab = 0, cap_bt_scale = 0, cap_bt_sinv = 0, cap_bt_ll = 0;
-    size_t cap_fix_mark = 0, cap_fix_list = 0;
-    int fix_stamp = 0;
+    dev_buf<char> fbt_tab;
+    dev_buf<int> best_word; // ghmm_recognise_full_streams: every utterance's winning word
+
+    // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
+    dev_buf<double> b_stream;
+    dev_buf<double> post_s[GHMM_MAX_STREAMS];
+
+    // ---- initial models
+    // ghmm_fmodel_init: the k-means partials and sums, and the last pass's full-layout statistics
+    dev_buf<double> finit;
+
+    // ---- host memory and bookkeeping
+    // pinned bounce buffers for large device-to-host copies into pageable memory
+    void *pin[2] = {nullptr, nullptr};
+    hipEvent_t pin_ev[2] = {nullptr, nullptr};
     long long launch_mark = 0, sync_mark = 0; // preparations enqueued / covered by a completed wait (stream_sync)
     // one page of fine-grained pinned host memory, 64 slots of 64 bytes: the models' host-visible
     // statistics flags (ghmm_model::hflag_host).  One allocation per context: hipHostMalloc takes
@@ -106,44 +178,6 @@ struct ghmm_ctx {
     long long *mbox_page = nullptr, *mbox_page_dev = nullptr;
     unsigned long long mbox_used = 0;
     long long mbox_seq = 0;
-    bool loglik_pieces = false; // log P of the last E-step is in lpart / logk, loglik[] not assembled
-    int lp_nch = 0;             // chunks per utterance of those pieces
-    bool own_bwd_done = false; // k_scan_pair ran the backward direction for the current alpha
-    bool beta_valid = false;   // ctx->beta holds the reference's beta^
-    // what the last gamma / xi pass ran on, so that ghmm_fetch(GHMM_BUF_BETA) can form beta^ when
-    // ghmm_estep skipped it; cleared when that model changes or either object goes away
-    ghmm_model *last_m = nullptr;
-    ghmm_corpus *last_c = nullptr;
-    int slots = 0;             // partial-sum slots filled by the last backward / combine pass
-    double *part_mu = nullptr, *part_var = nullptr, *part_m = nullptr;
-    // ghmm_fmodel_init: the k-means partials and sums, and the last pass's full-layout statistics
-    double *finit = nullptr;
-    size_t cap_finit = 0;
-    // several feature streams: the stream being evaluated (b^p) and every stream's posteriors
-    double *b_stream = nullptr;
-    double *b_alloc = nullptr; // b sits B_PAD_FRAMES rows inside this allocation (grow_b)
-    unsigned *smask = nullptr; // states occupied in each 16-frame stage (k_stage_masks)
-    size_t cap_smask = 0;
-    size_t b_pad = 0;
-    size_t cap_b_stream = 0;
-    std::vector<double *> post_s;
-    std::vector<size_t> cap_post_s;
-    unsigned char *psi = nullptr;
-    unsigned char *path = nullptr; // Viterbi state per frame (N <= 255): one byte on the device
-    // shape of what the workspace currently holds (for ghmm_fetch)
-    long long F = 0;
-    int U = 0, N = 0, G = 0;
-    bool b_is_log = false;
-    // what the emission densities in the workspace belong to (ghmm_forward / ghmm_backward /
-    // ghmm_accumulate check it): model, its preparation count, corpus
-    const ghmm_model *em_m = nullptr;
-    const ghmm_corpus *em_c = nullptr;
-    int em_epoch = -1;
-    // ctx->post holds the mixture posteriors of that emission (or what a full-covariance call put
-    // there for ghmm_fetch): only then do ghmm_accumulate and ghmm_fetch(GHMM_BUF_POST) read it.
-    // The buffer is only ever grown, so without this an emission that wrote no posteriors, or wrote
-    // them into post_s[p], would leave an earlier call's, of another shape, to be read.
-    bool post_valid = false;
     // kernels whose dynamic-LDS limit has been raised on THIS context's device (the attribute
     // is per device and per function; nothing process-wide, nothing shared between threads)
     std::vector<const void *> lds_fns;
@@ -161,25 +195,25 @@ static hipError_t stream_sync(ghmm_ctx *ctx)
     return e;
 }
 
-struct ghmm_model {
+struct GHMM_LOCAL ghmm_model {
     int N = 0, M = 0, D = 0;
-    double *A = nullptr, *c = nullptr, *mean = nullptr, *inv_var = nullptr, *det = nullptr;
-    double *wk = nullptr, *logwk = nullptr, *logA = nullptr;
+    dev_buf<double> A, c, mean, inv_var, det;
+    dev_buf<double> wk, logwk, logA;
     // matrix-core tier (ghmm_mfma.hpp): padded geometry and B fragments
     int Mp = 0, NT = 0, DP = 0, TC = 0, tps = 1;
     int TCs[3] = {0, 0, 0}; // tiles per chunk of k_emission_sched, per output mode
     size_t em_lds = 0;
     bool mfma_ok = false;
-    double *Wm = nullptr, *offs = nullptr, *wkp = nullptr, *logwkp = nullptr, *condp = nullptr;
-    double *oglob = nullptr, *condg = nullptr;
-    int *gmap = nullptr, *anyflag = nullptr;
+    dev_buf<double> Wm, offs, wkp, logwkp;
+    dev_buf<double> oglob, condg;
+    dev_buf<int> gmap, anyflag;
     // per-tile offsets of the expanded form (ghmm_mfma.hpp): otile[NT][DP] the offset itself,
     // dtile = otile - oglob, tshift[NT] = the tile has its own offset; condt = conditioning
     // relative to the tile's offset; sflag: like anyflag, for the statistics (global offset)
-    double *otile = nullptr, *dtile = nullptr, *condt = nullptr;
-    int *tshift = nullptr, *sflag = nullptr, *tnext = nullptr; // tnext: the choice for the next preparation
-    int *scls = nullptr;  // [NT*16] how each padded Gaussian's statistics are taken (stats_class)
-    int *tfull = nullptr; // [NT] the tile's slots are 16 consecutive real Gaussians, even start, G even
+    dev_buf<double> otile, dtile, condt;
+    dev_buf<int> tshift, sflag, tnext; // tnext: the choice for the next preparation
+    dev_buf<int> scls;  // [NT*16] how each padded Gaussian's statistics are taken (stats_class)
+    dev_buf<int> tfull; // [NT] the tile's slots are 16 consecutive real Gaussians, even start, G even
     // sflag's value as the HOST sees it, some launches late (pinned, mapped memory that the
     // preparing kernels write directly): the last preparation that found a class-2 Gaussian.
     // run_accumulate launches the vector-ALU k_mixstats only while that is recent (or the model
@@ -195,11 +229,11 @@ struct ghmm_model {
     int NE = 0, CT = 0; // statistics kernel: feature tiles, Gaussian tiles per wave
 };
 
-struct ghmm_corpus {
+struct GHMM_LOCAL ghmm_corpus {
     const double *X = nullptr;
     bool own = false;
-    long long *off = nullptr; // device, U+1
-    int *order = nullptr;     // device, U: utterance indices by decreasing length (stable)
+    dev_buf<long long> off; // device, U+1
+    dev_buf<int> order;     // device, U: utterance indices by decreasing length (stable)
     std::vector<int32_t> len;
     long long F = 0;
     int U = 0, D = 0, Tmax = 0;
@@ -228,18 +262,6 @@ extern "C" const char *ghmm_kernel_name(int k)
 }
 
 // ----------------------------------------------------------------- helpers
-
-template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap && *p) return GHMM_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    size_t n = need ? need : 1;
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return GHMM_OK;
-}
 
 template <class T> static int dev_alloc(T **p, size_t n)
 {
@@ -422,16 +444,6 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
             ghmm_fmodel_destroy(ctx, cat);
             cat = nullptr;
         }
-    void *bufs[] = {ctx->best_word, ctx->fbt_tab, ctx->bt_tab, ctx->bt_scale, ctx->bt_sinv, ctx->bt_ll, ctx->b_alloc, ctx->post,      ctx->alpha,     ctx->beta,    ctx->gamma,
-                    ctx->scale,   ctx->lognorm,   ctx->loglik,    ctx->part_xi, ctx->part_dena,
-                    ctx->part_denc, ctx->part_mu, ctx->part_var,  ctx->psi,     ctx->path,
-                    ctx->part_m,  ctx->sinv,      ctx->sink,      ctx->wrow,    ctx->sb,
-                    ctx->lpart,   ctx->logk,      ctx->b_stream,  ctx->smask,
-                    ctx->fix_mark, ctx->fix_list, ctx->fix_cnt, ctx->wide_flag, ctx->finit};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    for (double *p : ctx->post_s)
-        if (p) (void)hipFree(p);
     if (ctx->hflag_page) (void)hipHostFree(ctx->hflag_page);
     if (ctx->mbox_page) (void)hipHostFree(ctx->mbox_page);
     for (int k = 0; k < 2; k++) {
@@ -442,8 +454,9 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
         for (auto &e : t.pending) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         for (auto &e : t.pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     }
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t own = ctx->own_stream ? ctx->stream : nullptr;
+    delete ctx; // the device buffers free themselves: behind the wait above, before the stream goes
+    if (own) (void)hipStreamDestroy(own);
 }
 
 extern "C" int ghmm_ctx_sync(ghmm_ctx *ctx)
@@ -610,10 +623,10 @@ extern "C" int ghmm_model_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_model 
     if (!m) return GHMM_ERR_ALLOC;
     m->N = N; m->M = M; m->D = D;
     size_t G = (size_t)N * M;
-    if ((rc = dev_alloc(&m->A, (size_t)N * N)) || (rc = dev_alloc(&m->c, G)) ||
-        (rc = dev_alloc(&m->mean, G * D)) || (rc = dev_alloc(&m->inv_var, G * D)) ||
-        (rc = dev_alloc(&m->det, G)) || (rc = dev_alloc(&m->wk, G)) ||
-        (rc = dev_alloc(&m->logwk, G)) || (rc = dev_alloc(&m->logA, (size_t)N * N))) {
+    if ((rc = m->A.alloc((size_t)N * N)) || (rc = m->c.alloc(G)) ||
+        (rc = m->mean.alloc(G * D)) || (rc = m->inv_var.alloc(G * D)) ||
+        (rc = m->det.alloc(G)) || (rc = m->wk.alloc(G)) ||
+        (rc = m->logwk.alloc(G)) || (rc = m->logA.alloc((size_t)N * N))) {
         ghmm_model_destroy(ctx, m);
         return rc;
     }
@@ -646,17 +659,16 @@ extern "C" int ghmm_model_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_model 
         m->mfma_ok = TC >= m->tps && TC > 0 && m->em_lds <= 150 * 1024 && 16 * m->D <= 64 * EM_XR;
         if (m->mfma_ok) {
             size_t nw = (size_t)m->NT * (m->DP / 2) * 64;
-            if ((rc = dev_alloc(&m->Wm, nw)) || (rc = dev_alloc(&m->offs, (size_t)m->NT * m->DP)) ||
-                (rc = dev_alloc(&m->wkp, (size_t)m->NT * 16)) ||
-                (rc = dev_alloc(&m->logwkp, (size_t)m->NT * 16)) ||
-                (rc = dev_alloc(&m->condp, (size_t)m->NT * 16)) ||
-                (rc = dev_alloc(&m->gmap, (size_t)m->NT * 16)) ||
-                (rc = dev_alloc(&m->condg, (size_t)m->NT * 16)) ||
-                (rc = dev_alloc(&m->oglob, (size_t)m->DP)) || (rc = dev_alloc(&m->anyflag, 1)) ||
-                (rc = dev_alloc(&m->otile, (size_t)m->NT * m->DP)) || (rc = dev_alloc(&m->dtile, (size_t)m->NT * m->DP)) ||
-                (rc = dev_alloc(&m->condt, (size_t)m->NT * 16)) || (rc = dev_alloc(&m->tshift, (size_t)m->NT)) ||
-                (rc = dev_alloc(&m->sflag, 1)) || (rc = dev_alloc(&m->tnext, (size_t)m->NT)) ||
-                (rc = dev_alloc(&m->tfull, (size_t)m->NT)) || (rc = dev_alloc(&m->scls, (size_t)m->NT * 16))) {
+            if ((rc = m->Wm.alloc(nw)) || (rc = m->offs.alloc((size_t)m->NT * m->DP)) ||
+                (rc = m->wkp.alloc((size_t)m->NT * 16)) ||
+                (rc = m->logwkp.alloc((size_t)m->NT * 16)) ||
+                (rc = m->gmap.alloc((size_t)m->NT * 16)) ||
+                (rc = m->condg.alloc((size_t)m->NT * 16)) ||
+                (rc = m->oglob.alloc((size_t)m->DP)) || (rc = m->anyflag.alloc(1)) ||
+                (rc = m->otile.alloc((size_t)m->NT * m->DP)) || (rc = m->dtile.alloc((size_t)m->NT * m->DP)) ||
+                (rc = m->condt.alloc((size_t)m->NT * 16)) || (rc = m->tshift.alloc((size_t)m->NT)) ||
+                (rc = m->sflag.alloc(1)) || (rc = m->tnext.alloc((size_t)m->NT)) ||
+                (rc = m->tfull.alloc((size_t)m->NT)) || (rc = m->scls.alloc((size_t)m->NT * 16))) {
                 ghmm_model_destroy(ctx, m);
                 return rc;
             }
@@ -734,13 +746,8 @@ extern "C" void ghmm_model_destroy(ghmm_ctx *ctx, ghmm_model *m)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    void *bufs[] = {m->A,  m->c,    m->mean, m->inv_var, m->det,   m->wk,    m->logwk, m->logA,
-                    m->Wm, m->offs, m->wkp,  m->condp,   m->gmap,  m->oglob, m->condg, m->anyflag,
-                    m->logwkp, m->otile, m->dtile, m->condt, m->tshift, m->sflag, m->tnext, m->tfull, m->scls};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
     if (m->hflag_slot >= 0 && ctx) ctx->hflag_used &= ~(1ull << m->hflag_slot);
-    delete m;
+    delete m; // (a partly built one too: its buffers free themselves)
 }
 
 extern "C" int ghmm_model_set(ghmm_ctx *ctx, ghmm_model *m, const double *A, const double *c,
@@ -825,8 +832,7 @@ static int corpus_make(ghmm_ctx *ctx, const double *X_host, const double *X_dev,
     std::vector<int> ord((size_t)n_utt);
     for (int u = 0; u < n_utt; u++) ord[u] = u;
     std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return len[a] > len[b]; });
-    if ((rc = dev_alloc(&c->off, off.size())) || (rc = dev_alloc(&c->order, ord.size()))) {
-        if (c->off) (void)hipFree(c->off);
+    if ((rc = c->off.alloc(off.size())) || (rc = c->order.alloc(ord.size()))) {
         delete c;
         return rc;
     }
@@ -837,8 +843,6 @@ static int corpus_make(ghmm_ctx *ctx, const double *X_host, const double *X_dev,
     if (e == hipSuccess && X_host) {
         double *xd = nullptr;
         if ((rc = dev_alloc(&xd, (size_t)c->F * D))) {
-            (void)hipFree(c->off);
-            (void)hipFree(c->order);
             delete c;
             return rc;
         }
@@ -853,8 +857,6 @@ static int corpus_make(ghmm_ctx *ctx, const double *X_host, const double *X_dev,
     if (e != hipSuccess) {
         ghmm_set_error("corpus upload failed: %s", hipGetErrorString(e));
         if (c->own) (void)hipFree((void *)c->X);
-        (void)hipFree(c->off);
-        (void)hipFree(c->order);
         delete c;
         return GHMM_ERR_HIP;
     }
@@ -887,8 +889,6 @@ extern "C" void ghmm_corpus_destroy(ghmm_ctx *ctx, ghmm_corpus *c)
         (void)hipStreamSynchronize(ctx->stream);
     }
     if (c->own && c->X) (void)hipFree((void *)c->X);
-    if (c->off) (void)hipFree(c->off);
-    if (c->order) (void)hipFree(c->order);
     delete c;
 }
 
@@ -1059,15 +1059,14 @@ static int check_pair(const ghmm_model *m, const ghmm_corpus *c)
 static int grow_b(ghmm_ctx *ctx, size_t F, size_t N)
 {
     const size_t pad = (size_t)B_PAD_FRAMES * N, need = F * N;
-    if (ctx->b_alloc && ctx->b_pad >= pad && ctx->b_pad + need + pad <= ctx->cap_b) return GHMM_OK;
-    if (ctx->b_alloc) HIP_TRY(hipFree(ctx->b_alloc));
-    ctx->b_alloc = ctx->b = nullptr;
-    ctx->cap_b = ctx->b_pad = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->b_alloc, (need + 2 * pad + 1) * sizeof(double)));
+    int rc;
+    if (ctx->b_alloc && ctx->b_pad >= pad && ctx->b_pad + need + pad <= ctx->b_alloc.cap) return GHMM_OK;
+    ctx->b = nullptr;
+    ctx->b_pad = 0;
+    if ((rc = ctx->b_alloc.renew(need + 2 * pad + 1))) return rc;
     // (defined contents for the rows no frame owns)
     HIP_TRY(hipMemsetAsync(ctx->b_alloc, 0, pad * sizeof(double), ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->b_alloc + pad + need, 0, (pad + 1) * sizeof(double), ctx->stream));
-    ctx->cap_b = need + 2 * pad + 1;
     ctx->b_pad = pad;
     ctx->b = ctx->b_alloc + pad;
     return GHMM_OK;
@@ -1080,13 +1079,13 @@ static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
     int rc;
     const size_t F = (size_t)c->F;
     if ((rc = grow_b(ctx, F, (size_t)N))) return rc;
-    if ((rc = dev_grow(&ctx->scale, &ctx->cap_scale, F))) return rc;
-    if ((rc = dev_grow(&ctx->sinv, &ctx->cap_sinv, F))) return rc;
+    if ((rc = ctx->scale.grow(F))) return rc;
+    if ((rc = ctx->sinv.grow(F))) return rc;
     if (!ctx->sink) {
-        if ((rc = dev_grow(&ctx->sink, &ctx->cap_sink, (size_t)2 * WAVE * SINK_WAVES))) return rc;
+        if ((rc = ctx->sink.grow((size_t)2 * WAVE * SINK_WAVES))) return rc;
         HIP_TRY(hipMemsetAsync(ctx->sink, 0, (size_t)2 * WAVE * SINK_WAVES * sizeof(double), ctx->stream));
     }
-    if ((rc = dev_grow(&ctx->loglik, &ctx->cap_loglik, (size_t)c->U))) return rc;
+    if ((rc = ctx->loglik.grow((size_t)c->U))) return rc;
     ctx->F = c->F;
     ctx->U = c->U;
     ctx->N = N;
@@ -1100,8 +1099,8 @@ static int ws_frames(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c, b
     int rc;
     const size_t F = (size_t)c->F;
     if ((rc = ws_full(ctx, m->N, m->M, c))) return rc;
-    if (want_post && (rc = dev_grow(&ctx->post, &ctx->cap_post, F * m->N * m->M))) return rc;
-    return dev_grow(&ctx->lognorm, &ctx->cap_lognorm, F);
+    if (want_post && (rc = ctx->post.grow(F * m->N * m->M))) return rc;
+    return ctx->lognorm.grow(F);
 }
 
 // The workspace is about to be rewritten by something no diagonal model owns: the row API refuses
@@ -1124,24 +1123,24 @@ static int ws_fb(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c)
 {
     int rc;
     size_t FN = (size_t)c->F * m->N, UN = (size_t)c->U * m->N * CB_CH; // one slot per (utterance, chunk)
-    if ((rc = dev_grow(&ctx->wrow, &ctx->cap_wrow, FN))) return rc;
-    if ((rc = dev_grow(&ctx->sb, &ctx->cap_sb, (size_t)c->F))) return rc;
-    if ((rc = dev_grow(&ctx->lpart, &ctx->cap_lpart, (size_t)c->U * CB_CH))) return rc;
-    if ((rc = dev_grow(&ctx->logk, &ctx->cap_logk, (size_t)c->U))) return rc;
-    if ((rc = dev_grow(&ctx->alpha, &ctx->cap_alpha, FN))) return rc;
-    if ((rc = dev_grow(&ctx->beta, &ctx->cap_beta, FN))) return rc;
-    if ((rc = dev_grow(&ctx->gamma, &ctx->cap_gamma, FN))) return rc;
-    if ((rc = dev_grow(&ctx->part_xi, &ctx->cap_pxi, UN * (MAX_DELTA + 1)))) return rc;
-    if ((rc = dev_grow(&ctx->part_dena, &ctx->cap_pdena, UN))) return rc;
-    if ((rc = dev_grow(&ctx->part_denc, &ctx->cap_pdenc, UN))) return rc;
-    if ((size_t)c->U > ctx->cap_fix_mark) {
-        if ((rc = dev_grow(&ctx->fix_mark, &ctx->cap_fix_mark, (size_t)c->U))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->cap_fix_mark * sizeof(int), ctx->stream));
+    if ((rc = ctx->wrow.grow(FN))) return rc;
+    if ((rc = ctx->sb.grow((size_t)c->F))) return rc;
+    if ((rc = ctx->lpart.grow((size_t)c->U * CB_CH))) return rc;
+    if ((rc = ctx->logk.grow((size_t)c->U))) return rc;
+    if ((rc = ctx->alpha.grow(FN))) return rc;
+    if ((rc = ctx->beta.grow(FN))) return rc;
+    if ((rc = ctx->gamma.grow(FN))) return rc;
+    if ((rc = ctx->part_xi.grow(UN * (MAX_DELTA + 1)))) return rc;
+    if ((rc = ctx->part_dena.grow(UN))) return rc;
+    if ((rc = ctx->part_denc.grow(UN))) return rc;
+    if ((size_t)c->U > ctx->fix_mark.cap) {
+        if ((rc = ctx->fix_mark.grow((size_t)c->U))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->fix_mark.cap * sizeof(int), ctx->stream));
         ctx->fix_stamp = 0; // (stamps start at 1: a zeroed mark never equals one)
     }
-    if ((rc = dev_grow(&ctx->fix_list, &ctx->cap_fix_list, (size_t)c->U))) return rc;
+    if ((rc = ctx->fix_list.grow((size_t)c->U))) return rc;
     if (!ctx->fix_cnt) {
-        if ((rc = dev_alloc(&ctx->fix_cnt, 2))) return rc;
+        if ((rc = ctx->fix_cnt.alloc(2))) return rc;
         HIP_TRY(hipMemsetAsync(ctx->fix_cnt, 0, 2 * sizeof(int), ctx->stream));
     }
     return GHMM_OK;
@@ -1160,7 +1159,9 @@ static bool nt_posteriors(const ghmm_ctx *ctx, const ghmm_model *m, const ghmm_c
            (ctx->nt_post == 0 && (double)c->F * m->N * m->M * 8.0 <= 1024.0 * 1048576.0);
 }
 
-static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, bool want_post)
+// b: where the densities go (the workspace's b, or b_stream); post: where the mixture posteriors go
+// (the workspace's own buffer, a stream's post_s[p], or null for none)
+static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, double *b, double *post)
 {
     // the workspace is rewritten: alpha^ / W / 1/s of an earlier E-step no longer go with its b
     // (ghmm_fetch(GHMM_BUF_BETA) refuses instead of rebuilding beta^ from mixed buffers)
@@ -1169,11 +1170,9 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
     ctx->em_m = m;
     ctx->em_c = c;
     ctx->em_epoch = m->epoch;
-    // posteriors written into ctx->post's own buffer are the workspace's; streams_emission points
-    // ctx->post at post_s[p], which ghmm_fetch and ghmm_accumulate do not serve
-    ctx->post_valid = want_post;
-    for (const double *ps : ctx->post_s)
-        if (ps && ps == ctx->post) ctx->post_valid = false;
+    // posteriors written into the workspace's own buffer are the workspace's; streams_emission
+    // passes post_s[p], which ghmm_fetch and ghmm_accumulate do not serve
+    ctx->post_valid = post && post == ctx->post;
     if (c->F == 0) return GHMM_OK;
     const long long blocks = (c->F + WAVE - 1) / WAVE;
     const size_t lds = (size_t)WAVE * (m->D | 1) * sizeof(double);
@@ -1181,7 +1180,6 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
         ghmm_set_error("coefficient count %d too large for the emission tile", m->D);
         return GHMM_ERR_UNSUPPORTED;
     }
-    double *post = want_post ? ctx->post : nullptr;
     const bool sched_ok = m->mfma_ok && ctx->kernels != 1 &&
                           (m->Mp <= 16 || m->Mp == 32 || m->Mp == 64) &&
                           m->DP >= 8 && m->DP <= 48;
@@ -1208,7 +1206,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
         if ((rc = lds_attr(ctx, (const void *)k_emission_sched<KSV, MP, PO>))) return rc;        \
         hipLaunchKernelGGL((k_emission_sched<KSV, MP, PO>), dim3((unsigned)gxs, (unsigned)chunks), \
                            dim3((unsigned)(wv * WAVE)), lds_s, ctx->stream, m->N, m->M, m->D, m->NT, \
-                           tcs, c->F, c->X, m->Wm, m->oglob, wk, m->gmap, ctx->b, post, m->dtile, \
+                           tcs, c->F, c->X, m->Wm, m->oglob, wk, m->gmap, b, post, m->dtile, \
                            m->tshift, m->tfull, m->condt, m->mean, m->inv_var, ntp);              \
     } while (0)
 #define GHMM_EMS(MP, PO)                                                                          \
@@ -1258,7 +1256,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
             hipLaunchKernelGGL(k_emission_mfma, dim3((unsigned)gx, (unsigned)chunks),
                                dim3(EM_WAVES * WAVE), m->em_lds, ctx->stream, m->N, m->M, m->Mp, m->D,
                                m->DP, m->NT, m->TC, c->F, c->X, m->Wm, m->oglob, m->wkp, m->gmap,
-                               m->condt, m->mean, m->inv_var, ctx->b, post, (const int *)nullptr,
+                               m->condt, m->mean, m->inv_var, b, post, (const int *)nullptr,
                                m->epoch, m->tshift, m->dtile);
         }
         ctx->b_is_log = false;
@@ -1270,15 +1268,15 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
         if (mode == 0)
             hipLaunchKernelGGL(k_emission<0>, dim3((unsigned)blocks), dim3(WAVE), lds, ctx->stream,
                                m->N, m->M, m->D, c->F, c->X, m->mean, m->inv_var, m->wk, m->logwk,
-                               ctx->b, post, ctx->lognorm, only_if, m->epoch);
+                               b, post, ctx->lognorm, only_if, m->epoch);
         else if (mode == 1)
             hipLaunchKernelGGL(k_emission<1>, dim3((unsigned)blocks), dim3(WAVE), lds, ctx->stream,
                                m->N, m->M, m->D, c->F, c->X, m->mean, m->inv_var, m->wk, m->logwk,
-                               ctx->b, post, ctx->lognorm, only_if, m->epoch);
+                               b, post, ctx->lognorm, only_if, m->epoch);
         else
             hipLaunchKernelGGL(k_emission<2>, dim3((unsigned)blocks), dim3(WAVE), lds, ctx->stream,
                                m->N, m->M, m->D, c->F, c->X, m->mean, m->inv_var, m->wk, m->logwk,
-                               ctx->b, post, ctx->lognorm, only_if, m->epoch);
+                               b, post, ctx->lognorm, only_if, m->epoch);
     }
     ctx->b_is_log = (mode == 2);
     return launch_ok("k_emission");
@@ -1289,7 +1287,7 @@ extern "C" int ghmm_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int w
     int rc = use(ctx);
     if (rc || (rc = check_pair(m, c))) return rc;
     if ((rc = ws_frames(ctx, m, c, want_post != 0))) return rc;
-    return run_emission(ctx, m, c, ctx->robust ? 1 : 0, want_post != 0);
+    return run_emission(ctx, m, c, ctx->robust ? 1 : 0, ctx->b, want_post ? ctx->post : nullptr);
 }
 
 // ------------------------------------------------------- forward / backward
@@ -1327,7 +1325,7 @@ static int fb_lanes(const ghmm_model *m, int *L)
 static int wide_band_flag(ghmm_ctx *ctx, const ghmm_model *m, const double *A, double zero)
 {
     int rc;
-    if (!ctx->wide_flag && (rc = dev_alloc(&ctx->wide_flag, 1))) return rc;
+    if (!ctx->wide_flag && (rc = ctx->wide_flag.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->wide_flag, 0, sizeof(int), ctx->stream));
     const long long n = (long long)m->N * m->N;
     hipLaunchKernelGGL(k_wide_band, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->N, A, zero,
@@ -1443,7 +1441,7 @@ static int run_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool want_
             // no transition beyond i -> i + 1
             const bool band2 = m->banded && ctx->delta <= 1;
             if (++ctx->fix_stamp == 0x7fffffff) { // (2^31 passes: start the marks over)
-                HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->cap_fix_mark * sizeof(int), ctx->stream));
+                HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->fix_mark.cap * sizeof(int), ctx->stream));
                 HIP_TRY(hipMemsetAsync(ctx->fix_cnt, 0, 2 * sizeof(int), ctx->stream));
                 ctx->fix_stamp = 1;
             }
@@ -1501,7 +1499,7 @@ static int run_scan_combine(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool *
     ctx->own_bwd_done = true;
     ctx->loglik_pieces = true; // the combine phase takes the logs of log P
     if (++ctx->fix_stamp == 0x7fffffff) { // (2^31 passes: start the marks over)
-        HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->cap_fix_mark * sizeof(int), ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->fix_mark.cap * sizeof(int), ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->fix_cnt, 0, 2 * sizeof(int), ctx->stream));
         ctx->fix_stamp = 1;
     }
@@ -1554,7 +1552,7 @@ extern "C" int ghmm_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c)
 // -------------------------------------------------------------- statistics
 
 template <int CT, int NE>
-static int launch_mixstats_mfma(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int P, int chunks)
+static int launch_mixstats_mfma(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, const double *post, int P, int chunks)
 {
     const bool ntl = nt_posteriors(ctx, m, c); // (single-chunk launches only: small models)
     // fold buffer: three of the four register rows of every tile, four waves (ghmm_mfma.hpp, end of k_mixstats_mfma)
@@ -1594,7 +1592,7 @@ static int launch_mixstats_mfma(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, in
             if constexpr (NE == 5) {
                 if (chunks > 1 && c->F >= 16) {
                     const size_t nst = (size_t)((c->F + 15) / 16);
-                    if ((rc = dev_grow(&ctx->smask, &ctx->cap_smask, nst))) return rc;
+                    if ((rc = ctx->smask.grow(nst))) return rc;
                     hipLaunchKernelGGL(k_stage_masks, dim3((unsigned)((c->F + WAVE - 1) / WAVE)), dim3(WAVE), 0,
                                        ctx->stream, m->N, c->F, ctx->gamma, ctx->smask);
                     masked = true;
@@ -1605,7 +1603,7 @@ static int launch_mixstats_mfma(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, in
         if ((rc = lds_attr(ctx, (const void *)k_mixstats_mfma<__VA_ARGS__>))) return rc;          \
         hipLaunchKernelGGL((k_mixstats_mfma<__VA_ARGS__>), dim3((unsigned)P, 1u), dim3(MSM_WAVES * WAVE), lds,  \
                            ctx->stream, m->N, m->M, m->Mp, m->D, m->DP, m->NT, c->F, gmin, GW, c->X, ctx->gamma, \
-                           ctx->post, m->gmap + 0, m->oglob, ctx->part_m,                          \
+                           post, m->gmap + 0, m->oglob, ctx->part_m,                               \
                            masked ? ctx->smask : (const unsigned *)nullptr);                       \
     } while (0)
             // one launch per chunk so that gmin / GW are plain arguments (chunks == 1 at 10x8)
@@ -1629,17 +1627,20 @@ static int launch_mixstats_mfma(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, in
     if ((rc = lds_attr(ctx, (const void *)k_mixstats_mfma<CT, NE, false>))) return rc;
     hipLaunchKernelGGL((k_mixstats_mfma<CT, NE, false>), dim3((unsigned)P, (unsigned)chunks),
                        dim3(MSM_WAVES * WAVE), fold, ctx->stream, m->N, m->M, m->Mp, m->D, m->DP, m->NT,
-                       c->F, 0, 0, c->X, ctx->gamma, ctx->post, m->gmap, m->oglob, ctx->part_m,
+                       c->F, 0, 0, c->X, ctx->gamma, post, m->gmap, m->oglob, ctx->part_m,
                        (const unsigned *)nullptr);
     return GHMM_OK;
 }
 
-static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *s)
+// post: the mixture posteriors to read (the workspace's own, or a stream's post_s[p]); vector_only:
+// the vector-ALU tier whatever GHMM_OPT_KERNELS says (ghmm_model_init's direct-form pass)
+static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *s, const double *post,
+                          bool vector_only = false)
 {
     const int N = m->N, M = m->M, D = m->D, G = N * M, D1 = D + 1;
     const long long E = (long long)G * D1;
     const int NB = (int)((E + MS_THREADS * MS_EPT - 1) / (MS_THREADS * MS_EPT));
-    const bool mfma = m->mfma_ok && m->CT > 0 && ctx->kernels != 1;
+    const bool mfma = m->mfma_ok && m->CT > 0 && ctx->kernels != 1 && !vector_only;
     int rc;
     // frame-block partials: enough blocks to fill the chip a few times over, few
     // enough that the partial sums stay small next to the frame data
@@ -1670,8 +1671,8 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
     const int *only_if = mfma ? m->sflag : nullptr; // statistics: conditioning around the global offset
     if (P > 0) {
         size_t need = (size_t)P * (size_t)E;
-        if ((rc = dev_grow(&ctx->part_mu, &ctx->cap_pmu, need))) return rc;
-        if ((rc = dev_grow(&ctx->part_var, &ctx->cap_pvar, need))) return rc;
+        if ((rc = ctx->part_mu.grow(need))) return rc;
+        if ((rc = ctx->part_var.grow(need))) return rc;
     }
     int Pm = 0;
     size_t nsum = 0;
@@ -1683,18 +1684,18 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
         if (steps < (long long)Pm * MSM_WAVES) Pm = (int)((steps + MSM_WAVES - 1) / MSM_WAVES);
         if (Pm < 1) Pm = 1;
         nsum = (size_t)m->NT * 16 * m->NE * 16;
-        if ((rc = dev_grow(&ctx->part_m, &ctx->cap_pm, (size_t)Pm * nsum))) return rc;
+        if ((rc = ctx->part_m.grow((size_t)Pm * nsum))) return rc;
         {
             kscope ks(ctx, GHMM_K_MIXSTATS);
             switch (m->NE) {
-            case 1: rc = launch_mixstats_mfma<8, 1>(ctx, m, c, Pm, chunks); break;
-            case 2: rc = launch_mixstats_mfma<8, 2>(ctx, m, c, Pm, chunks); break;
-            case 3: rc = launch_mixstats_mfma<8, 3>(ctx, m, c, Pm, chunks); break;
-            case 4: rc = launch_mixstats_mfma<6, 4>(ctx, m, c, Pm, chunks); break;
-            case 5: rc = launch_mixstats_mfma<5, 5>(ctx, m, c, Pm, chunks); break;
-            case 6: rc = launch_mixstats_mfma<4, 6>(ctx, m, c, Pm, chunks); break;
-            case 7: rc = launch_mixstats_mfma<3, 7>(ctx, m, c, Pm, chunks); break;
-            default: rc = launch_mixstats_mfma<3, 8>(ctx, m, c, Pm, chunks); break;
+            case 1: rc = launch_mixstats_mfma<8, 1>(ctx, m, c, post, Pm, chunks); break;
+            case 2: rc = launch_mixstats_mfma<8, 2>(ctx, m, c, post, Pm, chunks); break;
+            case 3: rc = launch_mixstats_mfma<8, 3>(ctx, m, c, post, Pm, chunks); break;
+            case 4: rc = launch_mixstats_mfma<6, 4>(ctx, m, c, post, Pm, chunks); break;
+            case 5: rc = launch_mixstats_mfma<5, 5>(ctx, m, c, post, Pm, chunks); break;
+            case 6: rc = launch_mixstats_mfma<4, 6>(ctx, m, c, post, Pm, chunks); break;
+            case 7: rc = launch_mixstats_mfma<3, 7>(ctx, m, c, post, Pm, chunks); break;
+            default: rc = launch_mixstats_mfma<3, 8>(ctx, m, c, post, Pm, chunks); break;
             }
         }
         if (rc || (rc = launch_ok("k_mixstats_mfma"))) return rc;
@@ -1721,7 +1722,7 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
         // when the model holds ill-conditioned Gaussians, whose sums it then supplies
         kscope ks(ctx, GHMM_K_MIXSTATS);
         hipLaunchKernelGGL(k_mixstats, dim3((unsigned)P, (unsigned)NB), dim3(MS_THREADS), lds,
-                           ctx->stream, N, M, D, c->F, fpb, FS, c->X, ctx->gamma, ctx->post, m->mean,
+                           ctx->stream, N, M, D, c->F, fpb, FS, c->X, ctx->gamma, post, m->mean,
                            ctx->part_mu, ctx->part_var, only_if, m->epoch,
                            (mfma && G <= MS_MAXG) ? m->scls : (const int *)nullptr, m->Mp);
         if ((rc = launch_ok("k_mixstats"))) return rc;
@@ -1741,7 +1742,7 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
         ra.otile = ra.Pm > 0 ? m->otile : nullptr;
         ra.tnext = m->tnext;
         ra.scls = m->scls;
-        ra.X = c->X; ra.gamma = ctx->gamma; ra.post = ctx->post; ra.F = c->F;
+        ra.X = c->X; ra.gamma = ctx->gamma; ra.post = post; ra.F = c->F;
         // rounding bound of a sum of `len` terms accumulated in sequence (a wave's share of the
         // frames) and then over the partials: (len + partials) * eps, doubled
         ra.kappa = 2.0 * 1.1102230246251565e-16 * ((double)c->F / (double)(ctx->cus * MSM_WAVES) + 2.0 * ctx->cus + 64.0);
@@ -1780,7 +1781,7 @@ extern "C" int ghmm_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghm
         ghmm_set_error("call ghmm_emission(want_post=1), ghmm_forward and ghmm_backward first");
         return GHMM_ERR_ARG;
     }
-    return run_accumulate(ctx, m, c, s);
+    return run_accumulate(ctx, m, c, s, ctx->post);
 }
 
 static int fetch_impl(ghmm_ctx *ctx, int which, bool whole, size_t first, double *host, size_t n)
@@ -1856,14 +1857,14 @@ extern "C" int ghmm_estep(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
     int rc = use(ctx);
     if (rc || (rc = check_pair(m, c)) || (rc = check_stats(m, s))) return rc;
     if ((rc = ws_frames(ctx, m, c, true)) || (rc = ws_fb(ctx, m, c))) return rc;
-    if ((rc = run_emission(ctx, m, c, ctx->robust ? 1 : 0, true))) return rc;
+    if ((rc = run_emission(ctx, m, c, ctx->robust ? 1 : 0, ctx->b, ctx->post))) return rc;
     bool fused = false;
     if ((rc = run_scan_combine(ctx, m, c, &fused))) return rc;
     if (!fused) {
         if ((rc = run_forward(ctx, m, c, true))) return rc;
         if ((rc = run_backward(ctx, m, c, false))) return rc; // beta^ on demand (ghmm_fetch)
     }
-    return run_accumulate(ctx, m, c, s);
+    return run_accumulate(ctx, m, c, s, ctx->post);
 }
 
 extern "C" int ghmm_mstep(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *s)
@@ -1939,6 +1940,11 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
     HIP_TRY(hipMemsetAsync(ctx->loglik, 0, (size_t)c->U * 8, ctx->stream));
     ghmm_stats *st = nullptr;
     if ((rc = ghmm_stats_create(ctx, N, M, D, &st))) return rc;
+    struct stats_guard { // the passes' statistics vector goes on every way out
+        ghmm_ctx *ctx;
+        ghmm_stats *st;
+        ~stats_guard() { ghmm_stats_destroy(ctx, st); }
+    } guard{ctx, st};
     const size_t ns = st->n;
     std::vector<double> sv(ns), A((size_t)N * N), cw((size_t)G, 1.0 / M), cells((size_t)G * D, 0.0),
         ones((size_t)G * D, 1.0), det1((size_t)G, 1.0), dist((size_t)G, 0.0);
@@ -1955,19 +1961,13 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
             else a = 1.0 / (double)(delta + 1);
             A[(size_t)i * N + j] = a;
         }
-    const int64_t saved_kernels = ctx->kernels;
     // The k-means passes only need the cells' means (a plain quotient of sums) and the ORDER of
     // their distortions: they run on the context's tier (matrix-core sums, 0.08 ms a pass).  The
     // last pass gives the model's variances: direct-form statistics (x - mean)^2 on the vector
     // ALU, like the reference takes them (0.7 ms).
     bool first_pass = true;
-    auto pass = [&](int n_cells, bool exact) -> int {
-        ctx->kernels = exact ? 1 : saved_kernels;
-        // (only the cells' means change from pass to pass)
-        int r = first_pass ? ghmm_model_set(ctx, m, A.data(), cw.data(), cells.data(), ones.data(), det1.data())
-                           : model_set_means(ctx, m, cells.data());
-        first_pass = false;
-        if (r) return r;
+    // every frame to the nearest of its state's n_cells cells: one-hot rows into gamma and post
+    auto classify = [&](int n_cells) -> int {
         {
             kscope ks(ctx, GHMM_K_PREPARE);
             int FR = IC_FRAMES; // frames per block: their copy in LDS stays under 48 KB
@@ -1976,7 +1976,15 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
                                (size_t)FR * (D | 1) * sizeof(double), ctx->stream, N, M, D, n_cells,
                                c->U, c->F, FR, c->X, c->off, m->mean, ctx->gamma, ctx->post);
         }
-        if ((r = launch_ok("k_init_classify")) || (r = run_accumulate(ctx, m, c, st))) return r;
+        return launch_ok("k_init_classify");
+    };
+    auto pass = [&](int n_cells, bool exact) -> int {
+        // (only the cells' means change from pass to pass)
+        int r = first_pass ? ghmm_model_set(ctx, m, A.data(), cw.data(), cells.data(), ones.data(), det1.data())
+                           : model_set_means(ctx, m, cells.data());
+        first_pass = false;
+        if (r) return r;
+        if ((r = classify(n_cells)) || (r = run_accumulate(ctx, m, c, st, ctx->post, exact))) return r;
         // a corpus sharded over ranks: the cell sums of all shards (every rank then does the
         // same bookkeeping on the same numbers)
         if (comm && (r = ghmm_stats_allreduce(ctx, st, comm))) return r;
@@ -2005,11 +2013,6 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
         for (int l = 0; l < D; l++) ck[(size_t)to * D + l] = ck[(size_t)from * D + l] * 1.005;
         for (int l = 0; l < D; l++) ck[(size_t)from * D + l] = ck[(size_t)from * D + l] * 0.995;
     };
-    auto finish = [&](int r) {
-        ctx->kernels = saved_kernels;
-        ghmm_stats_destroy(ctx, st);
-        return r;
-    };
     bool dev_done = false;
     if (M <= INIT_MAXM) {
         // The k-means rounds without a trip to the host: a pass leaves the cell sums in `st`,
@@ -2028,27 +2031,18 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
                 m->prep_mark = ++ctx->launch_mark;
                 if ((r = model_prepare(ctx, m, true))) return r;
             }
-            {
-                kscope ks(ctx, GHMM_K_PREPARE);
-                int FR = IC_FRAMES;
-                while (FR > 1 && (size_t)FR * (D | 1) * sizeof(double) > 48 * 1024) FR /= 2;
-                hipLaunchKernelGGL(k_init_classify, dim3((unsigned)((c->F + FR - 1) / FR)), dim3(256),
-                                   (size_t)FR * (D | 1) * sizeof(double), ctx->stream, N, M, D, n_cells,
-                                   c->U, c->F, FR, c->X, c->off, m->mean, ctx->gamma, ctx->post);
-            }
-            if ((r = launch_ok("k_init_classify")) || (r = run_accumulate(ctx, m, c, st))) return r;
+            if ((r = classify(n_cells)) || (r = run_accumulate(ctx, m, c, st, ctx->post))) return r;
             if (comm && (r = ghmm_stats_allreduce(ctx, st, comm))) return r;
             hipLaunchKernelGGL(k_init_cells, dim3((unsigned)N), dim3(64), 0, ctx->stream, N, M, D, n_cells,
                                do_split, first ? 1 : 0, st->v, m->mean);
             return launch_ok("k_init_cells");
         };
-        ctx->kernels = saved_kernels;
-        if ((rc = dev_pass(1, 1 < M ? 1 : 0, true))) return finish(rc);
+        if ((rc = dev_pass(1, 1 < M ? 1 : 0, true))) return rc;
         int nc = 1;
         while (nc < M) {
             nc = (2 * nc < M) ? 2 * nc : M;
             for (int it = 0; it < 3; it++)
-                if ((rc = dev_pass(nc, (it == 2 && nc < M) ? 1 : 0, false))) return finish(rc);
+                if ((rc = dev_pass(nc, (it == 2 && nc < M) ? 1 : 0, false))) return rc;
         }
         // the final means, for the last (direct-form) pass's bookkeeping below
         HIP_TRY(hipMemcpyAsync(cells.data(), m->mean, (size_t)G * D * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2058,7 +2052,7 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
     }
     if (!dev_done) {
     // one cell per state: the mean of the state's frames
-    if ((rc = pass(1, false))) return finish(rc);
+    if ((rc = pass(1, false))) return rc;
     for (int k = 0; k < N; k++)
         for (int l = 0; l < D; l++)
             cells[((size_t)k * M) * D + l] = num_mu[((size_t)k * M) * D + l] / num_c[(size_t)k * M];
@@ -2075,7 +2069,7 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
         }
         n_cells = (2 * n_cells < M) ? 2 * n_cells : M;
         for (int it = 0; it < 3; it++) { // TF:1043
-            if ((rc = pass(n_cells, false))) return finish(rc);
+            if ((rc = pass(n_cells, false))) return rc;
             for (int k = 0; k < N; k++) {
                 double *ck = cells.data() + (size_t)k * M * D;
                 for (int j = 0; j < n_cells; j++)
@@ -2092,7 +2086,7 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
     }
     } // (!dev_done)
     // per-cell variance around the final means and cell weights (TF:883-933)
-    if ((rc = pass(M, true))) return finish(rc);
+    if ((rc = pass(M, true))) return rc;
     std::vector<double> iv((size_t)G * D), dt((size_t)G);
     for (int k = 0; k < N; k++) {
         double dur = 0.0, sum = 0.0;
@@ -2115,10 +2109,7 @@ extern "C" int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c
         }
         for (int j = 0; j < M; j++) cw[(size_t)k * M + j] /= sum;
     }
-    ctx->kernels = saved_kernels;
-    rc = ghmm_model_set(ctx, m, A.data(), cw.data(), cells.data(), iv.data(), dt.data());
-    ghmm_stats_destroy(ctx, st);
-    return rc;
+    return ghmm_model_set(ctx, m, A.data(), cw.data(), cells.data(), iv.data(), dt.data());
 }
 
 extern "C" int ghmm_score(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, double *loglik_host)
@@ -2127,7 +2118,7 @@ extern "C" int ghmm_score(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, double *
     if (rc || (rc = check_pair(m, c))) return rc;
     ARG_CHECK(loglik_host || c->U == 0, "null destination");
     if ((rc = ws_frames(ctx, m, c, false)) || (rc = ws_fb(ctx, m, c))) return rc;
-    if ((rc = run_emission(ctx, m, c, ctx->robust ? 1 : 0, false))) return rc;
+    if ((rc = run_emission(ctx, m, c, ctx->robust ? 1 : 0, ctx->b, nullptr))) return rc;
     if ((rc = run_forward(ctx, m, c, false, true))) return rc;
     if (c->U)
         HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost,
@@ -2146,9 +2137,9 @@ extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_
     if ((rc = fb_lanes(m, &L))) return rc;
     ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
     if ((rc = ws_frames(ctx, m, c, false))) return rc;
-    if ((rc = dev_grow(&ctx->psi, &ctx->cap_psi, (size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
-    if ((rc = dev_grow(&ctx->path, &ctx->cap_path, (size_t)c->F))) return rc;
-    if ((rc = run_emission(ctx, m, c, 2, false))) return rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
+    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
+    if ((rc = run_emission(ctx, m, c, 2, ctx->b, nullptr))) return rc;
     if (c->U) {
         if (L == 0) { // one wave per utterance
             if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
@@ -2202,33 +2193,25 @@ static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpu
 {
     int rc;
     const size_t FN = (size_t)corpora[0]->F * models[0]->N;
-    if ((int)ctx->post_s.size() < P) {
-        ctx->post_s.resize((size_t)P, nullptr);
-        ctx->cap_post_s.resize((size_t)P, 0);
-    }
     for (int p = 0; p < P; p++) {
         if ((rc = ws_frames(ctx, models[p], corpora[p], false))) return rc;
         if (want_post &&
-            (rc = dev_grow(&ctx->post_s[p], &ctx->cap_post_s[p], (size_t)corpora[p]->F * models[p]->N * models[p]->M)))
+            (rc = ctx->post_s[p].grow((size_t)corpora[p]->F * models[p]->N * models[p]->M)))
             return rc;
     }
-    if ((rc = dev_grow(&ctx->b_stream, &ctx->cap_b_stream, FN))) return rc;
-    double *const b_all = ctx->b, *const post_own = ctx->post;
+    if ((rc = ctx->b_stream.grow(FN))) return rc;
     for (int p = 0; p < P && !rc; p++) {
-        ctx->b = p == 0 ? b_all : ctx->b_stream;
-        ctx->post = want_post ? ctx->post_s[p] : nullptr;
-        rc = run_emission(ctx, models[p], corpora[p], 0, want_post);
+        rc = run_emission(ctx, models[p], corpora[p], 0, p == 0 ? ctx->b : ctx->b_stream,
+                          want_post ? ctx->post_s[p] : nullptr);
         if (!rc && p > 0 && FN) {
             long long blocks = ((long long)FN + 255) / 256;
             if (blocks > 4096) blocks = 4096;
             kscope ks(ctx, GHMM_K_EMISSION);
             hipLaunchKernelGGL(k_mul_streams, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (long long)FN,
-                               b_all, ctx->b_stream);
+                               ctx->b, ctx->b_stream);
             rc = launch_ok("k_mul_streams");
         }
     }
-    ctx->b = b_all;
-    ctx->post = post_own; // (not written: run_emission has cleared post_valid)
     // the product belongs to stream 0's (model, corpus) pair as far as the row API is concerned
     ctx->em_m = models[0];
     ctx->em_c = corpora[0];
@@ -2253,12 +2236,7 @@ extern "C" int ghmm_estep_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
     if ((rc = run_backward(ctx, models[0], corpora[0], false))) return rc;
     // calc_mix_param per stream (TF:306-315) with the common gamma; the transition sums, den_c,
     // log P and the exemplar count go into every stream's vector
-    double *const post_own = ctx->post;
-    for (int p = 0; p < P && !rc; p++) {
-        ctx->post = ctx->post_s[p];
-        rc = run_accumulate(ctx, models[p], corpora[p], stats[p]);
-    }
-    ctx->post = post_own;
+    for (int p = 0; p < P && !rc; p++) rc = run_accumulate(ctx, models[p], corpora[p], stats[p], ctx->post_s[p]);
     return rc;
 }
 
@@ -2279,56 +2257,7 @@ extern "C" int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
 }
 
 // ------------------------------------------------ a vocabulary in one pass
-// ghmm_score_batch's helpers; the full-covariance batch calls (ghmm_fullhost.hpp: fvocab_begin builds the
-// same tables for several feature streams) share vocab_scores_out.
-
-// every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
-template <class MODEL>
-static int vocab_shape(MODEL *const *models, int n_models, const char *what, int *NS, int *Nmax)
-{
-    const int M = models[0]->M, D = models[0]->D;
-    *NS = *Nmax = 0;
-    for (int k = 0; k < n_models; k++) {
-        if (models[k]->M != M || models[k]->D != D) {
-            ghmm_set_error("%s: every model must have the same M and D", what);
-            return GHMM_ERR_UNSUPPORTED;
-        }
-        *NS += models[k]->N;
-        *Nmax = models[k]->N > *Nmax ? models[k]->N : *Nmax;
-    }
-    return GHMM_OK;
-}
-
-// The pass's two tables, built on the host and uploaded into one context buffer (*buf, grown on
-// demand): the words' recursions (N and the offset of the word's states in b; fill() adds A or log A)
-// and the gather kernel's sources (the word's Gaussians g0 .. g0 + ng of the concatenated model;
-// fill() adds the parameter pointers).
-template <class SRC, class MODEL, class FILL>
-static int vocab_tables(ghmm_ctx *ctx, MODEL *const *models, int n_models, char **buf, size_t *cap, FILL fill,
-                        const fwd_model **dtab, const SRC **dsrc)
-{
-    int rc;
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<SRC> src((size_t)n_models);
-    int go = 0, so = 0;
-    for (int k = 0; k < n_models; k++) {
-        const MODEL *m = models[k];
-        fill(m, tab[k], src[k]);
-        tab[k].N = m->N;
-        tab[k].bo = so;
-        src[k].g0 = go; src[k].ng = m->N * m->M;
-        go += m->N * m->M;
-        so += m->N;
-    }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(SRC);
-    if ((rc = dev_grow(buf, cap, tab_bytes + src_bytes + 16))) return rc;
-    *dtab = (const fwd_model *)*buf;
-    *dsrc = (const SRC *)(*buf + ((tab_bytes + 15) / 16) * 16);
-    // (the tables leave pageable host vectors: the copies complete before the call returns them)
-    HIP_TRY(hipMemcpyAsync(*buf, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync((void *)*dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GHMM_OK;
-}
+// ghmm_score_batch; the full-covariance batch calls (ghmm_fullhost.hpp) share vocab_scores_out.
 
 // the pass's scores, bt_ll[n_models][U], to the host; waits for the stream
 static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, double *host)
@@ -2346,9 +2275,17 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
     ARG_CHECK(models && n_models > 0 && c, "null argument");
     ARG_CHECK(loglik_host || c->U == 0, "null destination");
     for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
+    // every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
     const int M = models[0]->M, D = models[0]->D;
-    int NS, Nmax;
-    if ((rc = vocab_shape(models, n_models, __func__, &NS, &Nmax))) return rc;
+    int NS = 0, Nmax = 0;
+    for (int k = 0; k < n_models; k++) {
+        if (models[k]->M != M || models[k]->D != D) {
+            ghmm_set_error("%s: every model must have the same M and D", __func__);
+            return GHMM_ERR_UNSUPPORTED;
+        }
+        NS += models[k]->N;
+        Nmax = models[k]->N > Nmax ? models[k]->N : Nmax;
+    }
     if (D != c->D) {
         ghmm_set_error("models have %d coefficients per frame, corpus has %d", D, c->D);
         return GHMM_ERR_ARG;
@@ -2378,24 +2315,37 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
         HIP_TRY(hipMemsetAsync(ctx->bt_cat->A, 0, (size_t)NS * NS * 8, ctx->stream));
     }
     ghmm_model *cat = ctx->bt_cat;
-    if ((rc = dev_grow(&ctx->bt_scale, &ctx->cap_bt_scale, (size_t)n_models * c->F + 1)) ||
-        (rc = dev_grow(&ctx->bt_sinv, &ctx->cap_bt_sinv, (size_t)n_models * c->F + 1)) ||
-        (rc = dev_grow(&ctx->bt_ll, &ctx->cap_bt_ll, (size_t)n_models * c->U)))
+    if ((rc = ctx->bt_scale.grow((size_t)n_models * c->F + 1)) ||
+        (rc = ctx->bt_sinv.grow((size_t)n_models * c->F + 1)) ||
+        (rc = ctx->bt_ll.grow((size_t)n_models * c->U)))
         return rc;
-    const fwd_model *dtab;
-    const gather_src *dsrc;
-    const auto fill = [](const ghmm_model *m, fwd_model &t, gather_src &s) {
-        t.A = m->A;
-        s.c = m->c; s.mean = m->mean; s.inv_var = m->inv_var; s.det = m->det;
-    };
-    if ((rc = vocab_tables(ctx, models, n_models, &ctx->bt_tab, &ctx->cap_bt_tab, fill, &dtab, &dsrc))) return rc;
+    // The pass's two tables, built on the host and uploaded into one context buffer: the words'
+    // recursions (A, N and the offset of the word's states in b) and the gather kernel's sources (the
+    // word's parameters, for the Gaussians g0 .. g0 + ng of the concatenated model).
+    std::vector<fwd_model> tab((size_t)n_models);
+    std::vector<gather_src> src((size_t)n_models);
+    int go = 0, so = 0;
+    for (int k = 0; k < n_models; k++) {
+        const ghmm_model *m = models[k];
+        tab[k] = {m->A, m->N, so};
+        src[k] = {m->c, m->mean, m->inv_var, m->det, go, m->N * m->M};
+        go += m->N * m->M;
+        so += m->N;
+    }
+    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(gather_src);
+    if ((rc = ctx->bt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
+    const fwd_model *dtab = (const fwd_model *)ctx->bt_tab.p;
+    const gather_src *dsrc = (const gather_src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
+    // (the tables leave pageable host vectors: the copies complete before the call returns them)
+    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((void *)dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_gather_models, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
                        cat->mean, cat->inv_var, cat->det);
     if ((rc = launch_ok("k_gather_models"))) return rc;
     cat->epoch++;
     cat->prep_mark = ++ctx->launch_mark;
     if ((rc = model_prepare(ctx, cat, true)) || (rc = ws_frames(ctx, cat, c, false)) ||
-        (rc = run_emission(ctx, cat, c, 0, false)))
+        (rc = run_emission(ctx, cat, c, 0, ctx->b, nullptr)))
         return rc;
     {
         const lane_grid lg(Nmax, c->U);
