@@ -300,9 +300,9 @@ int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghm
  * GHMM_ERR_UNSUPPORTED; a null array or entry, n_streams outside the range, streams that differ in N, in
  * the utterance count or in a length, a corpus of another D than its model, or a statistics vector that
  * is full-covariance or not of its stream's shape gives GHMM_ERR_ARG.
- * Viterbi and the batched vocabulary calls on several streams exist for the full-covariance models only:
- * see "several-stream vocabularies" below (ghmm_viterbi_full_streams, ghmm_*_full_streams_batch,
- * ghmm_recognise_full_streams). */
+ * Viterbi and the batched vocabulary calls on several streams are in the section "several-stream
+ * vocabularies of diagonal models" below (ghmm_viterbi_streams, ghmm_score_streams_batch,
+ * ghmm_viterbi_streams_batch, ghmm_recognise_streams). */
 int ghmm_estep_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
                        int n_streams, ghmm_stats *const *stats);
 /* forward score per utterance of a P-stream model (RF:349-366) */
@@ -316,6 +316,79 @@ int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *co
  * one byte per frame; it is widened to int32 on the way into path_host.) */
 int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
                  double *score_host);
+
+/* ------------- several-stream vocabularies of diagonal models: Viterbi, batched scoring and word decoding */
+
+/* ghmm_viterbi's lattice on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...): every
+ * term is the log b that ghmm_viterbi's emission launch makes for that stream alone, stream 0 into b,
+ * every later stream into a buffer of its own that one IEEE addition per entry folds into b, the earlier
+ * streams' sum on the left; NaN and +-inf propagate as the addition gives them.  The transitions are
+ * models[0]'s log A; up to 255 states as in ghmm_viterbi (beyond 64 the one-wave-per-utterance kernel).
+ * path_host[F], score_host[U]; T = 0 scores 0.  n_streams == 1 is ghmm_viterbi itself, the same bits.
+ * Afterwards GHMM_BUF_B holds the summed log b[F][N]; the row API does not reuse it and GHMM_BUF_POST
+ * gives GHMM_ERR_ARG.  The folds count under GHMM_K_EMISSION: 2 n_streams - 1 launches there, one under
+ * GHMM_K_VITERBI.  The checks and refusals are ghmm_score_streams's, each before anything is launched or
+ * written, and a null destination with U > 0 gives GHMM_ERR_ARG; U = 0 touches nothing.  Synchronises. */
+int ghmm_viterbi_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
+                         int n_streams, int32_t *path_host, double *score_host);
+/* A vocabulary of n_models words on n_streams streams in one pass, for the three calls below:
+ *   models[k * n_streams + p] = stream p of word k;  corpora[p] = stream p of the utterances;
+ *   the streams of one word have the same N, the transitions are stream 0's;
+ *   for every stream p all words share M_p and D_p;
+ *   the corpora have the same utterance count and lengths, corpora[p] has D_p coefficients.
+ * Per stream one gather of the words' Gaussians into that stream's concatenated vocabulary (kept in the
+ * context between calls, rebuilt when its shape changes; stream 0's is the one ghmm_score_batch uses) and
+ * one emission launch over it, stream 0 into b[F][NS] (NS = the sum of the words' N), every later stream
+ * into a buffer of its own that one launch folds into b, by multiplication or, on log b, by addition,
+ * as in ghmm_score_streams and ghmm_viterbi_streams; then ONE lattice launch over every (word, utterance)
+ * pair on word k's columns and stream 0's A or log A.  Under GHMM_OPT_TIMING: 2 n_streams - 1 launches
+ * under GHMM_K_EMISSION (n_streams emissions, n_streams - 1 folds), one under GHMM_K_FORWARD or
+ * GHMM_K_VITERBI; one wait for the stream.
+ * out[k*U + u] is what the matching per-word call gives word k alone (ghmm_score_streams with its
+ * final-state term, RF:349-366; ghmm_viterbi_streams' score): bit for bit with GHMM_OPT_KERNELS = 1,
+ * where every state's density comes from its own Gaussians alone; under the matrix-core emission the
+ * Gaussians are evaluated around the concatenated vocabulary's offsets, in tiles of 16 that may straddle
+ * two words, so a score agrees with the per-word call's to rounding (1e-12 relative) and identical
+ * Gaussians at different tile positions need not give identical bits: an exact tie between two words
+ * is a property of the GHMM_OPT_KERNELS = 1 tier only.
+ * Afterwards GHMM_BUF_B holds the product (or the sum of logs) over [F][NS]; as after ghmm_score_batch the
+ * row API does not reuse it, and GHMM_BUF_POST gives GHMM_ERR_ARG.  U = 0 touches nothing.  A second
+ * identical call repeats every byte.
+ * Refusals, each before anything is launched or written.  GHMM_ERR_ARG: a null array or entry,
+ * n_models < 1, n_streams outside 1..GHMM_MAX_STREAMS, a null destination with U > 0, streams of one
+ * word that differ in N, corpora that differ in the utterance count or in a length, a corpus whose D is
+ * not its stream's.  GHMM_ERR_UNSUPPORTED: words that differ in M_p or D_p for some stream p;
+ * GHMM_OPT_ROBUST set with n_streams > 1; a word of more than 64 states in the two Viterbi calls. */
+/* loglik_host[k*U + u] = ghmm_score_streams of word k: calc_probability with its final-state term
+ * (RF:349-366) on the product of the streams' densities.  n_streams == 1 is ghmm_score_batch itself: the
+ * same bits, the same cached vocabulary, the same two fall-backs (GHMM_OPT_ROBUST, a word of more than
+ * 64 states).  n_streams > 1 and a word of more than 64 states: the word-by-word ghmm_score_streams loop. */
+int ghmm_score_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                             ghmm_corpus *const *corpora, int n_streams, double *loglik_host);
+/* score_host[k*U + u] = ghmm_viterbi_streams' score of word k (no paths); T = 0 scores 0.  Every word has
+ * at most 64 states. */
+int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                               ghmm_corpus *const *corpora, int n_streams, double *score_host);
+/* Which word was it, and how does it align (n_streams >= 1): ghmm_viterbi_streams_batch's score table,
+ * every utterance's winning word picked on the device, and the winner's lattice run again with
+ * back-pointers on the log b already in the workspace, all enqueued without a host round trip and
+ * ended by one wait for the stream.
+ *   score_host[n_models*U]  the batch call's table, bit for bit
+ *   word_host[U]            the winner: best = 0; for k = 1 .. n_models-1 in order, k takes over if
+ *                           score[k] > score[best], or if score[best] is NaN and score[k] is not.  Ties
+ *                           go to the lowest word, a NaN never beats a number, and all NaN or all -inf
+ *                           gives word 0
+ *   path_host[F]            over utterance u's frames, the path of ghmm_viterbi's lattice for word
+ *                           word_host[u] on that word's columns of GHMM_BUF_B (ties take the lowest
+ *                           predecessor); with GHMM_OPT_KERNELS = 1 bit for bit ghmm_viterbi_streams' path
+ *                           of that word
+ * T = 0 scores 0 under every word, gives word 0 and no path entries.  U = 0 touches nothing.  The
+ * vocabulary layout, GHMM_BUF_B afterwards and the refusals are the batch calls' (all three destinations
+ * are needed when U > 0).  The two extra launches count under GHMM_K_VITERBI (three there in all).  A
+ * second identical call repeats every byte. */
+int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                           ghmm_corpus *const *corpora, int n_streams, int32_t *word_host,
+                           int32_t *path_host, double *score_host);
 
 /* ------------------------------------------ the full-covariance recogniser */
 

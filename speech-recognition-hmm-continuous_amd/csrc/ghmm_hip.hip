@@ -146,6 +146,8 @@ struct ghmm_ctx {
     // ---- vocabulary passes
     // ghmm_score_batch: the concatenated vocabulary model and the pass's tables, kept between calls
     ghmm_model *bt_cat = nullptr;
+    // the several-stream vocabulary calls: bt_cat is stream 0's vocabulary, bt_cat_s[p] stream p's (p >= 1)
+    ghmm_model *bt_cat_s[GHMM_MAX_STREAMS] = {};
     dev_buf<char> bt_tab;
     dev_buf<double> bt_scale, bt_sinv, bt_ll;
     // ghmm_score_full_batch: the same for the full-covariance vocabulary (the log P go to bt_ll)
@@ -153,7 +155,7 @@ struct ghmm_ctx {
     // the *_full_streams_batch calls: fbt_cat is stream 0's vocabulary, fbt_cat_s[p] stream p's (p >= 1)
     ghmm_fmodel *fbt_cat_s[GHMM_MAX_STREAMS] = {};
     dev_buf<char> fbt_tab;
-    dev_buf<int> best_word; // ghmm_recognise_full_streams: every utterance's winning word
+    dev_buf<int> best_word; // ghmm_recognise_streams / _full_streams: every utterance's winning word
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     dev_buf<double> b_stream;
@@ -435,6 +437,11 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
         ghmm_model_destroy(ctx, ctx->bt_cat);
         ctx->bt_cat = nullptr;
     }
+    for (ghmm_model *&cat : ctx->bt_cat_s)
+        if (cat) {
+            ghmm_model_destroy(ctx, cat);
+            cat = nullptr;
+        }
     if (ctx->fbt_cat) {
         ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
         ctx->fbt_cat = nullptr;
@@ -2127,19 +2134,18 @@ extern "C" int ghmm_score(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, double *
     return GHMM_OK;
 }
 
-extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
-                            double *score_host)
+// The lattice of ghmm_viterbi on m's log A and the log b[F][N] in the workspace (L from fb_lanes, N <= 255):
+// paths and scores to the host, then the wait for the stream.  viterbi_ws sizes what it writes.
+static int viterbi_ws(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c, int L)
 {
-    int rc = use(ctx);
-    if (rc || (rc = check_pair(m, c))) return rc;
-    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
-    int L;
-    if ((rc = fb_lanes(m, &L))) return rc;
-    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
-    if ((rc = ws_frames(ctx, m, c, false))) return rc;
+    int rc;
     if ((rc = ctx->psi.grow((size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
-    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
-    if ((rc = run_emission(ctx, m, c, 2, ctx->b, nullptr))) return rc;
+    return ctx->path.grow((size_t)c->F);
+}
+
+static int run_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int L, int32_t *path_host, double *score_host)
+{
+    int rc;
     if (c->U) {
         if (L == 0) { // one wave per utterance
             if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
@@ -2161,6 +2167,20 @@ extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_
     }
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
+}
+
+extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
+                            double *score_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_pair(m, c))) return rc;
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(m, &L))) return rc;
+    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
+    if ((rc = ws_frames(ctx, m, c, false)) || (rc = viterbi_ws(ctx, m, c, L))) return rc;
+    if ((rc = run_emission(ctx, m, c, 2, ctx->b, nullptr))) return rc;
+    return run_viterbi(ctx, m, c, L, path_host, score_host);
 }
 
 // ------------------------------------------------------ several feature streams
@@ -2187,9 +2207,26 @@ static int check_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *
     return GHMM_OK;
 }
 
-// emission of every stream; ctx->b ends up holding the product, ctx->post_s[p] stream p's posteriors
+// the fold of one more stream: b (n doubles) takes b_stream into it, by one IEEE multiply per entry or, on
+// log b, one IEEE addition, the earlier streams on the left
+static int fold_stream(ghmm_ctx *ctx, size_t n, bool log_domain)
+{
+    long long blocks = ((long long)n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    kscope ks(ctx, GHMM_K_EMISSION);
+    if (log_domain)
+        hipLaunchKernelGGL(k_add_streams, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (long long)n, ctx->b,
+                           ctx->b_stream);
+    else
+        hipLaunchKernelGGL(k_mul_streams, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (long long)n, ctx->b,
+                           ctx->b_stream);
+    return launch_ok(log_domain ? "k_add_streams" : "k_mul_streams");
+}
+
+// emission of every stream (mode 0, or 2 for log b); ctx->b ends up holding the product (mode 2: the sum
+// of logs), ctx->post_s[p] stream p's posteriors
 static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P,
-                            bool want_post)
+                            bool want_post, int mode = 0)
 {
     int rc;
     const size_t FN = (size_t)corpora[0]->F * models[0]->N;
@@ -2201,16 +2238,9 @@ static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpu
     }
     if ((rc = ctx->b_stream.grow(FN))) return rc;
     for (int p = 0; p < P && !rc; p++) {
-        rc = run_emission(ctx, models[p], corpora[p], 0, p == 0 ? ctx->b : ctx->b_stream,
+        rc = run_emission(ctx, models[p], corpora[p], mode, p == 0 ? ctx->b : ctx->b_stream,
                           want_post ? ctx->post_s[p] : nullptr);
-        if (!rc && p > 0 && FN) {
-            long long blocks = ((long long)FN + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            kscope ks(ctx, GHMM_K_EMISSION);
-            hipLaunchKernelGGL(k_mul_streams, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (long long)FN,
-                               ctx->b, ctx->b_stream);
-            rc = launch_ok("k_mul_streams");
-        }
+        if (!rc && p > 0 && FN) rc = fold_stream(ctx, FN, mode == 2);
     }
     // the product belongs to stream 0's (model, corpus) pair as far as the row API is concerned
     ctx->em_m = models[0];
@@ -2257,7 +2287,9 @@ extern "C" int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
 }
 
 // ------------------------------------------------ a vocabulary in one pass
-// ghmm_score_batch; the full-covariance batch calls (ghmm_fullhost.hpp) share vocab_scores_out.
+// ghmm_score_batch and the several-stream vocabulary calls (ghmm_score_streams_batch,
+// ghmm_viterbi_streams_batch, ghmm_recognise_streams; definitions in include/ghmm.h); the full-covariance
+// batch calls (ghmm_fullhost.hpp) share vocab_scores_out.
 
 // the pass's scores, bt_ll[n_models][U], to the host; waits for the stream
 static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, double *host)
@@ -2265,6 +2297,109 @@ static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, d
     HIP_TRY(hipMemcpyAsync(host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
+}
+
+// A vocabulary of n_models words on P feature streams (models[k * P + p] = stream p of word k;
+// ghmm_score_batch passes P = 1): NS = its states, Nmax = the largest word's, cats[p] = stream p's
+// concatenated model (NS states x M_p mixtures, transitions unused), dtab = the table of the words'
+// recursions on the device.  The diagonal sibling of fvocab (ghmm_fullhost.hpp).
+struct dvocab {
+    int NS = 0, Nmax = 0;
+    const fwd_model *dtab = nullptr;
+    ghmm_model *cats[GHMM_MAX_STREAMS] = {};
+};
+
+// The concatenated models live in the context from one call to the next (a recogniser scores batch after
+// batch against one vocabulary: creating and freeing twenty device buffers per call was 0.75 ms of a
+// 0.9 ms call), ctx->bt_cat for stream 0 and ctx->bt_cat_s[p] for the later ones, each rebuilt when its
+// shape changes; the words' parameters are gathered into each by ONE launch, and it is prepared like a
+// model just set.  The pass's tables are built on the host and uploaded into one context buffer: the
+// words' recursions (dtab[k].A = word k's A, or its log A with log_domain, stream 0's; N; the offset of
+// the word's states in b) and per stream the gather kernel's sources (the word's parameters, for the
+// Gaussians g0 .. g0 + ng of that stream's concatenated model).  v->NS and v->Nmax are the caller's.
+static int vocab_gather(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, int P, bool log_domain, dvocab *v)
+{
+    int rc;
+    for (int p = 0; p < P; p++) {
+        ghmm_model **slot = p ? &ctx->bt_cat_s[p] : &ctx->bt_cat;
+        const int M = models[p]->M, D = models[p]->D;
+        if (*slot && ((*slot)->N != v->NS || (*slot)->M != M || (*slot)->D != D)) {
+            ghmm_model_destroy(ctx, *slot);
+            *slot = nullptr;
+        }
+        if (!*slot) {
+            if ((rc = ghmm_model_create(ctx, v->NS, M, D, slot))) return rc;
+            HIP_TRY(hipMemsetAsync((*slot)->A, 0, (size_t)v->NS * v->NS * 8, ctx->stream));
+        }
+        v->cats[p] = *slot;
+    }
+    std::vector<fwd_model> tab((size_t)n_models);
+    std::vector<gather_src> src((size_t)n_models * P);
+    for (int p = 0; p < P; p++) {
+        int go = 0, so = 0;
+        for (int k = 0; k < n_models; k++) {
+            const ghmm_model *m = models[(size_t)k * P + p];
+            if (p == 0) tab[k] = {log_domain ? m->logA : m->A, m->N, so};
+            src[(size_t)p * n_models + k] = {m->c, m->mean, m->inv_var, m->det, go, m->N * m->M};
+            go += m->N * m->M;
+            so += m->N;
+        }
+    }
+    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(gather_src);
+    if ((rc = ctx->bt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
+    v->dtab = (const fwd_model *)ctx->bt_tab.p;
+    const gather_src *dsrc = (const gather_src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
+    // (the tables leave pageable host vectors: the copies complete before the call returns them)
+    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((void *)dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    for (int p = 0; p < P; p++) {
+        ghmm_model *cat = v->cats[p];
+        hipLaunchKernelGGL(k_gather_models, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, cat->D,
+                           dsrc + (size_t)p * n_models, cat->c, cat->mean, cat->inv_var, cat->det);
+        if ((rc = launch_ok("k_gather_models"))) return rc;
+        cat->epoch++;
+        cat->prep_mark = ++ctx->launch_mark;
+        if ((rc = model_prepare(ctx, cat, true))) return rc;
+    }
+    return GHMM_OK;
+}
+
+// One emission launch per stream over its concatenated model (mode 0, or 2 for log b): stream 0 into the
+// workspace's b[F][NS], every later stream into b_stream and from there folded into b.  Column bo_k + i
+// then holds what streams_emission leaves in column i for word k alone, up to the rounding of the
+// matrix-core emission (its offsets are the concatenated model's; GHMM_OPT_KERNELS = 1: the same bits).
+static int vocab_emission(ghmm_ctx *ctx, const dvocab &v, ghmm_corpus *const *corpora, int P, int mode)
+{
+    int rc;
+    const size_t FN = (size_t)corpora[0]->F * v.NS;
+    if ((rc = ws_frames(ctx, v.cats[0], corpora[0], false))) return rc;
+    if (P > 1 && (rc = ctx->b_stream.grow(FN))) return rc;
+    for (int p = 0; p < P; p++) {
+        if ((rc = run_emission(ctx, v.cats[p], corpora[p], mode, p == 0 ? ctx->b : ctx->b_stream, nullptr))) return rc;
+        if (p > 0 && FN && (rc = fold_stream(ctx, FN, mode == 2))) return rc;
+    }
+    // the workspace b belongs to the concatenated vocabulary: the row API does not reuse it
+    ctx->em_m = v.cats[0];
+    ctx->em_c = corpora[0];
+    ctx->em_epoch = v.cats[0]->epoch;
+    ctx->b_is_log = true;
+    return GHMM_OK;
+}
+
+// k_forward_multi over the n_models entries of v.dtab on the b in the workspace: log P with the
+// final-state term into bt_ll
+static int vocab_forward(ghmm_ctx *ctx, const dvocab &v, int n_models, const ghmm_corpus *c)
+{
+    int rc;
+    if ((rc = ctx->bt_scale.grow((size_t)n_models * c->F + 1)) ||
+        (rc = ctx->bt_sinv.grow((size_t)n_models * c->F + 1)))
+        return rc;
+    const lane_grid lg(v.Nmax, c->U);
+    kscope ks(ctx, GHMM_K_FORWARD);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                           0, ctx->stream, c->U, v.NS, c->F, v.dtab, ctx->b, c->off, ctx->bt_scale,
+                                           ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
+    return launch_ok("k_forward_multi");
 }
 
 extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
@@ -2277,21 +2412,21 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
     for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
     // every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
     const int M = models[0]->M, D = models[0]->D;
-    int NS = 0, Nmax = 0;
+    dvocab v;
     for (int k = 0; k < n_models; k++) {
         if (models[k]->M != M || models[k]->D != D) {
             ghmm_set_error("%s: every model must have the same M and D", __func__);
             return GHMM_ERR_UNSUPPORTED;
         }
-        NS += models[k]->N;
-        Nmax = models[k]->N > Nmax ? models[k]->N : Nmax;
+        v.NS += models[k]->N;
+        v.Nmax = models[k]->N > v.Nmax ? models[k]->N : v.Nmax;
     }
     if (D != c->D) {
         ghmm_set_error("models have %d coefficients per frame, corpus has %d", D, c->D);
         return GHMM_ERR_ARG;
     }
     if (c->U == 0) return GHMM_OK;
-    if (Nmax > 64) { // the one-launch vocabulary loop holds one state per lane: word by word instead
+    if (v.Nmax > 64) { // the one-launch vocabulary loop holds one state per lane: word by word instead
         for (int k = 0; k < n_models; k++)
             if ((rc = ghmm_score(ctx, models[k], c, loglik_host + (size_t)k * c->U))) return rc;
         return GHMM_OK;
@@ -2302,60 +2437,178 @@ extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_
             if ((rc = ghmm_score(ctx, models[k], c, loglik_host + (size_t)k * c->U))) return rc;
         return GHMM_OK;
     }
-    // The concatenated model: NS states x M mixtures (transition matrix unused).  It and the
-    // pass's tables live in the context from one call to the next (a recogniser scores batch after
-    // batch against one vocabulary: creating and freeing twenty device buffers per call was 0.75 ms
-    // of a 0.9 ms call); the words' parameters are gathered into it by ONE launch.
-    if (ctx->bt_cat && (ctx->bt_cat->N != NS || ctx->bt_cat->M != M || ctx->bt_cat->D != D)) {
-        ghmm_model_destroy(ctx, ctx->bt_cat);
-        ctx->bt_cat = nullptr;
-    }
-    if (!ctx->bt_cat) {
-        if ((rc = ghmm_model_create(ctx, NS, M, D, &ctx->bt_cat))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->bt_cat->A, 0, (size_t)NS * NS * 8, ctx->stream));
-    }
-    ghmm_model *cat = ctx->bt_cat;
-    if ((rc = ctx->bt_scale.grow((size_t)n_models * c->F + 1)) ||
-        (rc = ctx->bt_sinv.grow((size_t)n_models * c->F + 1)) ||
-        (rc = ctx->bt_ll.grow((size_t)n_models * c->U)))
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, 1, false, &v)) || (rc = vocab_emission(ctx, v, &c, 1, 0)) ||
+        (rc = vocab_forward(ctx, v, n_models, c)))
         return rc;
-    // The pass's two tables, built on the host and uploaded into one context buffer: the words'
-    // recursions (A, N and the offset of the word's states in b) and the gather kernel's sources (the
-    // word's parameters, for the Gaussians g0 .. g0 + ng of the concatenated model).
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<gather_src> src((size_t)n_models);
-    int go = 0, so = 0;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
+}
+
+// ---- several feature streams
+
+extern "C" int ghmm_viterbi_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
+                                    int P, int32_t *path_host, double *score_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_streams(ctx, models, corpora, P))) return rc;
+    if (P == 1) return ghmm_viterbi(ctx, models[0], corpora[0], path_host, score_host);
+    ghmm_model *m = models[0];
+    ghmm_corpus *c = corpora[0];
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(m, &L))) return rc;
+    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
+    if (c->U == 0) return GHMM_OK;
+    if ((rc = viterbi_ws(ctx, m, c, L))) return rc;
+    if ((rc = streams_emission(ctx, models, corpora, P, false, 2))) return rc;
+    return run_viterbi(ctx, m, c, L, path_host, score_host);
+}
+
+// The checks of the three several-stream vocabulary calls (`what` = the entry point's name in their
+// texts; lanes_only: a word of more than 64 states is refused), each before anything is launched or
+// written; fills v->NS and v->Nmax.  The diagonal sibling of fvocab_begin's first half.
+static int vocab_check(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                       bool have_dest, bool lanes_only, const char *what, dvocab *v)
+{
+    int rc;
+    ARG_CHECK_AS(what, models && n_models > 0 && corpora, "null argument");
+    if (P < 1 || P > GHMM_MAX_STREAMS) {
+        ghmm_set_error("%s: 1 to %d feature streams (asked: %d)", what, GHMM_MAX_STREAMS, P);
+        return GHMM_ERR_ARG;
+    }
+    for (int p = 0; p < P; p++) ARG_CHECK_AS(what, corpora[p], "null argument");
+    const ghmm_corpus *c = corpora[0];
+    ARG_CHECK_AS(what, have_dest || c->U == 0, "null destination");
+    for (int k = 0; k < n_models * P; k++) ARG_CHECK_AS(what, models[k], "null model");
+    v->NS = v->Nmax = 0;
     for (int k = 0; k < n_models; k++) {
-        const ghmm_model *m = models[k];
-        tab[k] = {m->A, m->N, so};
-        src[k] = {m->c, m->mean, m->inv_var, m->det, go, m->N * m->M};
-        go += m->N * m->M;
-        so += m->N;
+        const int N = models[(size_t)k * P]->N;
+        for (int p = 1; p < P; p++)
+            if (models[(size_t)k * P + p]->N != N) {
+                ghmm_set_error("%s: word %d: stream %d has %d states, stream 0 has %d", what, k, p,
+                               models[(size_t)k * P + p]->N, N);
+                return GHMM_ERR_ARG;
+            }
+        v->NS += N;
+        v->Nmax = N > v->Nmax ? N : v->Nmax;
     }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(gather_src);
-    if ((rc = ctx->bt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
-    const fwd_model *dtab = (const fwd_model *)ctx->bt_tab.p;
-    const gather_src *dsrc = (const gather_src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
-    // (the tables leave pageable host vectors: the copies complete before the call returns them)
-    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync((void *)dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_models, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D, dsrc, cat->c,
-                       cat->mean, cat->inv_var, cat->det);
-    if ((rc = launch_ok("k_gather_models"))) return rc;
-    cat->epoch++;
-    cat->prep_mark = ++ctx->launch_mark;
-    if ((rc = model_prepare(ctx, cat, true)) || (rc = ws_frames(ctx, cat, c, false)) ||
-        (rc = run_emission(ctx, cat, c, 0, ctx->b, nullptr)))
+    for (int p = 0; p < P; p++)
+        for (int k = 1; k < n_models; k++)
+            if (models[(size_t)k * P + p]->M != models[p]->M || models[(size_t)k * P + p]->D != models[p]->D) {
+                if (P > 1) ghmm_set_error("%s: every model must have the same M and D (stream %d)", what, p);
+                else ghmm_set_error("%s: every model must have the same M and D", what);
+                return GHMM_ERR_UNSUPPORTED;
+            }
+    for (int p = 0; p < P; p++) {
+        if ((rc = check_pair(models[p], corpora[p]))) return rc;
+        if (corpora[p]->U != c->U || corpora[p]->len != c->len) {
+            ghmm_set_error("%s: stream %d: utterance count or lengths differ from stream 0", what, p);
+            return GHMM_ERR_ARG;
+        }
+    }
+    if (P > 1 && ctx->robust) {
+        ghmm_set_error("%s: GHMM_OPT_ROBUST is not available with several feature streams", what);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    if (lanes_only && v->Nmax > 64) {
+        ghmm_set_error("%s: a word of %d states: the vocabulary lattices hold one state per lane (64)", what,
+                       v->Nmax);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_score_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                        ghmm_corpus *const *corpora, int P, double *loglik_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, loglik_host != nullptr, false, __func__, &v)))
         return rc;
-    {
-        const lane_grid lg(Nmax, c->U);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
-                                               0, ctx->stream, c->U, NS, c->F, dtab, ctx->b, c->off, ctx->bt_scale,
-                                               ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
+    if (P == 1) return ghmm_score_batch(ctx, models, n_models, corpora[0], loglik_host);
+    ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return GHMM_OK;
+    if (v.Nmax > 64) { // as in ghmm_score_batch: word by word
+        for (int k = 0; k < n_models; k++)
+            if ((rc = ghmm_score_streams(ctx, models + (size_t)k * P, corpora, P, loglik_host + (size_t)k * c->U)))
+                return rc;
+        return GHMM_OK;
     }
-    if ((rc = launch_ok("k_forward_multi")) || (rc = vocab_scores_out(ctx, n_models, c, loglik_host))) return rc;
-    ctx->b_is_log = true; // the workspace b belongs to the concatenated model: not reusable
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, P, false, &v)) || (rc = vocab_emission(ctx, v, corpora, P, 0)) ||
+        (rc = vocab_forward(ctx, v, n_models, c)))
+        return rc;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
+}
+
+// the Viterbi vocabulary calls up to their score table in bt_ll: the gathers, the streams' log b folded
+// into b[F][NS], and k_viterbi_multi over the n_models entries of v->dtab (log A)
+static int vocab_viterbi(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                         dvocab *v)
+{
+    int rc;
+    const ghmm_corpus *c = corpora[0];
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, P, true, v)) || (rc = vocab_emission(ctx, *v, corpora, P, 2)))
+        return rc;
+    const lane_grid lg(v->Nmax, c->U);
+    kscope ks(ctx, GHMM_K_VITERBI);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                           ctx->stream, c->U, v->NS, v->dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                           c->order));
+    return launch_ok("k_viterbi_multi");
+}
+
+extern "C" int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                          ghmm_corpus *const *corpora, int P, double *score_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, score_host != nullptr, true, __func__, &v)))
+        return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = vocab_viterbi(ctx, models, n_models, corpora, P, &v))) return rc;
+    return vocab_scores_out(ctx, n_models, corpora[0], score_host);
+}
+
+// The batch call's score table, then on the device and without a host round trip: every utterance's
+// winning word (k_vocab_best) and that word's lattice again with back-pointers on the log b already
+// in the workspace (k_viterbi_pick, over (blocks, words) like k_viterbi_multi).  One stream wait.
+extern "C" int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                      ghmm_corpus *const *corpora, int P, int32_t *word_host, int32_t *path_host,
+                                      double *score_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, word_host && path_host && score_host, true,
+                                __func__, &v)))
+        return rc;
+    const ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return GHMM_OK;
+    const lane_grid lg(v.Nmax, c->U);
+    if ((rc = ctx->best_word.grow((size_t)c->U))) return rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
+    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
+    if ((rc = vocab_viterbi(ctx, models, n_models, corpora, P, &v))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_vocab_best, dim3((unsigned)((c->U + 255) / 256)), dim3(256), 0, ctx->stream, n_models,
+                           c->U, (const double *)ctx->bt_ll, ctx->best_word);
+    }
+    if ((rc = launch_ok("k_vocab_best"))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_pick<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                               ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off,
+                                               (const int *)ctx->best_word, ctx->psi, ctx->path, ctx->sink,
+                                               c->order));
+    }
+    if ((rc = launch_ok("k_viterbi_pick"))) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(word_host, ctx->best_word, (size_t)c->U * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
 

@@ -159,6 +159,16 @@ k_mul_streams(long long n, double *__restrict__ b, const double *__restrict__ bp
         b[k] *= bp[k];
 }
 
+// its log-domain sibling: log b_i(t) <- log b_i(t) + log b^p_i(t), one IEEE addition per entry with the
+// earlier streams' sum on the left (ghmm_viterbi_streams and the several-stream vocabulary calls);
+// NaN and +-inf propagate as the addition gives them
+__global__ void __launch_bounds__(256)
+k_add_streams(long long n, double *__restrict__ b, const double *__restrict__ bp)
+{
+    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long long)gridDim.x * 256)
+        b[k] += bp[k];
+}
+
 // ------------------------------------------------------------ group helpers
 // A "group" is L consecutive lanes (L = 16, 32 or 64) that own one utterance, lane i =
 // state i.  Cross-lane traffic stays inside the group.

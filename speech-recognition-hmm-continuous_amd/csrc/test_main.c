@@ -14,7 +14,9 @@
  *
  * A model set may have several feature streams (param_number P > 1): its P feature lists follow
  * each other on the command line (RF:253-262) and the score runs on the product of the streams'
- * emission densities (ghmm_score_streams, RF:349-366).
+ * emission densities (RF:349-366): the whole vocabulary in one pass with ghmm_score_streams_batch (on
+ * one stream that is ghmm_score_batch) as long as the words agree in every stream's M, model by model
+ * with ghmm_score_streams otherwise.
  *
  * Built with -DGHMM_FULL_COV this is recognition-continuous-test-full-fs, the full-covariance
  * recogniser RC = test/source/recognition-full-fs/recognition_continuous_full_fs.c: the same
@@ -373,9 +375,9 @@ int main(int argc, char **argv)
             ghmm_corpus *corpus[GHMM_MAX_STREAMS];
             for (int p = 0; p < P; p++)
                 if ((rc = ghmm_corpus_create(ctx, X[j][p], len[j], n_utt, D[j][p], &corpus[p]))) die("corpus", rc);
-            /* one stream: the whole vocabulary in one batched call when the models share M and D
-               (ghmm_score_batch), model by model otherwise; several streams: model by model on
-               the product of the streams' densities (ghmm_score_streams) */
+            /* the whole vocabulary in one batched call on the product of the streams' densities when the
+               words share every stream's M and D (ghmm_score_streams_batch; with one stream that is
+               ghmm_score_batch), model by model otherwise (ghmm_score_streams) */
             ghmm_model **dm = (ghmm_model **)calloc((size_t)word_number * GHMM_MAX_STREAMS, sizeof(ghmm_model *));
             double *all = (double *)malloc((size_t)word_number * (size_t)n_utt * sizeof(double));
             if (!dm || !all) die("memory", GHMM_ERR_ALLOC);
@@ -392,11 +394,13 @@ int main(int argc, char **argv)
                     if ((rc = ghmm_model_create(ctx, m->N, m->M, m->D, slot))) die("model", rc);
                     if ((rc = ghmm_model_set(ctx, *slot, m->A, m->c, m->mean, m->inv_var, m->det))) die("model", rc);
                 }
-            if (P == 1 && same) {
-                ghmm_model **flat = (ghmm_model **)malloc((size_t)word_number * sizeof(ghmm_model *));
+            if (same) {
+                /* flat[k * P + p]: the layout of the batched call (P == 1: ghmm_score_batch's) */
+                ghmm_model **flat = (ghmm_model **)malloc((size_t)word_number * P * sizeof(ghmm_model *));
                 if (!flat) die("memory", GHMM_ERR_ALLOC);
-                for (int k = 0; k < word_number; k++) flat[k] = dm[(size_t)k * GHMM_MAX_STREAMS];
-                if ((rc = ghmm_score_batch(ctx, flat, word_number, corpus[0], all))) die("scoring", rc);
+                for (int k = 0; k < word_number; k++)
+                    for (int p = 0; p < P; p++) flat[(size_t)k * P + p] = dm[(size_t)k * GHMM_MAX_STREAMS + p];
+                if ((rc = ghmm_score_streams_batch(ctx, flat, word_number, corpus, P, all))) die("scoring", rc);
                 free(flat);
             } else {
                 for (int k = 0; k < word_number; k++)

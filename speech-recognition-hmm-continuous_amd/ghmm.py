@@ -102,6 +102,11 @@ SYMBOLS = {
     "ghmm_estep_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp)], True),
     "ghmm_score_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _dp], True),
     "ghmm_viterbi": (C.c_int, [_vp, _vp, _vp, _ip, _dp], True),
+    "ghmm_viterbi_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _ip, _dp], True),
+    "ghmm_score_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp], True),
+    "ghmm_viterbi_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp], True),
+    "ghmm_recognise_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _dp],
+                               True),
     "ghmm_fmodel_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
     "ghmm_fmodel_destroy": (None, [_vp, _vp], True),
     "ghmm_fmodel_set": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp], True),
@@ -663,6 +668,41 @@ class Context:
         out = np.empty(corpora[0].n_utt, dtype=np.float64)
         _check(self.lib.ghmm_score_streams(self.h, pm, pc, P, _d(out)), self.lib)
         return out
+
+    # ---- several-stream vocabularies of diagonal models: vocab[k][p] = stream p of word k
+    def viterbi_streams(self, models, corpora):
+        """viterbi on the sum of the streams' log b: (path, score); fetch(BUF_B, (frames, N)) is that sum"""
+        path = np.empty(corpora[0].frames, dtype=np.int32)
+        score = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_streams(self.h, self._stream_handles(models), self._stream_handles(corpora),
+                                             len(models), path.ctypes.data_as(_ip), _d(score)), self.lib)
+        return path, score
+
+    def score_streams_batch(self, vocab, corpora):
+        """out[k, u] = score_streams of word k, the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_score_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                 self._stream_handles(corpora), len(corpora), _d(out)), self.lib)
+        return out
+
+    def viterbi_streams_batch(self, vocab, corpora):
+        """out[k, u] = viterbi_streams' score of word k, the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_viterbi_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                   self._stream_handles(corpora), len(corpora), _d(out)), self.lib)
+        return out
+
+    def recognise_streams(self, vocab, corpora):
+        """(word[U], path[F], score[K, U]): every utterance's best word by Viterbi score (ties: the
+        lowest word), that word's path over the utterance's frames, and the whole score table"""
+        word = np.empty(corpora[0].n_utt, dtype=np.int32)
+        path = np.empty(corpora[0].frames, dtype=np.int32)
+        score = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_recognise_streams(self.h, self._vocab_handles(vocab), len(vocab),
+                                               self._stream_handles(corpora), len(corpora),
+                                               word.ctypes.data_as(_ip), path.ctypes.data_as(_ip), _d(score)),
+               self.lib)
+        return word, path, score
 
     # ---- the full-covariance recogniser
     def full_model(self, hfm):
