@@ -255,7 +255,25 @@ int ghmm_estep(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *stats);
  * changing_zero_coef TF:1338-1359, calc_det TF:1976 + inv_matrix TF:2012 as
  * called at TF:343-346.  num_a is read inside the band i <= j <= i + GHMM_OPT_DELTA only —
  * the only entries calc_transition_probab ever accumulates (TF:1601); a_ij outside it
- * becomes 0 / den_a = 0 as in the reference.  Asynchronous. */
+ * becomes 0 / den_a = 0 as in the reference.  Asynchronous.
+ * A, c, mean, inv_var and det are the reference's BIT FOR BIT (a NaN's sign and payload aside; A outside
+ * the band as above): correctly rounded divisions, a sum and a product in index order, on every shape
+ * (tests/test_mstep_gpu.py).  Its quirks, all the reference's:
+ *   updating_transition_probab (TF:1862-1889): a row with den_a == 0 is kept as it was, its entries
+ *     outside the band included (only an updated row is masked).
+ *   updating_mix_param (TF:1911-1955): a state with den_c == 0 is skipped: mean as it was, and its
+ *     variance slot, which holds last iteration's INVERSE variances, goes through calc_det / inv_matrix
+ *     again: det = their product, inv_var = 1 / inv_var.  num_c == 0 in an updated state: 0/0 mean and
+ *     variances.  Variances below 1e-5 become 1e-5, negative ones (rounding) included; a NaN variance is
+ *     NOT floored (NaN < 1e-5 is false) and gives a NaN det.
+ *   changing_zero_coef (TF:1338-1359) on every state, skipped ones too: weights below 1e-5 become 1e-5,
+ *     then all are divided by their sum taken in index order.
+ *   calc_det (TF:1976): det = the product of the D variances in index order: it may underflow to a
+ *     subnormal or to 0 (every variance at the floor: 1e-320 at D = 64, 0 from D = 65) or overflow to inf.
+ * The derived constants are den = pow(2 pi, D/2) * sqrt(|det|), wk = c / den, logwk = log(c) - log(den),
+ * log a = a > 0 ? log(a) : -inf, by the expressions ghmm_model_set uses (the same bits).  A subnormal det
+ * is an ordinary value (sqrt(1e-320) = 1e-160).  det == 0: wk = +inf and logwk = +inf; det == inf: wk = 0
+ * and logwk = -inf; NaN det: NaN both: the next emission carries them as the reference's calc_gaus would. */
 int ghmm_mstep(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *stats);
 /* Forward-algorithm score per utterance (RF:354-366): emission without
  * posteriors + the forward recursion + log P.  Synchronises, writes loglik[U] on the host.
