@@ -335,6 +335,31 @@ int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *co
 int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
                  double *score_host);
 
+/* The forward score of a diagonal model in the log domain (absent from the reference): the sum over
+ * paths where ghmm_viterbi takes the best one, on the same log b and log A.
+ *     log b_j(t)  what ghmm_viterbi's emission launch writes (either tier)
+ *     log a_ij    the model's log A: a_ij > 0 ? log(a_ij) : -inf
+ * The lattice is ghmm_logscore_full's, word for word:
+ *     la_0(j) = (j == 0 ? 0 : -inf) + log b_j(0)                      (the one-hot start)
+ *     la_t(j) = LSE_{i : a_ij > 0} (la_{t-1}(i) + log a_ij) + log b_j(t)
+ *     LSE(x)  = m + log(sum_i exp(x_i - m)),  m = max_i x_i
+ * LSE is -inf when it has no term or every term is -inf, and NaN when a term is NaN.  A transition
+ * with a_ij == 0 is not a term: a NaN in a predecessor that cannot be reached from does not leak.
+ *     final_state != 0:  log P = la_{T-1}(N-1)       the diagonal recogniser's and trainer's convention
+ *                        (calc_probability with its final-state term, RF:349-366): equal to ghmm_score
+ *                        up to rounding where that is finite and none of its densities underflowed
+ *     final_state == 0:  log P = LSE_j la_{T-1}(j)
+ * Where the linear densities of ghmm_score underflow (one frame far from every Gaussian ends the
+ * utterance with -inf or NaN there) this score stays finite.  T = 0 scores 0; U = 0 touches nothing; a
+ * null destination with U > 0 gives GHMM_ERR_ARG.  1 to 512 states (GHMM_ERR_UNSUPPORTED above): up to
+ * 64 the lattice kernel of ghmm_logscore_full on a table of one word, beyond that one wave per utterance
+ * with the states in LDS (k_logforward_wide: a band-diagonal log A takes a two-term step, any other the
+ * dense one of N exp per state and frame).  The checks are ghmm_viterbi's; GHMM_OPT_ROBUST has no effect,
+ * as there.  Afterwards GHMM_BUF_B holds log b[F][N]; the row API does not reuse it and GHMM_BUF_POST
+ * gives GHMM_ERR_ARG.  One launch under GHMM_K_EMISSION, one under GHMM_K_FORWARD.  Synchronises; a
+ * second identical call repeats every byte. */
+int ghmm_logscore(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int final_state, double *loglik_host);
+
 /* ------------- several-stream vocabularies of diagonal models: Viterbi, batched scoring and word decoding */
 
 /* ghmm_viterbi's lattice on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...): every
@@ -407,6 +432,31 @@ int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_m
 int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                            ghmm_corpus *const *corpora, int n_streams, int32_t *word_host,
                            int32_t *path_host, double *score_host);
+/* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
+ * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
+ * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are
+ * ghmm_score_streams's (GHMM_OPT_ROBUST with n_streams > 1: GHMM_ERR_UNSUPPORTED), each before anything
+ * is launched or written; a null destination with U > 0 gives GHMM_ERR_ARG; U = 0 touches nothing.
+ * Afterwards GHMM_BUF_B holds the summed log b[F][N]; the row API does not reuse it and GHMM_BUF_POST
+ * gives GHMM_ERR_ARG.  2 n_streams - 1 launches under GHMM_K_EMISSION, one under GHMM_K_FORWARD.
+ * Synchronises; a second identical call repeats every byte. */
+int ghmm_logscore_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
+                          int n_streams, int final_state, double *loglik_host);
+/* loglik_host[k*U + u] = ghmm_logscore_streams of word k alone, the vocabulary in one pass as laid out
+ * above: the gathers, one log-emission launch per stream over its concatenated vocabulary, the folds,
+ * and ONE lattice launch over every (word, utterance) pair on stream 0's log A (2 n_streams - 1 launches
+ * under GHMM_K_EMISSION, one under GHMM_K_FORWARD).  Bit for bit the per-word call with
+ * GHMM_OPT_KERNELS = 1; under the matrix-core emission to rounding (1e-12 relative), as stated above.
+ * A vocabulary with a word of more than 64 states is scored word by word by ghmm_logscore_streams (the
+ * same bits on either tier), as ghmm_score_streams_batch does; a word of more than 512 states gives
+ * GHMM_ERR_UNSUPPORTED before anything is written.  The other refusals, GHMM_BUF_B afterwards and U = 0
+ * are ghmm_score_streams_batch's.  ghmm_logscore_batch is n_streams == 1 with the corpus itself: the
+ * same bits. */
+int ghmm_logscore_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *c,
+                        int final_state, double *loglik_host);
+int ghmm_logscore_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                ghmm_corpus *const *corpora, int n_streams, int final_state,
+                                double *loglik_host);
 
 /* ------------------------------------------ the full-covariance recogniser */
 

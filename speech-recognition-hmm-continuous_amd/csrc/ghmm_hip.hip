@@ -2612,6 +2612,117 @@ extern "C" int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, 
     return GHMM_OK;
 }
 
+// ---- the forward score in the log domain (ghmm_logscore and its three siblings; definitions in
+// include/ghmm.h): ghmm_viterbi's log b, the sum over paths where that takes the best one
+
+// k_logforward_multi over the n_models entries of dtab (log A) on the log b[F][NS] in the workspace:
+// la_{T-1}(N_k - 1), or LSE_j la_{T-1}(j) with final_state == 0, into bt_ll
+static int vocab_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
+                            const ghmm_corpus *c, int final_state)
+{
+    const lane_grid lg(Nmax, c->U);
+    kscope ks(ctx, GHMM_K_FORWARD);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                           0, ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                           c->order, final_state));
+    return launch_ok("k_logforward_multi");
+}
+
+// One word behind its checks (U > 0; L from fb_lanes): the streams' log b folded into b[F][N] as in
+// ghmm_viterbi_streams, then the lattice on models[0]'s log A: k_logforward_multi on a table of one
+// word, beyond 64 states one wave per utterance (k_logforward_wide); scores to the host, waits
+static int logscore_word(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P, int L,
+                         int final_state, double *loglik_host)
+{
+    int rc;
+    ghmm_model *m = models[0];
+    ghmm_corpus *c = corpora[0];
+    if (P == 1) {
+        if ((rc = ws_frames(ctx, m, c, false)) || (rc = run_emission(ctx, m, c, 2, ctx->b, nullptr))) return rc;
+    } else if ((rc = streams_emission(ctx, models, corpora, P, false, 2)))
+        return rc;
+    if (L == 0) {
+        if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
+        {
+            kscope ks(ctx, GHMM_K_FORWARD);
+            hipLaunchKernelGGL(k_logforward_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)4 * m->N * sizeof(double),
+                               ctx->stream, m->N, c->U, m->logA, ctx->b, c->off, ctx->loglik, c->order,
+                               ctx->wide_flag, final_state);
+        }
+        if ((rc = launch_ok("k_logforward_wide"))) return rc;
+        HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(stream_sync(ctx));
+        return GHMM_OK;
+    }
+    const fwd_model one = {m->logA, m->N, 0};
+    if ((rc = ctx->bt_ll.grow((size_t)c->U)) || (rc = ctx->bt_tab.grow(sizeof one))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = vocab_logforward(ctx, (const fwd_model *)ctx->bt_tab.p, 1, m->N, m->N, c, final_state))) return rc;
+    return vocab_scores_out(ctx, 1, c, loglik_host);
+}
+
+extern "C" int ghmm_logscore(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int final_state, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_pair(m, c))) return rc;
+    ARG_CHECK(loglik_host || c->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(m, &L))) return rc;
+    if (c->U == 0) return GHMM_OK;
+    return logscore_word(ctx, &m, &c, 1, L, final_state, loglik_host);
+}
+
+extern "C" int ghmm_logscore_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P,
+                                     int final_state, double *loglik_host)
+{
+    int rc = use(ctx);
+    if (rc || (rc = check_streams(ctx, models, corpora, P))) return rc;
+    if (P == 1) return ghmm_logscore(ctx, models[0], corpora[0], final_state, loglik_host);
+    ARG_CHECK(loglik_host || corpora[0]->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(models[0], &L))) return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    return logscore_word(ctx, models, corpora, P, L, final_state, loglik_host);
+}
+
+// the two vocabulary calls (`what` = the entry point's name in the checks' texts)
+static int logscore_vocab(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                          int final_state, double *loglik_host, const char *what)
+{
+    dvocab v;
+    int rc = use(ctx), L;
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, loglik_host != nullptr, false, what, &v)))
+        return rc;
+    for (int k = 0; k < n_models; k++) // (more than 512 states: before the words ahead of it are written)
+        if ((rc = fb_lanes(models[(size_t)k * P], &L))) return rc;
+    const ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return GHMM_OK;
+    if (v.Nmax > 64) { // as in ghmm_score_streams_batch: word by word
+        for (int k = 0; k < n_models; k++)
+            if ((rc = ghmm_logscore_streams(ctx, models + (size_t)k * P, corpora, P, final_state,
+                                            loglik_host + (size_t)k * c->U)))
+                return rc;
+        return GHMM_OK;
+    }
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, P, true, &v)) || (rc = vocab_emission(ctx, v, corpora, P, 2)) ||
+        (rc = vocab_logforward(ctx, v.dtab, n_models, v.NS, v.Nmax, c, final_state)))
+        return rc;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
+}
+
+extern "C" int ghmm_logscore_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *c,
+                                   int final_state, double *loglik_host)
+{
+    return logscore_vocab(ctx, models, n_models, &c, 1, final_state, loglik_host, __func__);
+}
+
+extern "C" int ghmm_logscore_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                           ghmm_corpus *const *corpora, int P, int final_state, double *loglik_host)
+{
+    return logscore_vocab(ctx, models, n_models, corpora, P, final_state, loglik_host, __func__);
+}
+
 // ------------------------------------------------------------ collective (RCCL)
 // One sum of the statistics vector over ranks per EM iteration.  RCCL is
 // resolved at run time from librccl.so.1: a single-GPU process never loads it, and a process

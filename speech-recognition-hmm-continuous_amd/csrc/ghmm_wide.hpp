@@ -1,4 +1,5 @@
-// ghmm_wide.hpp — forward / backward / Viterbi for models of more than 64 states (up to WIDE_MAX).
+// ghmm_wide.hpp — forward / backward / Viterbi and the log-domain forward score for models of more than
+// 64 states (up to WIDE_MAX).
 //
 // The kernels of ghmm_kernels.hpp / ghmm_pair.hpp hold one state per lane; here one wave owns an
 // utterance and every lane owns the states i = lane, lane + 64, ...  The state vectors of the
@@ -253,6 +254,87 @@ k_viterbi_wide(int N, int U, const double *__restrict__ logA, const double *__re
         pu[t] = (unsigned char)s;
         s = ps[(size_t)t * N + s];
     }
+}
+
+// The sum-over-paths lattice on log b (ghmm_logscore; definition in include/ghmm.h), score only:
+// k_viterbi_wide's layout with the max replaced by LSE, the operations of logforward_run
+// (ghmm_kernels.hpp) on states held in LDS instead of lanes.  Nothing per frame goes to global memory.
+//   banded: the terms from j - 1 and j, each guarded by its own log a != -inf, hi + log1p(exp(lo - hi)).
+//   dense: two passes over the N predecessors in index order (max, then the sum of exp): N exp per
+//     state and step.  It is the correctness path; the reference's trainer only produces banded A.
+//   final_state != 0: score[u] = la_{T-1}(N-1); otherwise LSE_j la_{T-1}(j): every lane's partial max
+//     and sum over its own states, then across the lanes as in k_logforward_multi.
+__global__ void __launch_bounds__(WAVE)
+k_logforward_wide(int N, int U, const double *__restrict__ logA, const double *__restrict__ logb,
+                  const long long *__restrict__ off, double *__restrict__ score,
+                  const int *__restrict__ order, const int *__restrict__ offband, int final_state)
+{
+    extern __shared__ double lds[]; // la[2][N] | lself[N] | lprev[N]
+    const int l = threadIdx.x;
+    const int u = order[blockIdx.x];
+    const long long f0 = off[u];
+    const int T = (int)(off[u + 1] - f0);
+    if (T <= 0) {
+        if (l == 0) score[u] = 0.0;
+        return;
+    }
+    const bool banded = offband[0] == 0;
+    double *lself = lds + 2 * N, *lprev = lds + 3 * N;
+    const double *lb = logb + f0 * N;
+    for (int j = l; j < N; j += WAVE) {
+        lself[j] = logA[(size_t)j * N + j];
+        lprev[j] = j > 0 ? logA[(size_t)(j - 1) * N + j] : -INFINITY;
+        lds[j] = ((j == 0) ? 0.0 : -INFINITY) + lb[j];
+    }
+    __syncthreads();
+    for (int t = 1; t < T; t++) {
+        const double *prev = lds + (size_t)((t + 1) & 1) * N;
+        double *cur = lds + (size_t)(t & 1) * N;
+        for (int j = l; j < N; j += WAVE) {
+            double r;
+            if (banded) {
+                const double la_self = lself[j], la_prev = lprev[j];
+                const double c1 = la_prev != -INFINITY ? prev[j > 0 ? j - 1 : 0] + la_prev : -INFINITY;
+                const double c0 = la_self != -INFINITY ? prev[j] + la_self : -INFINITY;
+                const bool up = c0 < c1; // (false for a NaN: lo - hi is then NaN)
+                const double hi = up ? c1 : c0, lo = up ? c0 : c1;
+                const double x = lo == -INFINITY ? -INFINITY : lo - hi; // (not -inf - -inf; a NaN lo stays)
+                r = hi + log1p(exp_emis(x));
+            } else {
+                double m = -INFINITY;
+                for (int i = 0; i < N; i++) {
+                    const double la = logA[(size_t)i * N + j];
+                    const double v = la != -INFINITY ? prev[i] + la : -INFINITY;
+                    m = fmax(m, v); // (a NaN term is passed over here and taken by the sum)
+                }
+                const double mm = m == -INFINITY ? 0.0 : m;
+                double s = 0.0;
+                for (int i = 0; i < N; i++) {
+                    const double la = logA[(size_t)i * N + j];
+                    const double v = la != -INFINITY ? prev[i] + la : -INFINITY;
+                    s += exp_emis(v - mm);
+                }
+                r = m + log(s);
+            }
+            cur[j] = r + lb[(size_t)t * N + j];
+        }
+        __syncthreads();
+    }
+    const double *fin = lds + (size_t)((T - 1) & 1) * N;
+    double sc;
+    if (final_state) {
+        sc = fin[N - 1];
+    } else {
+        double m = -INFINITY;
+        for (int j = l; j < N; j += WAVE) m = fmax(m, fin[j]);
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, WAVE));
+        const double mm = m == -INFINITY ? 0.0 : m;
+        double part = 0.0;
+        for (int j = l; j < N; j += WAVE) part += exp_emis(fin[j] - mm);
+        sc = m + log(wave_sum(part));
+    }
+    if (l == 0) score[u] = sc;
 }
 
 } // namespace ghmm

@@ -25,10 +25,11 @@
  * log P has no final-state term (calc_probability, RC:822-836): the whole vocabulary in one pass, on
  * one feature stream (where it is ghmm_score_full_batch) or several, as long as the words agree in
  * every stream's M; a set whose words do not is scored model by model with ghmm_score_full_streams.
- * With GHMM_LOG_SCORE=1 in the environment that program scores in the log domain instead
- * (ghmm_logscore_full_streams_batch / ghmm_logscore_full_streams, final_state = 0: the same quantity,
- * finite where the linear densities underflow) and says so in the report's second line; without the
- * variable nothing changes.
+ * With GHMM_LOG_SCORE=1 in the environment either program scores in the log domain instead and says so
+ * in the report's second line: the full-covariance one with ghmm_logscore_full_streams_batch /
+ * ghmm_logscore_full_streams and final_state = 0, the diagonal one with ghmm_logscore_streams_batch /
+ * ghmm_logscore_streams and final_state = 1 (its final-state term kept); the same quantities, finite
+ * where the linear densities underflow.  Without the variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -139,10 +140,8 @@ int main(int argc, char **argv)
     for (int i = 0; i < K; i++) coef_model[i] = atof(argv[K + 2 + i]);
     const char *output_file = argv[argc - 1], *word_file = argv[argc - 2];
     int rc;
-#ifdef GHMM_FULL_COV
     const char *env_log = getenv("GHMM_LOG_SCORE");
     const int log_score = env_log && strcmp(env_log, "1") == 0;
-#endif
 
     /* models: one list per set, the same vocabulary in every set */
 #ifdef GHMM_FULL_COV
@@ -295,7 +294,8 @@ int main(int argc, char **argv)
     /* writing_header, RF:1014-1031.  The reference declares coef_model as int* there
        and prints it with %.2d: the integer words of the double array are shown. */
     fprintf(f_out, "Isolated word recognition using Continuous HMM (diagonal covariance matrix). It is considered a final state. \n");
-    fprintf(f_out, "Algorithm used for recognition: Forward \n");
+    fprintf(f_out, log_score ? "Algorithm used for recognition: Forward (log domain) \n"
+                             : "Algorithm used for recognition: Forward \n");
     fprintf(f_out, "Number of models: %d  \n", K);
     for (int i = 0; i < K; i++) {
         int as_int;
@@ -377,7 +377,8 @@ int main(int argc, char **argv)
                 if ((rc = ghmm_corpus_create(ctx, X[j][p], len[j], n_utt, D[j][p], &corpus[p]))) die("corpus", rc);
             /* the whole vocabulary in one batched call on the product of the streams' densities when the
                words share every stream's M and D (ghmm_score_streams_batch; with one stream that is
-               ghmm_score_batch), model by model otherwise (ghmm_score_streams) */
+               ghmm_score_batch), model by model otherwise (ghmm_score_streams); GHMM_LOG_SCORE=1: their
+               log-domain counterparts with final_state = 1, the final-state term kept */
             ghmm_model **dm = (ghmm_model **)calloc((size_t)word_number * GHMM_MAX_STREAMS, sizeof(ghmm_model *));
             double *all = (double *)malloc((size_t)word_number * (size_t)n_utt * sizeof(double));
             if (!dm || !all) die("memory", GHMM_ERR_ALLOC);
@@ -400,13 +401,18 @@ int main(int argc, char **argv)
                 if (!flat) die("memory", GHMM_ERR_ALLOC);
                 for (int k = 0; k < word_number; k++)
                     for (int p = 0; p < P; p++) flat[(size_t)k * P + p] = dm[(size_t)k * GHMM_MAX_STREAMS + p];
-                if ((rc = ghmm_score_streams_batch(ctx, flat, word_number, corpus, P, all))) die("scoring", rc);
+                if ((rc = log_score ? ghmm_logscore_streams_batch(ctx, flat, word_number, corpus, P, 1, all)
+                                    : ghmm_score_streams_batch(ctx, flat, word_number, corpus, P, all)))
+                    die("scoring", rc);
                 free(flat);
             } else {
-                for (int k = 0; k < word_number; k++)
-                    if ((rc = ghmm_score_streams(ctx, &dm[(size_t)k * GHMM_MAX_STREAMS], corpus, P,
-                                                 all + (size_t)k * n_utt)))
+                for (int k = 0; k < word_number; k++) {
+                    ghmm_model **mk = &dm[(size_t)k * GHMM_MAX_STREAMS];
+                    double *dst = all + (size_t)k * n_utt;
+                    if ((rc = log_score ? ghmm_logscore_streams(ctx, mk, corpus, P, 1, dst)
+                                        : ghmm_score_streams(ctx, mk, corpus, P, dst)))
                         die("scoring", rc);
+                }
             }
             for (int k = 0; k < word_number; k++) {
                 for (int u = 0; u < n_utt; u++)

@@ -107,6 +107,11 @@ SYMBOLS = {
     "ghmm_viterbi_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp], True),
     "ghmm_recognise_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _dp],
                                True),
+    "ghmm_logscore": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
+    "ghmm_logscore_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
+    "ghmm_logscore_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp], True),
+    "ghmm_logscore_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _dp],
+                                    True),
     "ghmm_fmodel_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
     "ghmm_fmodel_destroy": (None, [_vp, _vp], True),
     "ghmm_fmodel_set": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp], True),
@@ -703,6 +708,38 @@ class Context:
                                                word.ctypes.data_as(_ip), path.ctypes.data_as(_ip), _d(score)),
                self.lib)
         return word, path, score
+
+    # ---- the forward score of diagonal models in the log domain
+    def logscore(self, model, corpus, final_state=False):
+        """log-domain forward score per utterance: LSE over the last frame's states, or the last
+        state's alone with final_state (score's quantity); finite where score underflows; log b stays
+        in the workspace (fetch(BUF_B, (frames, N)))"""
+        out = np.empty(corpus.n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_logscore(self.h, model.h, corpus.h, int(bool(final_state)), _d(out)), self.lib)
+        return out
+
+    def logscore_batch(self, models, corpus, final_state=False):
+        """out[k, u] = logscore of utterance u under model k, the vocabulary in one pass"""
+        arr = (_vp * len(models))(*[m.h for m in models])
+        out = np.empty((len(models), corpus.n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_logscore_batch(self.h, arr, len(models), corpus.h, int(bool(final_state)), _d(out)),
+               self.lib)
+        return out
+
+    def logscore_streams(self, models, corpora, final_state=False):
+        """logscore on the sum of the streams' log b"""
+        out = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(self.lib.ghmm_logscore_streams(self.h, self._stream_handles(models), self._stream_handles(corpora),
+                                              len(models), int(bool(final_state)), _d(out)), self.lib)
+        return out
+
+    def logscore_streams_batch(self, vocab, corpora, final_state=False):
+        """out[k, u] = logscore_streams of word k, the vocabulary in one pass"""
+        out = np.empty((len(vocab), corpora[0].n_utt), dtype=np.float64)
+        _check(self.lib.ghmm_logscore_streams_batch(self.h, self._vocab_handles(vocab), len(vocab),
+                                                    self._stream_handles(corpora), len(corpora),
+                                                    int(bool(final_state)), _d(out)), self.lib)
+        return out
 
     # ---- the full-covariance recogniser
     def full_model(self, hfm):
