@@ -1,7 +1,7 @@
 // ghmm_fullhost.hpp — the host side of the full-covariance entry points (recogniser RC, trainer TFF):
 // models, checks, launches of the kernels in ghmm_fullcov.hpp.  Part of ghmm_hip.hip's translation
-// unit, included once at its end: it uses that file's context, workspace and vocabulary helpers and
-// the RCCL table resolved there.
+// unit, included once at its end: it uses that file's context and workspace, the checks, tables and
+// lattice launches both model kinds share (ghmm_lattice_host.hpp) and the RCCL table resolved there.
 
 // ------------------------------------------------ the full-covariance recogniser (RC)
 
@@ -244,150 +244,64 @@ extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, d
 }
 
 // A vocabulary call up to its one launch, on P feature streams (models[k * P + p] = stream p of word k,
-// corpora[p] = stream p of the utterances; the single-stream calls pass P = 1).  The checks (`what` =
-// the entry point's name in their texts), then, unless the corpus is empty (the caller returns), per
-// stream the concatenated vocabulary (NS states, transitions unused; kept in the context between calls:
-// ctx->fbt_cat for stream 0, ctx->fbt_cat_s[p] for the later ones) with every word's Gaussians of that
-// stream gathered into it by one launch, the table of the words' recursions (dtab[k].A = word k's A
-// under FC_LIN, its log A under FC_LOG, stream 0's) and the vocabulary's b or log b in the workspace:
-// one emission launch per stream over its concatenated vocabulary, stream 0 plain, every later stream
-// folded into the same b[F][NS].  The FOLD epilogue is per state, so column bo_k + i holds what
-// emission_full_streams leaves in column i for word k alone.  The launch that follows writes bt_ll.
-struct fvocab {
-    int NS = 0, Nmax = 0; // the vocabulary's states, the largest word's
-    const fwd_model *dtab = nullptr;
-};
-
+// corpora[p] = stream p of the utterances; the single-stream calls pass P = 1).  The shared checks
+// (vocab_checks; `what` = the entry point's name in their texts), then, unless the corpus is empty (the
+// caller returns), the pass's tables (vocab_tables: dtab[k].A = word k's A under FC_LIN, its log A under
+// FC_LOG), per stream the concatenated vocabulary (NS states, transitions unused; ctx->fbt_cat[p],
+// cat_slot) with every word's Gaussians of that stream gathered into it by one launch, and the
+// vocabulary's b or log b in the workspace: one emission launch per stream over its concatenated
+// vocabulary, stream 0 plain, every later stream folded into the same b[F][NS].  The FOLD epilogue is per
+// state, so column bo_k + i holds what emission_full_streams leaves in column i for word k alone.  The
+// launch that follows writes bt_ll.
 static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *const *corpora, int P,
-                        bool have_dest, int mode, const char *what, fvocab *v)
+                        bool have_dest, int mode, const char *what, vocab_pass *v)
 {
     int rc = use(ctx);
     if (rc) return rc;
-    ARG_CHECK_AS(what, models && n_models > 0 && corpora, "null argument");
-    if (P < 1 || P > GHMM_MAX_STREAMS) {
-        ghmm_set_error("%s: 1 to %d feature streams (asked: %d)", what, GHMM_MAX_STREAMS, P);
-        return GHMM_ERR_ARG;
-    }
-    for (int p = 0; p < P; p++) ARG_CHECK_AS(what, corpora[p], "null argument");
+    rc = vocab_checks(models, n_models, corpora, P, have_dest, what,
+                      [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); }, v);
+    if (rc || corpora[0]->U == 0) return rc;
     const ghmm_corpus *c = corpora[0];
-    ARG_CHECK_AS(what, have_dest || c->U == 0, "null destination");
-    for (int k = 0; k < n_models * P; k++) ARG_CHECK_AS(what, models[k], "null model");
-    v->NS = v->Nmax = 0;
-    for (int k = 0; k < n_models; k++) {
-        const int N = models[(size_t)k * P]->N;
-        for (int p = 1; p < P; p++)
-            if (models[(size_t)k * P + p]->N != N) {
-                ghmm_set_error("%s: word %d: stream %d has %d states, stream 0 has %d", what, k, p,
-                               models[(size_t)k * P + p]->N, N);
-                return GHMM_ERR_ARG;
-            }
-        v->NS += N;
-        v->Nmax = N > v->Nmax ? N : v->Nmax;
-    }
-    for (int p = 0; p < P; p++)
-        for (int k = 1; k < n_models; k++)
-            if (models[(size_t)k * P + p]->M != models[p]->M || models[(size_t)k * P + p]->D != models[p]->D) {
-                if (P > 1) ghmm_set_error("%s: every model must have the same M and D (stream %d)", what, p);
-                else ghmm_set_error("%s: every model must have the same M and D", what);
-                return GHMM_ERR_UNSUPPORTED;
-            }
-    for (int p = 0; p < P; p++) {
-        if ((rc = check_full(ctx, models[p], corpora[p]))) return rc;
-        if (corpora[p]->U != c->U || corpora[p]->len != c->len) {
-            ghmm_set_error("%s: stream %d: utterance count or lengths differ from stream 0", what, p);
-            return GHMM_ERR_ARG;
-        }
-    }
-    if (c->U == 0) return GHMM_OK;
     if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
-    // the tables, built on the host and uploaded into one context buffer: the words' recursions, then
-    // every stream's gather sources (word k's Gaussians g0 .. g0 + ng of that stream's vocabulary)
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<fgather_src> src((size_t)n_models * P);
+    const fgather_src *dsrc;
+    rc = vocab_tables<fgather_src>(ctx, models, n_models, P, mode == FC_LOG, [](const ghmm_fmodel *m, int g0) {
+        return fgather_src{m->c, m->mean, m->inv_cov, m->den, m->lk, g0, m->N * m->M};
+    }, v, &dsrc);
+    if (rc) return rc;
     for (int p = 0; p < P; p++) {
-        int go = 0, so = 0;
-        for (int k = 0; k < n_models; k++) {
-            const ghmm_fmodel *m = models[(size_t)k * P + p];
-            if (p == 0) tab[k] = {mode == FC_LOG ? m->logA : m->A, m->N, so};
-            fgather_src &s = src[(size_t)p * n_models + k];
-            s.c = m->c; s.mean = m->mean; s.inv_cov = m->inv_cov; s.den = m->den; s.lk = m->lk;
-            s.g0 = go; s.ng = m->N * m->M;
-            go += m->N * m->M;
-            so += m->N;
-        }
-    }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(fgather_src);
-    if ((rc = ctx->fbt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
-    v->dtab = (const fwd_model *)ctx->fbt_tab.p;
-    const fgather_src *dsrc = (const fgather_src *)(ctx->fbt_tab + ((tab_bytes + 15) / 16) * 16);
-    // (the tables leave pageable host vectors: the copies complete before the call returns them)
-    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync((void *)dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    ghmm_fmodel *cats[GHMM_MAX_STREAMS];
-    for (int p = 0; p < P; p++) {
-        ghmm_fmodel **slot = p ? &ctx->fbt_cat_s[p] : &ctx->fbt_cat;
-        const int M = models[p]->M, D = models[p]->D;
-        if (*slot && ((*slot)->N != v->NS || (*slot)->M != M || (*slot)->D != D)) {
-            ghmm_fmodel_destroy(ctx, *slot);
-            *slot = nullptr;
-        }
-        if (!*slot && (rc = fmodel_alloc(ctx, v->NS, M, D, slot))) return rc;
-        ghmm_fmodel *cat = cats[p] = *slot;
+        const int NS = v->NS, M = models[p]->M, D = models[p]->D;
+        rc = cat_slot(ctx, &ctx->fbt_cat[p], NS, M, D, ghmm_fmodel_destroy,
+                      [=](ghmm_fmodel **slot) { return fmodel_alloc(ctx, NS, M, D, slot); });
+        if (rc) return rc;
+        ghmm_fmodel *cat = ctx->fbt_cat[p];
         hipLaunchKernelGGL(k_gather_fmodels, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, D,
                            dsrc + (size_t)p * n_models, cat->c, cat->mean, cat->inv_cov, cat->den, cat->lk);
         if ((rc = launch_ok("k_gather_fmodels"))) return rc;
     }
     if ((rc = ws_full(ctx, v->NS, models[0]->M, c))) return rc;
     for (int p = 0; p < P; p++)
-        if ((rc = run_emission_full(ctx, cats[p], corpora[p], mode, p > 0))) return rc;
+        if ((rc = run_emission_full(ctx, ctx->fbt_cat[p], corpora[p], mode, p > 0))) return rc;
     return GHMM_OK;
 }
 
-// k_forward_multi over the n_models entries of v.dtab on the b in the workspace; scores to the host
-static int run_forward_vocab(ghmm_ctx *ctx, const fvocab &v, int n_models, const ghmm_corpus *c, double *loglik_host)
+// the linear score of a vocabulary: no final-state term, nobody reads c_t (the sink takes them)
+static int fvocab_score(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                        double *loglik_host, const char *what)
 {
-    int rc;
-    {
-        const lane_grid lg(v.Nmax, c->U);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
-                                               0, ctx->stream, c->U, v.NS, c->F, v.dtab, ctx->b, c->off, ctx->sink,
-                                               ctx->sink, ctx->bt_ll, ctx->sink, c->order, 0));
-    }
-    if ((rc = launch_ok("k_forward_multi"))) return rc;
-    return vocab_scores_out(ctx, n_models, c, loglik_host);
+    vocab_pass v;
+    int rc = fvocab_begin(ctx, models, n_models, corpora, P, loglik_host != nullptr, FC_LIN, what, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    if ((rc = vocab_forward(ctx, v, n_models, corpora[0], ctx->sink, ctx->sink, 0))) return rc;
+    return vocab_scores_out(ctx, n_models, corpora[0], loglik_host);
 }
 
 extern "C" int ghmm_score_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                                      double *loglik_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, &c, 1, loglik_host != nullptr, FC_LIN, __func__, &v);
-    if (rc || c->U == 0) return rc;
-    return run_forward_vocab(ctx, v, n_models, c, loglik_host);
+    return fvocab_score(ctx, models, n_models, &c, 1, loglik_host, __func__);
 }
 
 // ------------------------------------------------ the full-covariance Viterbi
-
-// k_viterbi on fm's log A and the log b in the workspace (psi and path sized by the caller); paths and
-// scores to the host
-static int run_viterbi_full(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c, int32_t *path_host,
-                            double *score_host)
-{
-    int rc;
-    const lane_grid lg(fm->N, c->U);
-    {
-        kscope ks(ctx, GHMM_K_VITERBI);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
-                                               c->U, fm->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
-                                               ctx->sink, c->order));
-    }
-    if ((rc = launch_ok("k_viterbi"))) return rc;
-    HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
-}
 
 extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int32_t *path_host,
                                  double *score_host)
@@ -396,62 +310,47 @@ extern "C" int ghmm_viterbi_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c,
     if (rc || (rc = check_full(ctx, fm, c))) return rc;
     ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
     if (c->U == 0) return GHMM_OK;
-    const lane_grid lg(fm->N, c->U);
-    if ((rc = ws_full(ctx, fm->N, fm->M, c))) return rc;
-    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
+    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = viterbi_ws(ctx, c, lane_grid(fm->N, c->U).L))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
-    return run_viterbi_full(ctx, fm, c, path_host, score_host);
+    return run_viterbi_lanes(ctx, fm->N, fm->logA, c, path_host, score_host);
 }
 
-// k_viterbi_multi over the n_models entries of v.dtab on the log b in the workspace: scores into bt_ll
-static int run_viterbi_vocab(ghmm_ctx *ctx, const fvocab &v, int n_models, const ghmm_corpus *c)
+static int fvocab_viterbi(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                          double *score_host, const char *what)
 {
-    const lane_grid lg(v.Nmax, c->U);
-    kscope ks(ctx, GHMM_K_VITERBI);
-    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                           ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
-                                           c->order));
-    return launch_ok("k_viterbi_multi");
+    vocab_pass v;
+    int rc = fvocab_begin(ctx, models, n_models, corpora, P, score_host != nullptr, FC_LOG, what, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    if ((rc = vocab_viterbi(ctx, v, n_models, corpora[0]))) return rc;
+    return vocab_scores_out(ctx, n_models, corpora[0], score_host);
 }
 
 extern "C" int ghmm_viterbi_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                                        double *score_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, &c, 1, score_host != nullptr, FC_LOG, __func__, &v);
-    if (rc || c->U == 0) return rc;
-    if ((rc = run_viterbi_vocab(ctx, v, n_models, c))) return rc;
-    return vocab_scores_out(ctx, n_models, c, score_host);
+    return fvocab_viterbi(ctx, models, n_models, &c, 1, score_host, __func__);
 }
 
 // ------------------------------------------------ the full-covariance log-domain forward score
 
-// k_logforward_multi over the n_models entries of dtab on the log b in the workspace; scores to the host
-static int run_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
-                          const ghmm_corpus *c, int final_state, double *loglik_host)
-{
-    int rc;
-    {
-        const lane_grid lg(Nmax, c->U);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(lg.blocks, (unsigned)n_models),
-                                               dim3(WAVE), 0, ctx->stream, c->U, NS, dtab, ctx->b, c->off,
-                                               ctx->bt_ll, ctx->sink, c->order, final_state));
-    }
-    if ((rc = launch_ok("k_logforward_multi"))) return rc;
-    return vocab_scores_out(ctx, n_models, c, loglik_host);
-}
+static int emission_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora, int P,
+                                 int mode); // (with the several-stream calls, below)
 
-// the batch call's lattice launch on a table of one word: that table (fm's log A) into ctx->fbt_tab
-static int logforward_one_word(ghmm_ctx *ctx, const ghmm_fmodel *fm, const ghmm_corpus *c)
+// one word (models[0]'s log A) as a vocabulary of one: its table first, then the streams' log b
+static int flogscore_word(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora, int P,
+                          int final_state, double *loglik_host)
 {
     int rc;
-    const fwd_model one = {fm->logA, fm->N, 0};
-    if ((rc = ctx->bt_ll.grow((size_t)c->U))) return rc;
-    if ((rc = ctx->fbt_tab.grow(sizeof one))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->fbt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
-    return GHMM_OK;
+    vocab_pass one;
+    ghmm_fmodel *fm = models[0];
+    ghmm_corpus *c = corpora[0];
+    if ((rc = one_word_table(ctx, fm->logA, fm->N, c, &one))) return rc;
+    if (P == 1) {
+        if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
+    } else if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG)))
+        return rc;
+    if ((rc = vocab_logforward(ctx, one, 1, c, final_state))) return rc;
+    return vocab_scores_out(ctx, 1, c, loglik_host);
 }
 
 extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, int final_state,
@@ -461,18 +360,23 @@ extern "C" int ghmm_logscore_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c
     if (rc || (rc = check_full(ctx, fm, c))) return rc;
     ARG_CHECK(loglik_host || c->U == 0, "null destination");
     if (c->U == 0) return GHMM_OK;
-    if ((rc = logforward_one_word(ctx, fm, c))) return rc;
-    if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = run_emission_full(ctx, fm, c, FC_LOG))) return rc;
-    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab.p, 1, fm->N, fm->N, c, final_state, loglik_host);
+    return flogscore_word(ctx, &fm, &c, 1, final_state, loglik_host);
+}
+
+static int fvocab_logscore(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                           int final_state, double *loglik_host, const char *what)
+{
+    vocab_pass v;
+    int rc = fvocab_begin(ctx, models, n_models, corpora, P, loglik_host != nullptr, FC_LOG, what, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    if ((rc = vocab_logforward(ctx, v, n_models, corpora[0], final_state))) return rc;
+    return vocab_scores_out(ctx, n_models, corpora[0], loglik_host);
 }
 
 extern "C" int ghmm_logscore_full_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *c,
                                         int final_state, double *loglik_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, &c, 1, loglik_host != nullptr, FC_LOG, __func__, &v);
-    if (rc || c->U == 0) return rc;
-    return run_logforward(ctx, v.dtab, n_models, v.NS, v.Nmax, c, final_state, loglik_host);
+    return fvocab_logscore(ctx, models, n_models, &c, 1, final_state, loglik_host, __func__);
 }
 
 // ------------------------------------------------ the full-covariance trainer (TFF)
@@ -800,7 +704,9 @@ extern "C" int ghmm_fmodel_init(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, 
 // later stream's launch (k_emission_full's FOLD) multiplies into it, or adds onto log b.  There is no
 // second b and no pass of its own for the product.
 
-// `stats` may be null (the score calls); nothing is launched before every check has passed
+// the array and range check, then the shared stream_checks with, per stream, the statistics vector's
+// (`stats` may be null where want_stats is not set: the score calls); nothing is launched before every
+// check has passed
 static int check_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora, int P,
                               ghmm_stats *const *stats, bool want_stats)
 {
@@ -808,20 +714,9 @@ static int check_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_co
         ghmm_set_error("bad stream arguments (1 to %d feature streams, no null array)", GHMM_MAX_STREAMS);
         return GHMM_ERR_ARG;
     }
-    for (int p = 0; p < P; p++) {
-        int rc = check_full(ctx, models[p], corpora[p]);
-        if (rc) return rc;
-        if (models[p]->N != models[0]->N) {
-            ghmm_set_error("stream %d has %d states, stream 0 has %d", p, models[p]->N, models[0]->N);
-            return GHMM_ERR_ARG;
-        }
-        if (corpora[p]->U != corpora[0]->U || corpora[p]->len != corpora[0]->len) {
-            ghmm_set_error("stream %d: utterance count or lengths differ from stream 0", p);
-            return GHMM_ERR_ARG;
-        }
-        if (want_stats && (rc = check_stats_full(models[p], stats[p]))) return rc;
-    }
-    return GHMM_OK;
+    return stream_checks(
+        models, corpora, P, [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); },
+        [=](int p) { return want_stats ? check_stats_full(models[p], stats[p]) : GHMM_OK; });
 }
 
 // the workspace of stream 0's shape, then every stream's emission in stream order: ctx->b ends up
@@ -881,19 +776,15 @@ extern "C" int ghmm_logscore_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mod
     int rc = use(ctx);
     if (rc || (rc = check_full_streams(ctx, models, corpora, P, nullptr, false))) return rc;
     if (P == 1) return ghmm_logscore_full(ctx, models[0], corpora[0], final_state, loglik_host);
-    ghmm_fmodel *fm = models[0];
-    ghmm_corpus *c = corpora[0];
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    if (c->U == 0) return GHMM_OK;
-    if ((rc = logforward_one_word(ctx, fm, c))) return rc;
-    if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG))) return rc;
-    return run_logforward(ctx, (const fwd_model *)ctx->fbt_tab.p, 1, fm->N, fm->N, c, final_state, loglik_host);
+    ARG_CHECK(loglik_host || corpora[0]->U == 0, "null destination");
+    if (corpora[0]->U == 0) return GHMM_OK;
+    return flogscore_word(ctx, models, corpora, P, final_state, loglik_host);
 }
 
 // ------------------------------------------------ several-stream vocabularies
 // Viterbi on several streams, the three batched vocabulary calls on several streams, and the word
 // decoder (definitions in include/ghmm.h).  No new arithmetic: the streams' emission launches with
-// FOLD, then the lattice kernels of the single-stream calls on the folded b or log b.
+// FOLD, then the lattice launches of ghmm_lattice_host.hpp on the folded b or log b.
 
 extern "C" int ghmm_viterbi_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, ghmm_corpus *const *corpora,
                                          int P, int32_t *path_host, double *score_host)
@@ -905,77 +796,37 @@ extern "C" int ghmm_viterbi_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mode
     ghmm_corpus *c = corpora[0];
     ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
     if (c->U == 0) return GHMM_OK;
-    const lane_grid lg(fm->N, c->U);
-    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
+    if ((rc = viterbi_ws(ctx, c, lane_grid(fm->N, c->U).L))) return rc;
     if ((rc = emission_full_streams(ctx, models, corpora, P, FC_LOG))) return rc;
-    return run_viterbi_full(ctx, fm, c, path_host, score_host);
+    return run_viterbi_lanes(ctx, fm->N, fm->logA, c, path_host, score_host);
 }
 
 extern "C" int ghmm_score_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                              ghmm_corpus *const *corpora, int P, double *loglik_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, corpora, P, loglik_host != nullptr, FC_LIN, __func__, &v);
-    if (rc || corpora[0]->U == 0) return rc;
-    return run_forward_vocab(ctx, v, n_models, corpora[0], loglik_host);
+    return fvocab_score(ctx, models, n_models, corpora, P, loglik_host, __func__);
 }
 
 extern "C" int ghmm_logscore_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                                 ghmm_corpus *const *corpora, int P, int final_state,
                                                 double *loglik_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, corpora, P, loglik_host != nullptr, FC_LOG, __func__, &v);
-    if (rc || corpora[0]->U == 0) return rc;
-    return run_logforward(ctx, v.dtab, n_models, v.NS, v.Nmax, corpora[0], final_state, loglik_host);
+    return fvocab_logscore(ctx, models, n_models, corpora, P, final_state, loglik_host, __func__);
 }
 
 extern "C" int ghmm_viterbi_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                                ghmm_corpus *const *corpora, int P, double *score_host)
 {
-    fvocab v;
-    int rc = fvocab_begin(ctx, models, n_models, corpora, P, score_host != nullptr, FC_LOG, __func__, &v);
-    if (rc || corpora[0]->U == 0) return rc;
-    if ((rc = run_viterbi_vocab(ctx, v, n_models, corpora[0]))) return rc;
-    return vocab_scores_out(ctx, n_models, corpora[0], score_host);
+    return fvocab_viterbi(ctx, models, n_models, corpora, P, score_host, __func__);
 }
 
-// The batch call's score table, then on the device and without a host round trip: every utterance's
-// winning word (k_vocab_best) and that word's lattice again with back-pointers on the log b already
-// in the workspace (k_viterbi_pick, over (blocks, words) like k_viterbi_multi).  One stream wait.
 extern "C" int ghmm_recognise_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                            ghmm_corpus *const *corpora, int P, int32_t *word_host,
                                            int32_t *path_host, double *score_host)
 {
-    fvocab v;
+    vocab_pass v;
     int rc = fvocab_begin(ctx, models, n_models, corpora, P, word_host && path_host && score_host, FC_LOG, __func__,
                           &v);
     if (rc || corpora[0]->U == 0) return rc;
-    const ghmm_corpus *c = corpora[0];
-    const lane_grid lg(v.Nmax, c->U);
-    if ((rc = ctx->best_word.grow((size_t)c->U))) return rc;
-    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
-    if ((rc = run_viterbi_vocab(ctx, v, n_models, c))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_VITERBI);
-        hipLaunchKernelGGL(k_vocab_best, dim3((unsigned)((c->U + 255) / 256)), dim3(256), 0, ctx->stream, n_models,
-                           c->U, (const double *)ctx->bt_ll, ctx->best_word);
-    }
-    if ((rc = launch_ok("k_vocab_best"))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_VITERBI);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_pick<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                               ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off,
-                                               (const int *)ctx->best_word, ctx->psi, ctx->path, ctx->sink,
-                                               c->order));
-    }
-    if ((rc = launch_ok("k_viterbi_pick"))) return rc;
-    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
-    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(word_host, ctx->best_word, (size_t)c->U * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
+    return vocab_decode(ctx, v, n_models, corpora[0], word_host, path_host, score_host);
 }

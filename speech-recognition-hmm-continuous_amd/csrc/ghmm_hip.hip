@@ -4,7 +4,8 @@
 // All arithmetic of the path happens in the kernels (ghmm_kernels.hpp,
 // ghmm_mfma.hpp, ghmm_pair.hpp).  No CPU fallback: without a gfx950 device every entry point that
 // needs one fails with GHMM_ERR_NODEVICE.  The full-covariance entry points are in ghmm_fullhost.hpp,
-// included at the end of this file: one translation unit.
+// included at the end of this file, and what the several-stream and vocabulary calls of both model
+// kinds share is in ghmm_lattice_host.hpp, included ahead of ghmm_viterbi: one translation unit.
 #include "ghmm.h"
 
 #include <hip/hip_runtime.h>
@@ -144,17 +145,14 @@ struct ghmm_ctx {
     dev_buf<unsigned char> psi, path;
 
     // ---- vocabulary passes
-    // ghmm_score_batch: the concatenated vocabulary model and the pass's tables, kept between calls
-    ghmm_model *bt_cat = nullptr;
-    // the several-stream vocabulary calls: bt_cat is stream 0's vocabulary, bt_cat_s[p] stream p's (p >= 1)
-    ghmm_model *bt_cat_s[GHMM_MAX_STREAMS] = {};
+    // stream p's concatenated vocabulary model of either kind, kept between calls (cat_slot; the
+    // single-stream calls use slot 0)
+    ghmm_model *bt_cat[GHMM_MAX_STREAMS] = {};
+    ghmm_fmodel *fbt_cat[GHMM_MAX_STREAMS] = {};
+    // a pass's host-built tables (vocab_tables, one_word_table): every call uploads its own before its
+    // launches, in stream order
     dev_buf<char> bt_tab;
-    dev_buf<double> bt_scale, bt_sinv, bt_ll;
-    // ghmm_score_full_batch: the same for the full-covariance vocabulary (the log P go to bt_ll)
-    ghmm_fmodel *fbt_cat = nullptr;
-    // the *_full_streams_batch calls: fbt_cat is stream 0's vocabulary, fbt_cat_s[p] stream p's (p >= 1)
-    ghmm_fmodel *fbt_cat_s[GHMM_MAX_STREAMS] = {};
-    dev_buf<char> fbt_tab;
+    dev_buf<double> bt_scale, bt_sinv, bt_ll; // the score table bt_ll[words][U] of both kinds
     dev_buf<int> best_word; // ghmm_recognise_streams / _full_streams: every utterance's winning word
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
@@ -433,20 +431,12 @@ extern "C" void ghmm_ctx_destroy(ghmm_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->bt_cat) {
-        ghmm_model_destroy(ctx, ctx->bt_cat);
-        ctx->bt_cat = nullptr;
-    }
-    for (ghmm_model *&cat : ctx->bt_cat_s)
+    for (ghmm_model *&cat : ctx->bt_cat)
         if (cat) {
             ghmm_model_destroy(ctx, cat);
             cat = nullptr;
         }
-    if (ctx->fbt_cat) {
-        ghmm_fmodel_destroy(ctx, ctx->fbt_cat);
-        ctx->fbt_cat = nullptr;
-    }
-    for (ghmm_fmodel *&cat : ctx->fbt_cat_s)
+    for (ghmm_fmodel *&cat : ctx->fbt_cat)
         if (cat) {
             ghmm_fmodel_destroy(ctx, cat);
             cat = nullptr;
@@ -2134,39 +2124,28 @@ extern "C" int ghmm_score(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, double *
     return GHMM_OK;
 }
 
-// The lattice of ghmm_viterbi on m's log A and the log b[F][N] in the workspace (L from fb_lanes, N <= 255):
-// paths and scores to the host, then the wait for the stream.  viterbi_ws sizes what it writes.
-static int viterbi_ws(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c, int L)
-{
-    int rc;
-    if ((rc = ctx->psi.grow((size_t)c->F * (L ? L : m->N) + 16))) return rc; // rows of L (N) bytes
-    return ctx->path.grow((size_t)c->F);
-}
+// ------------------------------------------------ what the two model kinds share on the host
+#include "ghmm_lattice_host.hpp"
 
+// The lattice of ghmm_viterbi on m's log A and the log b[F][N] in the workspace (L from fb_lanes, N <= 255;
+// psi in rows of L bytes, beyond 64 states of N): paths and scores to the host, then the wait for the stream.
 static int run_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int L, int32_t *path_host, double *score_host)
 {
     int rc;
-    if (c->U) {
-        if (L == 0) { // one wave per utterance
-            if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
-            kscope ks(ctx, GHMM_K_VITERBI);
-            hipLaunchKernelGGL(k_viterbi_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)2 * m->N * sizeof(double),
-                               ctx->stream, m->N, c->U, m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
-                               c->order, ctx->wide_flag);
-        } else {
-            const unsigned blocks = lane_grid(m->N, c->U).blocks;
-            kscope ks(ctx, GHMM_K_VITERBI);
-            GHMM_BY_LANES(L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, m->N, c->U,
-                                                m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
-                                                ctx->sink, c->order));
-        }
-        if ((rc = launch_ok("k_viterbi"))) return rc;
-        HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    if (c->U == 0) {
+        HIP_TRY(stream_sync(ctx));
+        return GHMM_OK;
     }
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
+    if (L) return run_viterbi_lanes(ctx, m->N, m->logA, c, path_host, score_host);
+    if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
+    { // one wave per utterance
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_viterbi_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)2 * m->N * sizeof(double),
+                           ctx->stream, m->N, c->U, m->logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik,
+                           c->order, ctx->wide_flag);
+    }
+    if ((rc = launch_ok("k_viterbi"))) return rc;
+    return viterbi_out(ctx, c, path_host, score_host);
 }
 
 extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_host,
@@ -2178,7 +2157,7 @@ extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_
     int L;
     if ((rc = fb_lanes(m, &L))) return rc;
     ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
-    if ((rc = ws_frames(ctx, m, c, false)) || (rc = viterbi_ws(ctx, m, c, L))) return rc;
+    if ((rc = ws_frames(ctx, m, c, false)) || (rc = viterbi_ws(ctx, c, L ? L : m->N))) return rc;
     if ((rc = run_emission(ctx, m, c, 2, ctx->b, nullptr))) return rc;
     return run_viterbi(ctx, m, c, L, path_host, score_host);
 }
@@ -2188,18 +2167,8 @@ extern "C" int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_
 static int check_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P)
 {
     ARG_CHECK(models && corpora && P >= 1 && P <= GHMM_MAX_STREAMS, "bad stream arguments");
-    for (int p = 0; p < P; p++) {
-        int rc = check_pair(models[p], corpora[p]);
-        if (rc) return rc;
-        if (models[p]->N != models[0]->N) {
-            ghmm_set_error("stream %d has %d states, stream 0 has %d", p, models[p]->N, models[0]->N);
-            return GHMM_ERR_ARG;
-        }
-        if (corpora[p]->U != corpora[0]->U || corpora[p]->len != corpora[0]->len) {
-            ghmm_set_error("stream %d: utterance count or lengths differ from stream 0", p);
-            return GHMM_ERR_ARG;
-        }
-    }
+    int rc = stream_checks(models, corpora, P, check_pair, [](int) { return GHMM_OK; });
+    if (rc) return rc;
     if (P > 1 && ctx->robust) {
         ghmm_set_error("GHMM_OPT_ROBUST is not available with several feature streams");
         return GHMM_ERR_UNSUPPORTED;
@@ -2286,72 +2255,59 @@ extern "C" int ghmm_score_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm
     return GHMM_OK;
 }
 
-// ------------------------------------------------ a vocabulary in one pass
-// ghmm_score_batch and the several-stream vocabulary calls (ghmm_score_streams_batch,
-// ghmm_viterbi_streams_batch, ghmm_recognise_streams; definitions in include/ghmm.h); the full-covariance
-// batch calls (ghmm_fullhost.hpp) share vocab_scores_out.
-
-// the pass's scores, bt_ll[n_models][U], to the host; waits for the stream
-static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, double *host)
+extern "C" int ghmm_viterbi_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
+                                    int P, int32_t *path_host, double *score_host)
 {
-    HIP_TRY(hipMemcpyAsync(host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
+    int rc = use(ctx);
+    if (rc || (rc = check_streams(ctx, models, corpora, P))) return rc;
+    if (P == 1) return ghmm_viterbi(ctx, models[0], corpora[0], path_host, score_host);
+    ghmm_model *m = models[0];
+    ghmm_corpus *c = corpora[0];
+    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
+    int L;
+    if ((rc = fb_lanes(m, &L))) return rc;
+    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
+    if (c->U == 0) return GHMM_OK;
+    if ((rc = viterbi_ws(ctx, c, L ? L : m->N))) return rc;
+    if ((rc = streams_emission(ctx, models, corpora, P, false, 2))) return rc;
+    return run_viterbi(ctx, m, c, L, path_host, score_host);
 }
 
+// ------------------------------------------------ a vocabulary in one pass
+// ghmm_score_batch, the several-stream vocabulary calls and the forward score in the log domain
+// (definitions in include/ghmm.h).  The checks, the tables, the lattice launches and the word decoder
+// are ghmm_lattice_host.hpp's; what is here is the diagonal side's own: its further refusals, the
+// gathers with their preparation, the emission with its fold, and word by word beyond 64 states.
+
 // A vocabulary of n_models words on P feature streams (models[k * P + p] = stream p of word k;
-// ghmm_score_batch passes P = 1): NS = its states, Nmax = the largest word's, cats[p] = stream p's
-// concatenated model (NS states x M_p mixtures, transitions unused), dtab = the table of the words'
-// recursions on the device.  The diagonal sibling of fvocab (ghmm_fullhost.hpp).
-struct dvocab {
-    int NS = 0, Nmax = 0;
-    const fwd_model *dtab = nullptr;
+// ghmm_score_batch passes P = 1) with cats[p] = stream p's concatenated model (NS states x M_p mixtures,
+// transitions unused)
+struct dvocab : vocab_pass {
     ghmm_model *cats[GHMM_MAX_STREAMS] = {};
 };
 
-// The concatenated models live in the context from one call to the next (a recogniser scores batch after
-// batch against one vocabulary: creating and freeing twenty device buffers per call was 0.75 ms of a
-// 0.9 ms call), ctx->bt_cat for stream 0 and ctx->bt_cat_s[p] for the later ones, each rebuilt when its
-// shape changes; the words' parameters are gathered into each by ONE launch, and it is prepared like a
-// model just set.  The pass's tables are built on the host and uploaded into one context buffer: the
-// words' recursions (dtab[k].A = word k's A, or its log A with log_domain, stream 0's; N; the offset of
-// the word's states in b) and per stream the gather kernel's sources (the word's parameters, for the
-// Gaussians g0 .. g0 + ng of that stream's concatenated model).  v->NS and v->Nmax are the caller's.
+// The concatenated models (ctx->bt_cat[p], cat_slot), the pass's tables (vocab_tables), then the words'
+// parameters gathered into each concatenated model by ONE launch, which is prepared like a model just
+// set.  v->NS and v->Nmax are the caller's.
 static int vocab_gather(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, int P, bool log_domain, dvocab *v)
 {
     int rc;
     for (int p = 0; p < P; p++) {
-        ghmm_model **slot = p ? &ctx->bt_cat_s[p] : &ctx->bt_cat;
-        const int M = models[p]->M, D = models[p]->D;
-        if (*slot && ((*slot)->N != v->NS || (*slot)->M != M || (*slot)->D != D)) {
-            ghmm_model_destroy(ctx, *slot);
-            *slot = nullptr;
-        }
-        if (!*slot) {
-            if ((rc = ghmm_model_create(ctx, v->NS, M, D, slot))) return rc;
-            HIP_TRY(hipMemsetAsync((*slot)->A, 0, (size_t)v->NS * v->NS * 8, ctx->stream));
-        }
-        v->cats[p] = *slot;
+        const int NS = v->NS, M = models[p]->M, D = models[p]->D;
+        rc = cat_slot(ctx, &ctx->bt_cat[p], NS, M, D, ghmm_model_destroy, [=](ghmm_model **slot) -> int {
+            int r = ghmm_model_create(ctx, NS, M, D, slot);
+            if (r) return r;
+            HIP_TRY(hipMemsetAsync((*slot)->A, 0, (size_t)NS * NS * 8, ctx->stream));
+            return GHMM_OK;
+        });
+        if (rc) return rc;
+        v->cats[p] = ctx->bt_cat[p];
     }
-    std::vector<fwd_model> tab((size_t)n_models);
-    std::vector<gather_src> src((size_t)n_models * P);
-    for (int p = 0; p < P; p++) {
-        int go = 0, so = 0;
-        for (int k = 0; k < n_models; k++) {
-            const ghmm_model *m = models[(size_t)k * P + p];
-            if (p == 0) tab[k] = {log_domain ? m->logA : m->A, m->N, so};
-            src[(size_t)p * n_models + k] = {m->c, m->mean, m->inv_var, m->det, go, m->N * m->M};
-            go += m->N * m->M;
-            so += m->N;
-        }
-    }
-    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = src.size() * sizeof(gather_src);
-    if ((rc = ctx->bt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
-    v->dtab = (const fwd_model *)ctx->bt_tab.p;
-    const gather_src *dsrc = (const gather_src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
-    // (the tables leave pageable host vectors: the copies complete before the call returns them)
-    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync((void *)dsrc, src.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const gather_src *dsrc;
+    rc = vocab_tables<gather_src>(ctx, models, n_models, P, log_domain, [](const ghmm_model *m, int g0) {
+        return gather_src{m->c, m->mean, m->inv_var, m->det, g0, m->N * m->M};
+    }, v, &dsrc);
+    if (rc) return rc;
     for (int p = 0; p < P; p++) {
         ghmm_model *cat = v->cats[p];
         hipLaunchKernelGGL(k_gather_models, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, cat->D,
@@ -2386,126 +2342,63 @@ static int vocab_emission(ghmm_ctx *ctx, const dvocab &v, ghmm_corpus *const *co
     return GHMM_OK;
 }
 
-// k_forward_multi over the n_models entries of v.dtab on the b in the workspace: log P with the
-// final-state term into bt_ll
-static int vocab_forward(ghmm_ctx *ctx, const dvocab &v, int n_models, const ghmm_corpus *c)
+// A vocabulary call behind its checks (U > 0, no word beyond 64 states) up to its lattice launch: room
+// for the score table, the gathers, and the streams' b (mode 0; the table holds A) or log b (mode 2; log A)
+static int dvocab_begin(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                        int mode, dvocab *v)
 {
     int rc;
+    if ((rc = ctx->bt_ll.grow((size_t)n_models * corpora[0]->U))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, P, mode == 2, v))) return rc;
+    return vocab_emission(ctx, *v, corpora, P, mode);
+}
+
+// ... and the linear score: log P with the final-state term, c_t and 1 / c_t into bt_scale and bt_sinv
+static int dvocab_score(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                        dvocab *v, double *loglik_host)
+{
+    int rc;
+    const ghmm_corpus *c = corpora[0];
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 0, v))) return rc;
     if ((rc = ctx->bt_scale.grow((size_t)n_models * c->F + 1)) ||
         (rc = ctx->bt_sinv.grow((size_t)n_models * c->F + 1)))
         return rc;
-    const lane_grid lg(v.Nmax, c->U);
-    kscope ks(ctx, GHMM_K_FORWARD);
-    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
-                                           0, ctx->stream, c->U, v.NS, c->F, v.dtab, ctx->b, c->off, ctx->bt_scale,
-                                           ctx->bt_sinv, ctx->bt_ll, ctx->sink, c->order, 1));
-    return launch_ok("k_forward_multi");
+    if ((rc = vocab_forward(ctx, *v, n_models, c, ctx->bt_scale, ctx->bt_sinv, 1))) return rc;
+    return vocab_scores_out(ctx, n_models, c, loglik_host);
 }
 
 extern "C" int ghmm_score_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                                 ghmm_corpus *c, double *loglik_host)
 {
+    dvocab v;
     int rc = use(ctx);
     if (rc) return rc;
-    ARG_CHECK(models && n_models > 0 && c, "null argument");
-    ARG_CHECK(loglik_host || c->U == 0, "null destination");
-    for (int k = 0; k < n_models; k++) ARG_CHECK(models[k], "null model");
-    // every model shares M and D: NS = the vocabulary's states, Nmax = the largest model's
-    const int M = models[0]->M, D = models[0]->D;
-    dvocab v;
-    for (int k = 0; k < n_models; k++) {
-        if (models[k]->M != M || models[k]->D != D) {
-            ghmm_set_error("%s: every model must have the same M and D", __func__);
-            return GHMM_ERR_UNSUPPORTED;
-        }
-        v.NS += models[k]->N;
-        v.Nmax = models[k]->N > v.Nmax ? models[k]->N : v.Nmax;
-    }
-    if (D != c->D) {
-        ghmm_set_error("models have %d coefficients per frame, corpus has %d", D, c->D);
-        return GHMM_ERR_ARG;
-    }
-    if (c->U == 0) return GHMM_OK;
-    if (v.Nmax > 64) { // the one-launch vocabulary loop holds one state per lane: word by word instead
+    // the shared checks on one stream, with this call's own text for another D
+    rc = vocab_checks(models, n_models, &c, 1, loglik_host != nullptr, __func__,
+                      [](const ghmm_model *m, const ghmm_corpus *cp) -> int {
+                          if (m->D == cp->D) return GHMM_OK;
+                          ghmm_set_error("models have %d coefficients per frame, corpus has %d", m->D, cp->D);
+                          return GHMM_ERR_ARG;
+                      }, &v);
+    if (rc || c->U == 0) return rc;
+    // model by model: beyond 64 states (the one-launch vocabulary loop holds one state per lane), and
+    // under GHMM_OPT_ROBUST (per-frame normalisation couples the models' densities)
+    if (v.Nmax > 64 || ctx->robust) {
         for (int k = 0; k < n_models; k++)
             if ((rc = ghmm_score(ctx, models[k], c, loglik_host + (size_t)k * c->U))) return rc;
         return GHMM_OK;
     }
-    if (ctx->robust) {
-        // per-frame normalisation couples the models' densities; score them one by one
-        for (int k = 0; k < n_models; k++)
-            if ((rc = ghmm_score(ctx, models[k], c, loglik_host + (size_t)k * c->U))) return rc;
-        return GHMM_OK;
-    }
-    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
-    if ((rc = vocab_gather(ctx, models, n_models, 1, false, &v)) || (rc = vocab_emission(ctx, v, &c, 1, 0)) ||
-        (rc = vocab_forward(ctx, v, n_models, c)))
-        return rc;
-    return vocab_scores_out(ctx, n_models, c, loglik_host);
+    return dvocab_score(ctx, models, n_models, &c, 1, &v, loglik_host);
 }
 
-// ---- several feature streams
-
-extern "C" int ghmm_viterbi_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
-                                    int P, int32_t *path_host, double *score_host)
-{
-    int rc = use(ctx);
-    if (rc || (rc = check_streams(ctx, models, corpora, P))) return rc;
-    if (P == 1) return ghmm_viterbi(ctx, models[0], corpora[0], path_host, score_host);
-    ghmm_model *m = models[0];
-    ghmm_corpus *c = corpora[0];
-    ARG_CHECK((path_host && score_host) || c->U == 0, "null destination");
-    int L;
-    if ((rc = fb_lanes(m, &L))) return rc;
-    ARG_CHECK(m->N <= 255, "too many states for byte back-pointers");
-    if (c->U == 0) return GHMM_OK;
-    if ((rc = viterbi_ws(ctx, m, c, L))) return rc;
-    if ((rc = streams_emission(ctx, models, corpora, P, false, 2))) return rc;
-    return run_viterbi(ctx, m, c, L, path_host, score_host);
-}
-
-// The checks of the three several-stream vocabulary calls (`what` = the entry point's name in their
-// texts; lanes_only: a word of more than 64 states is refused), each before anything is launched or
-// written; fills v->NS and v->Nmax.  The diagonal sibling of fvocab_begin's first half.
+// The checks of the several-stream vocabulary calls (`what` = the entry point's name in their texts):
+// the shared ones, then the diagonal side's own (lanes_only: a word of more than 64 states is refused),
+// each before anything is launched or written; fills v->NS and v->Nmax
 static int vocab_check(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
                        bool have_dest, bool lanes_only, const char *what, dvocab *v)
 {
-    int rc;
-    ARG_CHECK_AS(what, models && n_models > 0 && corpora, "null argument");
-    if (P < 1 || P > GHMM_MAX_STREAMS) {
-        ghmm_set_error("%s: 1 to %d feature streams (asked: %d)", what, GHMM_MAX_STREAMS, P);
-        return GHMM_ERR_ARG;
-    }
-    for (int p = 0; p < P; p++) ARG_CHECK_AS(what, corpora[p], "null argument");
-    const ghmm_corpus *c = corpora[0];
-    ARG_CHECK_AS(what, have_dest || c->U == 0, "null destination");
-    for (int k = 0; k < n_models * P; k++) ARG_CHECK_AS(what, models[k], "null model");
-    v->NS = v->Nmax = 0;
-    for (int k = 0; k < n_models; k++) {
-        const int N = models[(size_t)k * P]->N;
-        for (int p = 1; p < P; p++)
-            if (models[(size_t)k * P + p]->N != N) {
-                ghmm_set_error("%s: word %d: stream %d has %d states, stream 0 has %d", what, k, p,
-                               models[(size_t)k * P + p]->N, N);
-                return GHMM_ERR_ARG;
-            }
-        v->NS += N;
-        v->Nmax = N > v->Nmax ? N : v->Nmax;
-    }
-    for (int p = 0; p < P; p++)
-        for (int k = 1; k < n_models; k++)
-            if (models[(size_t)k * P + p]->M != models[p]->M || models[(size_t)k * P + p]->D != models[p]->D) {
-                if (P > 1) ghmm_set_error("%s: every model must have the same M and D (stream %d)", what, p);
-                else ghmm_set_error("%s: every model must have the same M and D", what);
-                return GHMM_ERR_UNSUPPORTED;
-            }
-    for (int p = 0; p < P; p++) {
-        if ((rc = check_pair(models[p], corpora[p]))) return rc;
-        if (corpora[p]->U != c->U || corpora[p]->len != c->len) {
-            ghmm_set_error("%s: stream %d: utterance count or lengths differ from stream 0", what, p);
-            return GHMM_ERR_ARG;
-        }
-    }
+    int rc = vocab_checks(models, n_models, corpora, P, have_dest, what, check_pair, v);
+    if (rc) return rc;
     if (P > 1 && ctx->robust) {
         ghmm_set_error("%s: GHMM_OPT_ROBUST is not available with several feature streams", what);
         return GHMM_ERR_UNSUPPORTED;
@@ -2534,29 +2427,7 @@ extern "C" int ghmm_score_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models
                 return rc;
         return GHMM_OK;
     }
-    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
-    if ((rc = vocab_gather(ctx, models, n_models, P, false, &v)) || (rc = vocab_emission(ctx, v, corpora, P, 0)) ||
-        (rc = vocab_forward(ctx, v, n_models, c)))
-        return rc;
-    return vocab_scores_out(ctx, n_models, c, loglik_host);
-}
-
-// the Viterbi vocabulary calls up to their score table in bt_ll: the gathers, the streams' log b folded
-// into b[F][NS], and k_viterbi_multi over the n_models entries of v->dtab (log A)
-static int vocab_viterbi(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
-                         dvocab *v)
-{
-    int rc;
-    const ghmm_corpus *c = corpora[0];
-    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
-    if ((rc = vocab_gather(ctx, models, n_models, P, true, v)) || (rc = vocab_emission(ctx, *v, corpora, P, 2)))
-        return rc;
-    const lane_grid lg(v->Nmax, c->U);
-    kscope ks(ctx, GHMM_K_VITERBI);
-    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                           ctx->stream, c->U, v->NS, v->dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
-                                           c->order));
-    return launch_ok("k_viterbi_multi");
+    return dvocab_score(ctx, models, n_models, corpora, P, &v, loglik_host);
 }
 
 extern "C" int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
@@ -2566,14 +2437,13 @@ extern "C" int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *mode
     int rc = use(ctx);
     if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, score_host != nullptr, true, __func__, &v)))
         return rc;
-    if (corpora[0]->U == 0) return GHMM_OK;
-    if ((rc = vocab_viterbi(ctx, models, n_models, corpora, P, &v))) return rc;
-    return vocab_scores_out(ctx, n_models, corpora[0], score_host);
+    const ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return GHMM_OK;
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v)) || (rc = vocab_viterbi(ctx, v, n_models, c)))
+        return rc;
+    return vocab_scores_out(ctx, n_models, c, score_host);
 }
 
-// The batch call's score table, then on the device and without a host round trip: every utterance's
-// winning word (k_vocab_best) and that word's lattice again with back-pointers on the log b already
-// in the workspace (k_viterbi_pick, over (blocks, words) like k_viterbi_multi).  One stream wait.
 extern "C" int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                                       ghmm_corpus *const *corpora, int P, int32_t *word_host, int32_t *path_host,
                                       double *score_host)
@@ -2583,50 +2453,13 @@ extern "C" int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, 
     if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, word_host && path_host && score_host, true,
                                 __func__, &v)))
         return rc;
-    const ghmm_corpus *c = corpora[0];
-    if (c->U == 0) return GHMM_OK;
-    const lane_grid lg(v.Nmax, c->U);
-    if ((rc = ctx->best_word.grow((size_t)c->U))) return rc;
-    if ((rc = ctx->psi.grow((size_t)c->F * lg.L + 16))) return rc; // rows of L bytes
-    if ((rc = ctx->path.grow((size_t)c->F))) return rc;
-    if ((rc = vocab_viterbi(ctx, models, n_models, corpora, P, &v))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_VITERBI);
-        hipLaunchKernelGGL(k_vocab_best, dim3((unsigned)((c->U + 255) / 256)), dim3(256), 0, ctx->stream, n_models,
-                           c->U, (const double *)ctx->bt_ll, ctx->best_word);
-    }
-    if ((rc = launch_ok("k_vocab_best"))) return rc;
-    {
-        kscope ks(ctx, GHMM_K_VITERBI);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_pick<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
-                                               ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off,
-                                               (const int *)ctx->best_word, ctx->psi, ctx->path, ctx->sink,
-                                               c->order));
-    }
-    if ((rc = launch_ok("k_viterbi_pick"))) return rc;
-    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
-    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(word_host, ctx->best_word, (size_t)c->U * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
-    HIP_TRY(stream_sync(ctx));
-    return GHMM_OK;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
+    return vocab_decode(ctx, v, n_models, corpora[0], word_host, path_host, score_host);
 }
 
-// ---- the forward score in the log domain (ghmm_logscore and its three siblings; definitions in
+// ---- the forward score in the log domain (ghmm_logscore and its three companions; definitions in
 // include/ghmm.h): ghmm_viterbi's log b, the sum over paths where that takes the best one
-
-// k_logforward_multi over the n_models entries of dtab (log A) on the log b[F][NS] in the workspace:
-// la_{T-1}(N_k - 1), or LSE_j la_{T-1}(j) with final_state == 0, into bt_ll
-static int vocab_logforward(ghmm_ctx *ctx, const fwd_model *dtab, int n_models, int NS, int Nmax,
-                            const ghmm_corpus *c, int final_state)
-{
-    const lane_grid lg(Nmax, c->U);
-    kscope ks(ctx, GHMM_K_FORWARD);
-    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
-                                           0, ctx->stream, c->U, NS, dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
-                                           c->order, final_state));
-    return launch_ok("k_logforward_multi");
-}
 
 // One word behind its checks (U > 0; L from fb_lanes): the streams' log b folded into b[F][N] as in
 // ghmm_viterbi_streams, then the lattice on models[0]'s log A: k_logforward_multi on a table of one
@@ -2654,10 +2487,9 @@ static int logscore_word(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *
         HIP_TRY(stream_sync(ctx));
         return GHMM_OK;
     }
-    const fwd_model one = {m->logA, m->N, 0};
-    if ((rc = ctx->bt_ll.grow((size_t)c->U)) || (rc = ctx->bt_tab.grow(sizeof one))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = vocab_logforward(ctx, (const fwd_model *)ctx->bt_tab.p, 1, m->N, m->N, c, final_state))) return rc;
+    vocab_pass one;
+    if ((rc = one_word_table(ctx, m->logA, m->N, c, &one)) || (rc = vocab_logforward(ctx, one, 1, c, final_state)))
+        return rc;
     return vocab_scores_out(ctx, 1, c, loglik_host);
 }
 
@@ -2704,9 +2536,8 @@ static int logscore_vocab(ghmm_ctx *ctx, ghmm_model *const *models, int n_models
                 return rc;
         return GHMM_OK;
     }
-    if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
-    if ((rc = vocab_gather(ctx, models, n_models, P, true, &v)) || (rc = vocab_emission(ctx, v, corpora, P, 2)) ||
-        (rc = vocab_logforward(ctx, v.dtab, n_models, v.NS, v.Nmax, c, final_state)))
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v)) ||
+        (rc = vocab_logforward(ctx, v, n_models, c, final_state)))
         return rc;
     return vocab_scores_out(ctx, n_models, c, loglik_host);
 }

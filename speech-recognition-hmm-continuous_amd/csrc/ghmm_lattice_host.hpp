@@ -1,0 +1,270 @@
+// ghmm_lattice_host.hpp — what the several-stream and vocabulary calls of both model kinds share on
+// the host.  Part of ghmm_hip.hip's translation unit, included once ahead of ghmm_viterbi: the diagonal
+// entry points behind it and the full-covariance ones (ghmm_fullhost.hpp) call into it.  Once an emission
+// launch has written b or log b into the workspace nothing here knows which kind of Gaussian produced it:
+// the helpers see the context, a corpus, a table of the words' recursions and the workspace.  The
+// checks and the host-built tables are templates over the model type (ghmm_model and ghmm_fmodel both
+// have N, M, D, A and logA) and take the kind's own pair check (check_pair, check_full).
+
+// A vocabulary pass: NS = the vocabulary's states, Nmax = the largest word's, dtab = the table of the
+// words' recursions on the device (dtab[k] = {word k's A or log A, its N, the offset of its states in
+// b[F][NS]}).  A single word is a vocabulary of one (one_word_table).
+struct vocab_pass {
+    int NS = 0, Nmax = 0;
+    const fwd_model *dtab = nullptr;
+};
+
+// ------------------------------------------------ checks
+
+// One word on P feature streams, models[p] / corpora[p] = stream p (behind the caller's check of the
+// arrays and of P): per stream the kind's pair check, the states and the utterance lengths against
+// stream 0's, then whatever else the caller checks per stream (`then`: the full-covariance E-step's
+// statistics vector).  Called by check_streams and check_full_streams.
+template <class Model, class Pair, class Then>
+static int stream_checks(Model *const *models, ghmm_corpus *const *corpora, int P, Pair pair, Then then)
+{
+    for (int p = 0; p < P; p++) {
+        int rc = pair(models[p], corpora[p]);
+        if (rc) return rc;
+        if (models[p]->N != models[0]->N) {
+            ghmm_set_error("stream %d has %d states, stream 0 has %d", p, models[p]->N, models[0]->N);
+            return GHMM_ERR_ARG;
+        }
+        if (corpora[p]->U != corpora[0]->U || corpora[p]->len != corpora[0]->len) {
+            ghmm_set_error("stream %d: utterance count or lengths differ from stream 0", p);
+            return GHMM_ERR_ARG;
+        }
+        if ((rc = then(p))) return rc;
+    }
+    return GHMM_OK;
+}
+
+// A vocabulary of n_models words on P feature streams (models[k * P + p] = stream p of word k,
+// corpora[p] = stream p of the utterances; the single-stream calls pass P = 1).  `what` = the entry
+// point's name in the texts.  Nothing is launched, grown or written here; fills v->NS and v->Nmax.
+// Called by vocab_check (diagonal, which adds its own refusals behind it) and fvocab_begin.
+template <class Model, class Pair>
+static int vocab_checks(Model *const *models, int n_models, ghmm_corpus *const *corpora, int P, bool have_dest,
+                        const char *what, Pair pair, vocab_pass *v)
+{
+    int rc;
+    ARG_CHECK_AS(what, models && n_models > 0 && corpora, "null argument");
+    if (P < 1 || P > GHMM_MAX_STREAMS) {
+        ghmm_set_error("%s: 1 to %d feature streams (asked: %d)", what, GHMM_MAX_STREAMS, P);
+        return GHMM_ERR_ARG;
+    }
+    for (int p = 0; p < P; p++) ARG_CHECK_AS(what, corpora[p], "null argument");
+    const ghmm_corpus *c = corpora[0];
+    ARG_CHECK_AS(what, have_dest || c->U == 0, "null destination");
+    for (int k = 0; k < n_models * P; k++) ARG_CHECK_AS(what, models[k], "null model");
+    v->NS = v->Nmax = 0;
+    for (int k = 0; k < n_models; k++) {
+        const int N = models[(size_t)k * P]->N;
+        for (int p = 1; p < P; p++)
+            if (models[(size_t)k * P + p]->N != N) {
+                ghmm_set_error("%s: word %d: stream %d has %d states, stream 0 has %d", what, k, p,
+                               models[(size_t)k * P + p]->N, N);
+                return GHMM_ERR_ARG;
+            }
+        v->NS += N;
+        v->Nmax = N > v->Nmax ? N : v->Nmax;
+    }
+    for (int p = 0; p < P; p++)
+        for (int k = 1; k < n_models; k++)
+            if (models[(size_t)k * P + p]->M != models[p]->M || models[(size_t)k * P + p]->D != models[p]->D) {
+                if (P > 1) ghmm_set_error("%s: every model must have the same M and D (stream %d)", what, p);
+                else ghmm_set_error("%s: every model must have the same M and D", what);
+                return GHMM_ERR_UNSUPPORTED;
+            }
+    for (int p = 0; p < P; p++) {
+        if ((rc = pair(models[p], corpora[p]))) return rc;
+        if (corpora[p]->U != c->U || corpora[p]->len != c->len) {
+            ghmm_set_error("%s: stream %d: utterance count or lengths differ from stream 0", what, p);
+            return GHMM_ERR_ARG;
+        }
+    }
+    return GHMM_OK;
+}
+
+// ------------------------------------------------ tables and the cached concatenated models
+
+// The concatenated vocabulary of one stream lives in the context from one call to the next (a recogniser
+// scores batch after batch against one vocabulary: creating and freeing twenty device buffers per call
+// was 0.75 ms of a 0.9 ms call): *slot stays while its shape is (N, M, D), otherwise it is destroyed and
+// `create` makes a new one.  Called by vocab_gather and fvocab_begin.
+template <class Model, class Create>
+static int cat_slot(ghmm_ctx *ctx, Model **slot, int N, int M, int D, void (*destroy)(ghmm_ctx *, Model *),
+                    Create create)
+{
+    if (*slot && ((*slot)->N != N || (*slot)->M != M || (*slot)->D != D)) {
+        destroy(ctx, *slot);
+        *slot = nullptr;
+    }
+    return *slot ? GHMM_OK : create(slot);
+}
+
+// A pass's tables, built on the host and uploaded into the context's one table buffer, ahead of the
+// launches that read them on the same stream: the words' recursions (dtab[k].A = word k's A, or its log A
+// with log_domain, stream 0's; N; the offset of the word's states in b), then from the next 16-byte
+// boundary every stream's gather sources, *dsrc (src(m, g0) = the kind's source for word model m, whose
+// Gaussians go to g0 .. g0 + m->N * m->M of that stream's concatenated model; stream p's n_models
+// entries start at (*dsrc)[p * n_models]).  Called by vocab_gather and fvocab_begin.
+template <class Src, class Model, class MakeSrc>
+static int vocab_tables(ghmm_ctx *ctx, Model *const *models, int n_models, int P, bool log_domain, MakeSrc src,
+                        vocab_pass *v, const Src **dsrc)
+{
+    int rc;
+    std::vector<fwd_model> tab((size_t)n_models);
+    std::vector<Src> srcs((size_t)n_models * P);
+    for (int p = 0; p < P; p++) {
+        int go = 0, so = 0;
+        for (int k = 0; k < n_models; k++) {
+            const Model *m = models[(size_t)k * P + p];
+            if (p == 0) tab[k] = {log_domain ? m->logA : m->A, m->N, so};
+            srcs[(size_t)p * n_models + k] = src(m, go);
+            go += m->N * m->M;
+            so += m->N;
+        }
+    }
+    const size_t tab_bytes = tab.size() * sizeof(fwd_model), src_bytes = srcs.size() * sizeof(Src);
+    if ((rc = ctx->bt_tab.grow(tab_bytes + src_bytes + 16))) return rc;
+    v->dtab = (const fwd_model *)ctx->bt_tab.p;
+    *dsrc = (const Src *)(ctx->bt_tab + ((tab_bytes + 15) / 16) * 16);
+    // (the tables leave pageable host vectors: the copies complete before the call returns them)
+    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((void *)*dsrc, srcs.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return GHMM_OK;
+}
+
+// A single word as a vocabulary of one, for the log-domain score's lattice launch: its table (log A)
+// into the table buffer, bt_ll for its scores.  Called by logscore_word, ghmm_logscore_full and
+// ghmm_logscore_full_streams.
+static int one_word_table(ghmm_ctx *ctx, const double *logA, int N, const ghmm_corpus *c, vocab_pass *v)
+{
+    int rc;
+    const fwd_model one = {logA, N, 0};
+    if ((rc = ctx->bt_ll.grow((size_t)c->U)) || (rc = ctx->bt_tab.grow(sizeof one))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->bt_tab, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    v->NS = v->Nmax = N;
+    v->dtab = (const fwd_model *)ctx->bt_tab.p;
+    return GHMM_OK;
+}
+
+// ------------------------------------------------ the vocabulary lattices
+// Each runs over the n_models entries of v.dtab on the b or log b[F][NS] in the workspace, one state per
+// lane (Nmax <= 64), and writes bt_ll[n_models][U].  Called by the batch calls of both kinds.
+
+// k_forward_multi on b: log P, with the final-state term if final_state; scale / sinv: n_models * F + 1
+// doubles each for c_t and 1 / c_t, or the sink where nobody reads them
+static int vocab_forward(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const ghmm_corpus *c, double *scale,
+                         double *sinv, int final_state)
+{
+    const lane_grid lg(v.Nmax, c->U);
+    kscope ks(ctx, GHMM_K_FORWARD);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_forward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                           ctx->stream, c->U, v.NS, c->F, v.dtab, ctx->b, c->off, scale, sinv,
+                                           ctx->bt_ll, ctx->sink, c->order, final_state));
+    return launch_ok("k_forward_multi");
+}
+
+// k_viterbi_multi on log b (dtab: log A): the best path's score
+static int vocab_viterbi(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const ghmm_corpus *c)
+{
+    const lane_grid lg(v.Nmax, c->U);
+    kscope ks(ctx, GHMM_K_VITERBI);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                           ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                           c->order));
+    return launch_ok("k_viterbi_multi");
+}
+
+// k_logforward_multi on log b (dtab: log A): la_{T-1}(N_k - 1), or LSE_j la_{T-1}(j) with final_state == 0
+static int vocab_logforward(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const ghmm_corpus *c, int final_state)
+{
+    const lane_grid lg(v.Nmax, c->U);
+    kscope ks(ctx, GHMM_K_FORWARD);
+    GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logforward_multi<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE),
+                                           0, ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off, ctx->bt_ll, ctx->sink,
+                                           c->order, final_state));
+    return launch_ok("k_logforward_multi");
+}
+
+// the pass's scores, bt_ll[n_models][U], to the host; waits for the stream
+static int vocab_scores_out(ghmm_ctx *ctx, int n_models, const ghmm_corpus *c, double *host)
+{
+    HIP_TRY(hipMemcpyAsync(host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+// ------------------------------------------------ Viterbi paths
+
+// what a Viterbi lattice writes: psi in rows of `row` bytes per frame (the lanes per utterance, or the
+// states of a model beyond 64), and the state per frame
+static int viterbi_ws(ghmm_ctx *ctx, const ghmm_corpus *c, int row)
+{
+    int rc;
+    if ((rc = ctx->psi.grow((size_t)c->F * row + 16))) return rc;
+    return ctx->path.grow((size_t)c->F);
+}
+
+// a Viterbi lattice's paths (ctx->path) and scores (ctx->loglik) to the host; waits for the stream
+static int viterbi_out(ghmm_ctx *ctx, const ghmm_corpus *c, int32_t *path_host, double *score_host)
+{
+    int rc;
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
+// k_viterbi of one word of N <= 64 states on its log A and the log b[F][N] in the workspace (psi and
+// path sized by the caller, U > 0), then viterbi_out.  Called by run_viterbi (diagonal), ghmm_viterbi_full
+// and ghmm_viterbi_full_streams.
+static int run_viterbi_lanes(ghmm_ctx *ctx, int N, const double *logA, const ghmm_corpus *c, int32_t *path_host,
+                             double *score_host)
+{
+    int rc;
+    const lane_grid lg(N, c->U);
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, N, c->U,
+                                               logA, ctx->b, c->off, ctx->psi, ctx->path, ctx->loglik, ctx->sink,
+                                               c->order));
+    }
+    if ((rc = launch_ok("k_viterbi"))) return rc;
+    return viterbi_out(ctx, c, path_host, score_host);
+}
+
+// The word decoder behind its emission launches: the score table (vocab_viterbi), then on the device and
+// without a host round trip every utterance's winning word (k_vocab_best) and that word's lattice again
+// with back-pointers on the log b already in the workspace (k_viterbi_pick, over (blocks, words) like
+// k_viterbi_multi).  One stream wait.  Called by ghmm_recognise_streams and ghmm_recognise_full_streams.
+static int vocab_decode(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const ghmm_corpus *c, int32_t *word_host,
+                        int32_t *path_host, double *score_host)
+{
+    int rc;
+    const lane_grid lg(v.Nmax, c->U);
+    if ((rc = ctx->best_word.grow((size_t)c->U)) || (rc = viterbi_ws(ctx, c, lg.L))) return rc;
+    if ((rc = vocab_viterbi(ctx, v, n_models, c))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_vocab_best, dim3((unsigned)((c->U + 255) / 256)), dim3(256), 0, ctx->stream, n_models,
+                           c->U, (const double *)ctx->bt_ll, ctx->best_word);
+    }
+    if ((rc = launch_ok("k_vocab_best"))) return rc;
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_viterbi_pick<LL>, dim3(lg.blocks, (unsigned)n_models), dim3(WAVE), 0,
+                                               ctx->stream, c->U, v.NS, v.dtab, ctx->b, c->off,
+                                               (const int *)ctx->best_word, ctx->psi, ctx->path, ctx->sink,
+                                               c->order));
+    }
+    if ((rc = launch_ok("k_viterbi_pick"))) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)n_models * c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(word_host, ctx->best_word, (size_t)c->U * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F && (rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+    HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
