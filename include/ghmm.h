@@ -168,12 +168,32 @@ int64_t ghmm_corpus_frames(const ghmm_corpus *c);
 int ghmm_corpus_utterances(const ghmm_corpus *c);
 
 /* creating_initial_model (TF:732-1317) on the device, from a corpus resident in HBM:
- * uniform segmentation, LBG splitting (x1.005 / x0.995), three nearest-mean passes per
- * split, per-cell variance floored at 1e-5, weights floored and renormalised, one-step
- * left-to-right transitions.  The distance / accumulation passes run on the GPU (they
- * are the statistics kernels fed with one-hot weights), the cell bookkeeping (splitting
- * order, empty cells) on the host.  Fills model `m` (its N, M, D).  Synchronises.
- */
+ * ghmm_init_model's definition (ghmm_init.c), written into `m` (its N, M, D).  Synchronises.
+ *   Segmentation: uniform, every utterance cut into N runs of T / N frames, the first T % N runs one
+ *     frame longer (TF:1005-1013); state i owns run i.  A state that owns no frame gets the host's
+ *     0/0 values (NaN mean, inverse variance, det and weights); the other states are not affected.
+ *   A: a_ij = 1 / min(2, N - i) for j = i, i + 1, else 0 (TF:774-806).
+ *   Cells: the state's mean first; while 2n < M every cell is split x1.005 / x0.995, otherwise the
+ *     M - n cells of largest distortion are, in `sorting`'s order (adjacent swaps, strict <,
+ *     TF:1289-1315).  Each level runs three nearest-mean passes: squared Euclidean distance summed in
+ *     coefficient order, strict < from 1e20, so the lowest cell wins a tie and a cell whose mean is NaN
+ *     is never chosen.  After every pass mean = sum / count, and empty cells are re-seeded
+ *     x1.005 / x0.995 from the cells of largest distortion, in the host's order.
+ *   Variances: one more classification against the final cells; per coefficient the squared
+ *     deviations from the CELL MEAN over the count, floored at 1e-5; det = their product in
+ *     coefficient order, then inverted; weights = count / (frames of the state), floored at 1e-5 and
+ *     renormalised in index order.
+ *   One difference: a frame farther than 1e20 from every cell takes cell 0, where the host carries the
+ *     previous frame's cell.  Reached only when some frame lies at least 1e10 from every cell of its
+ *     state.
+ * The sums are added in a fixed order of the device's own, so the values differ from the host's in the
+ * last bits; the discrete parts (A, every assignment and count, hence c) are the host's wherever neither a
+ * frame nor a distortion that decides a split or a re-seed sits within rounding of a tie.  Two calls on the
+ * same inputs give the same bits.  No cap on M (where each part runs).
+ * An empty corpus or a corpus of another D: GHMM_ERR_ARG before anything is written.  A failure later on
+ * (an allocation, a launch) leaves the model's parameters undefined: set or initialise it again.
+ * The context's workspace is overwritten: GHMM_BUF_GAMMA holds the one-hot state rows, GHMM_BUF_POST is
+ * refused until the next emission. */
 int ghmm_model_init(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c);
 
 /* ---------------------------------------------------- sufficient statistics */
@@ -798,7 +818,8 @@ int ghmm_model_init_comm(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_comm
  *     ghmm_mstep_full_dev (D = 1: det = var, inverse = 1 / var) WITHOUT treat_zero_det; weights =
  *     count / (frames of the state), floored at 1e-5 and renormalised in index order; mean = the cell.
  *   One difference: a frame farther than 1e20 from every cell takes cell 0 (the host carries the
- *     previous frame's cell).  Not reachable on finite features of sane magnitude.
+ *     previous frame's cell).  Reached only when some frame lies at least 1e10 from every cell of its
+ *     state.
  * Given equal sums the quotients, the inverse, det and the weights are the host's bit for bit (the
  * shared, uncontracted bodies of the device M-step).  The sums themselves are added block by block in a
  * fixed order, so they differ from the host's frame-order sums in the last bits; the discrete parts (A,

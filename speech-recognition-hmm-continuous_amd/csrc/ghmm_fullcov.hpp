@@ -601,8 +601,8 @@ k_fmstep_state(int N, int M, int D, const double *__restrict__ stats, double nor
 // a lane per frame reads conflict-free).  Classification: wave w of the four takes cells w, w + 4, ... in
 // ascending order with the host's strict '<' from 1e20 (a NaN distance is never smaller); lane r of wave 0
 // then takes the smallest of the four candidates, the lowest cell among equals — the cell the host's one
-// ascending scan keeps.  No candidate: cell 0 (the host carries the previous frame's cell; unreachable on
-// finite features).  The distance is the host's sum, uncontracted, in coefficient order.
+// ascending scan keeps.  No candidate: cell 0 (the host carries the previous frame's cell; reached only by
+// a frame >= 1e10 from every cell of its state).  The distance is the host's sum, uncontracted, in coefficient order.
 // Accumulation: entry (cell c, l) of the block's [n_cells][E2] table in LDS belongs to ONE thread, the one
 // with tid % E2 == l and tid / E2 == c % (FI_THREADS / E2), which walks the staged frames in order: no
 // atomics, and a block's sums are the frames' in corpus order.  l < D: x[l]; l == D: 1; l == D + 1: the distance.

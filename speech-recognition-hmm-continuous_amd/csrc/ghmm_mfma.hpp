@@ -43,7 +43,7 @@ constexpr int EM_WAVES = 8;        // waves per block of the generic emission ke
 constexpr int EM_XR = 16;          // frame-tile doubles per lane: 16*D/64, D <= 64
 
 // Offsets for the expanded forms: offs[c][DP] = mean of the means of tile c's real
-// Gaussians (0 beyond D); oglob[d] = mean of all means (grid = NT + D blocks).
+// Gaussians (0 beyond D); oglob[d] = mean of all finite means (grid = NT + D blocks).
 __global__ void __launch_bounds__(64)
 k_prepare_offsets(int N, int M, int D, int Mp, int NT, int DP, const double *__restrict__ mean,
                   double *__restrict__ offs, double *__restrict__ oglob)
@@ -64,17 +64,35 @@ k_prepare_offsets(int N, int M, int D, int Mp, int NT, int DP, const double *__r
             offs[(size_t)q * DP + d] = cnt ? o / cnt : 0.0;
         }
     } else {
+        // (a mean that is not finite — the 0/0 cells of a state without frames in ghmm_model_init's
+        // k-means passes — stays out: one such Gaussian would turn every Gaussian's sums into NaN.
+        // This holds for every model set from the host: the expanded forms of its finite Gaussians
+        // no longer turn NaN beside a Gaussian with a non-finite mean, whose own values stay NaN.
+        // The branch above is left as it was on purpose: offs[] is read by no kernel, the tiles'
+        // own offsets are otile / dtile, taken from a single finite-conditioned Gaussian's mean.)
         __shared__ double sh[64];
+        __shared__ int shn[64];
         const int d = q - NT, G = N * M;
         double o = 0.0;
-        for (int g = t; g < G; g += 64) o += mean[(size_t)g * D + d];
+        int cnt = 0;
+        for (int g = t; g < G; g += 64) {
+            const double v = mean[(size_t)g * D + d];
+            if (isfinite(v)) {
+                o += v;
+                cnt++;
+            }
+        }
         sh[t] = o;
+        shn[t] = cnt;
         __syncthreads();
         for (int k = 32; k > 0; k >>= 1) {
-            if (t < k) sh[t] += sh[t + k];
+            if (t < k) {
+                sh[t] += sh[t + k];
+                shn[t] += shn[t + k];
+            }
             __syncthreads();
         }
-        if (t == 0) oglob[d] = sh[0] / (double)G;
+        if (t == 0) oglob[d] = shn[0] ? sh[0] / (double)shn[0] : 0.0;
     }
 }
 
