@@ -380,6 +380,50 @@ int ghmm_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int32_t *path_hos
  * second identical call repeats every byte. */
 int ghmm_logscore(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int final_state, double *loglik_host);
 
+/* ghmm_estep with every quantity formed in the log domain (absent from the reference): where
+ * ghmm_estep's linear densities underflow to 0 on a whole frame (c_t = 1/0, NaN statistics, and a NaN
+ * model out of ghmm_mstep) this call keeps finite statistics.  ghmm_estep's contract otherwise: the same
+ * ghmm_stats_create vector, overwritten by the launches ghmm_estep makes, one partial per utterance;
+ * asynchronous on the context's stream; bitwise reproducible (a second identical call repeats every
+ * byte); GHMM_OPT_DELTA and GHMM_OPT_PARTIALS honoured; GHMM_OPT_ROBUST has no effect, as in
+ * ghmm_logscore; a full-covariance statistics vector or one of another shape gives GHMM_ERR_ARG;
+ * ghmm_mstep, ghmm_stats_allreduce and ghmm_stats_loglik take the result as it is.  1 to 512 states;
+ * above that GHMM_ERR_UNSUPPORTED before anything is launched or written.
+ * Emission: e_m = log(wk_m) - aux_m / 2 and log b_i(t) are what ghmm_viterbi's emission launch writes,
+ * bit for bit, on either tier (GHMM_OPT_KERNELS 1 and default).
+ *     post_t(i,m) = exp(e_m - mx_i) / sum_m' exp(e_m' - mx_i),  mx_i = max_m e_m
+ * the very terms log b's own sum is made of; 0 where log b_i(t) = -inf.
+ * Lattice: log a_ij is the model's log A (a_ij > 0 ? log(a_ij) : -inf); a transition with a_ij == 0 is
+ * not a term; LSE as at ghmm_logscore.
+ *     la_0(j)      = (j == 0 ? 0 : -inf) + log b_j(0)
+ *     la_t(j)      = LSE_{i : a_ij > 0} (la_{t-1}(i) + log a_ij) + log b_j(t)     (ghmm_logscore's)
+ *     lbe_{T-1}(i) = (i == N-1 ? 0 : -inf)
+ *     lbe_t(i)     = LSE_{j : a_ij > 0} (log a_ij + (log b_j(t+1) + lbe_{t+1}(j)))
+ *     log P_u      = la_{T-1}(N-1)            -> GHMM_BUF_LOGLIK and the vector's loglik: the bits of
+ *                                             ghmm_logscore with final_state = 1
+ *     log Z_u      = LSE_j la_{T-1}(j)        the normaliser of gamma and xi (ghmm_logscore's final_state = 0)
+ *     gamma_t(i)   = exp(la_t(i) + lbe_t(i) - log Z_u)
+ *     xi_t(i,j)    = exp(la_t(i) + log a_ij + log b_j(t+1) + lbe_{t+1}(j) - log Z_u),
+ *                    t < T-1, a_ij > 0, i <= j <= i + delta
+ *     num_a[i][j] = sum_u sum_{t<T-1} xi_t(i,j);  den_a[i] = sum_u sum_{t<T-1} gamma_t(i);
+ *     den_c[i] = sum_u sum_{t<T} gamma_t(i);  num_c / num_mu / num_var: calc_mix_param on
+ *     w = gamma * post, the launches of ghmm_estep.
+ * The normaliser is log Z_u, not log P_u: the reference's scaled recursions give gamma = alpha^ beta^ / c_t,
+ * which divides by the probability of the observations over ALL end states while beta starts in the
+ * last state only, so a frame's gammas sum to exp(log P_u - log Z_u) <= 1, the same value at every t.
+ * An utterance with T < N or no path into the last state has every lbe = -inf: its gammas are exactly
+ * 0 and log P_u = -inf, as in the linear call.  Where log Z_u is not finite the utterance's gamma rows
+ * are 0 and it adds nothing to any sum except loglik (its log P_u as it is) and n_utt.  T = 0 adds 0 to
+ * loglik and counts in n_utt.  U = 0 gives an all-zero vector.  A NaN log b (det == 0) gives the
+ * formula's values.
+ * Up to 64 states the lattice is ghmm_estep_full_log's two launches (one state per lane); beyond that
+ * one wave per utterance with the states in LDS (k_logfb_wide_fwd / k_logfb_wide_bwd: a band-diagonal
+ * log A takes two-term steps, any other the dense ones of N exp per state and frame).
+ * Afterwards ghmm_fetch returns GHMM_BUF_B: log b, _POST, _GAMMA, _LOGLIK, _ALPHA: la, _BETA: lbe; the
+ * row API does not reuse these buffers and no linear beta pass is started on them.  One launch under
+ * GHMM_K_EMISSION, the two lattice launches under GHMM_K_FORWARD, none under GHMM_K_BACKWARD. */
+int ghmm_estep_log(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *stats);
+
 /* ------------- several-stream vocabularies of diagonal models: Viterbi, batched scoring and word decoding */
 
 /* ghmm_viterbi's lattice on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...): every
@@ -462,6 +506,18 @@ int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_model
  * Synchronises; a second identical call repeats every byte. */
 int ghmm_logscore_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
                           int n_streams, int final_state, double *loglik_host);
+/* ghmm_estep_log (above) on several feature streams, as ghmm_estep_streams is ghmm_estep on them:
+ * log b = ((log b^0 + log b^1) + ...) folded exactly as in ghmm_viterbi_streams, stream p's posteriors
+ * kept apart, ONE lattice on models[0]'s log A, then ghmm_estep's statistics launches once per stream on
+ * the common gamma and stream p's posteriors, frames and means; the transition sums, den_c, log P and
+ * the exemplar count are the same bits in every stats[p].  n_streams == 1 is ghmm_estep_log itself, the
+ * same bits.  The checks and refusals are ghmm_estep_streams's (check by check, then every stream's
+ * vector) and more than 512 states gives GHMM_ERR_UNSUPPORTED, each before anything is launched or
+ * written.  Afterwards GHMM_BUF_B holds the summed log b[F][N], _GAMMA, _LOGLIK, _ALPHA (la) and _BETA
+ * (lbe) are served, and GHMM_BUF_POST gives GHMM_ERR_ARG as after ghmm_estep_streams.  2 n_streams - 1
+ * launches under GHMM_K_EMISSION, two under GHMM_K_FORWARD.  Asynchronous. */
+int ghmm_estep_log_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora,
+                           int n_streams, ghmm_stats *const *stats);
 /* loglik_host[k*U + u] = ghmm_logscore_streams of word k alone, the vocabulary in one pass as laid out
  * above: the gathers, one log-emission launch per stream over its concatenated vocabulary, the folds,
  * and ONE lattice launch over every (word, utterance) pair on stream 0's log A (2 n_streams - 1 launches

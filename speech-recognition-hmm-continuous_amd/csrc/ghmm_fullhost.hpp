@@ -491,30 +491,6 @@ extern "C" int ghmm_estep_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, g
     return run_fullstats(ctx, fm, c, s, ctx->post);
 }
 
-// the log-domain lattice and its utterance sums (k_logfb_fwd / k_logfb_bwd) on fm's log A and the
-// log b in the workspace
-static int run_log_lattice_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c)
-{
-    int rc;
-    if (c->U) {
-        const lane_grid lg(fm->N, c->U);
-        kscope ks(ctx, GHMM_K_FORWARD);
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_fwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
-                                               c->U, fm->logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk,
-                                               ctx->sink, c->order));
-        if ((rc = launch_ok("k_logfb_fwd"))) return rc;
-        GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_bwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, fm->N,
-                                               c->U, (int)ctx->delta, fm->logA, ctx->b, c->off, ctx->alpha, ctx->logk,
-                                               ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena, ctx->part_denc,
-                                               ctx->sink, c->order));
-        if ((rc = launch_ok("k_logfb_bwd"))) return rc;
-        ctx->beta_valid = true; // ctx->beta holds lbe: ghmm_fetch starts no linear pass on these buffers
-    }
-    ctx->slots = c->U; // one partial per utterance
-    ctx->loglik_pieces = false;
-    return GHMM_OK;
-}
-
 // The same E-step with every quantity formed in the log domain (definition in include/ghmm.h): log b
 // and the posteriors from FC_LOGPOST, the lattice and its utterance sums from k_logfb_fwd / k_logfb_bwd
 // (both counted under GHMM_K_FORWARD), then the linear call's statistics launches as they are.
@@ -525,7 +501,7 @@ extern "C" int ghmm_estep_full_log(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *
     if ((rc = ws_full(ctx, fm->N, fm->M, c)) || (rc = ws_fb(ctx, &fm->rec, c))) return rc;
     if ((rc = ctx->post.grow((size_t)c->F * fm->N * fm->M))) return rc;
     if ((rc = run_emission_full(ctx, fm, c, FC_LOGPOST))) return rc;
-    if ((rc = run_log_lattice_full(ctx, fm, c))) return rc;
+    if ((rc = run_log_lattice(ctx, fm->N, fm->logA, c, true))) return rc;
     return run_fullstats(ctx, fm, c, s, ctx->post);
 }
 
@@ -749,7 +725,7 @@ extern "C" int ghmm_estep_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models
     if (!log_domain && (rc = ctx->lognorm.grow((size_t)c->F))) return rc;
     if ((rc = emission_full_streams(ctx, models, corpora, P, log_domain ? FC_LOGPOST : FC_POST))) return rc;
     // the single-stream calls' recursion launches, on models[0]'s transitions and the product
-    if ((rc = log_domain ? run_log_lattice_full(ctx, fm, c) : run_recursions_full(ctx, fm, c))) return rc;
+    if ((rc = log_domain ? run_log_lattice(ctx, fm->N, fm->logA, c, true) : run_recursions_full(ctx, fm, c))) return rc;
     // calc_mix_param per stream (TFF:289-297) with the common gamma; the transition sums, den_c, log P
     // and the exemplar count go into every stream's vector
     for (int p = 0; p < P && !rc; p++) rc = run_fullstats(ctx, models[p], corpora[p], stats[p], ctx->post_s[p]);

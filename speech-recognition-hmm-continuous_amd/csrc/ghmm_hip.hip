@@ -201,7 +201,7 @@ struct GHMM_LOCAL ghmm_model {
     dev_buf<double> wk, logwk, logA;
     // matrix-core tier (ghmm_mfma.hpp): padded geometry and B fragments
     int Mp = 0, NT = 0, DP = 0, TC = 0, tps = 1;
-    int TCs[3] = {0, 0, 0}; // tiles per chunk of k_emission_sched, per output mode
+    int TCs[4] = {0, 0, 0, 0}; // tiles per chunk of k_emission_sched, per output mode
     size_t em_lds = 0;
     bool mfma_ok = false;
     dev_buf<double> Wm, offs, wkp, logwkp;
@@ -645,7 +645,7 @@ extern "C" int ghmm_model_create(ghmm_ctx *ctx, int N, int M, int D, ghmm_model 
         m->TC = TC;
         // the scheduled kernel: as many whole states per chunk as fit beside its slabs (none in
         // the b-only variant) — every chunk reads the frames again
-        for (int out = 0; out < 3; out++) {
+        for (int out = 0; out < 4; out++) {
             int tcs = ems_tc_cap(Mp, out) / m->tps * m->tps;
             while (tcs > m->tps && ems_lds_bytes(tcs, m->DP, ems_waves(Mp, out), Mp, out) > 159 * 1024) tcs -= m->tps;
             if (tcs < m->tps) tcs = m->tps;
@@ -1157,7 +1157,8 @@ static bool nt_posteriors(const ghmm_ctx *ctx, const ghmm_model *m, const ghmm_c
 }
 
 // b: where the densities go (the workspace's b, or b_stream); post: where the mixture posteriors go
-// (the workspace's own buffer, a stream's post_s[p], or null for none)
+// (the workspace's own buffer, a stream's post_s[p], or null for none).  mode 0: linear densities, 1: the
+// robust tier's, 2: log b (ghmm_viterbi), 3: log b, the same bits, and the posteriors (ghmm_estep_log)
 static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, double *b, double *post)
 {
     // the workspace is rewritten: alpha^ / W / 1/s of an earlier E-step no longer go with its b
@@ -1170,6 +1171,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
     // posteriors written into the workspace's own buffer are the workspace's; streams_emission
     // passes post_s[p], which ghmm_fetch and ghmm_accumulate do not serve
     ctx->post_valid = post && post == ctx->post;
+    ARG_CHECK(mode != 3 || post, "the log-domain emission with posteriors needs their destination");
     if (c->F == 0) return GHMM_OK;
     const long long blocks = (c->F + WAVE - 1) / WAVE;
     const size_t lds = (size_t)WAVE * (m->D | 1) * sizeof(double);
@@ -1180,7 +1182,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
     const bool sched_ok = m->mfma_ok && ctx->kernels != 1 &&
                           (m->Mp <= 16 || m->Mp == 32 || m->Mp == 64) &&
                           m->DP >= 8 && m->DP <= 48;
-    if ((mode == 2 || mode == 0) && sched_ok) {
+    if ((mode == 2 || mode == 0 || mode == 3) && sched_ok) {
         // The scheduled matrix-core kernel: compile-time K steps, KS = DP / 2 for D = 4 .. 47 (DP = D + 1
         // rounded up to a multiple of four, so D always reaches into the last group of four columns,
         // which its direct-operand variant reads unclamped up to there) — and mixture padding.  It needs no fallback launch: a Gaussian that is ill-conditioned even
@@ -1188,14 +1190,14 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
         // frames where its density is not 0.
         int rc;
         const long long ntf = (c->F + 15) / 16;
-        const int po = mode == 2 ? 2 : (post ? 1 : 0);
+        const int po = mode >= 2 ? mode : (post ? 1 : 0);
         const int tcs = m->TCs[po];
         const int chunks = (m->NT + tcs - 1) / tcs;
         const int wv = ems_waves(m->Mp, po);
         const size_t lds_s = ems_lds_bytes(tcs, m->DP, wv, m->Mp, po);
         long long gxs = (ntf + wv - 1) / wv;
         if (gxs > ctx->cus) gxs = ctx->cus;
-        const double *wk = mode == 2 ? m->logwkp : m->wkp; // OUT = 2 adds log wk to the exponents
+        const double *wk = mode >= 2 ? m->logwkp : m->wkp; // OUT = 2 and 3 add log wk to the exponents
         const int ntp = nt_posteriors(ctx, m, c) ? 1 : 0; // non-temporal posterior stores
         kscope ks(ctx, GHMM_K_EMISSION);
 #define GHMM_EMSK(KSV, MP, PO)                                                                    \
@@ -1224,7 +1226,8 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
     } while (0)
 #define GHMM_EMS3(MP)                                                                             \
     do {                                                                                          \
-        if (po == 2) GHMM_EMS(MP, 2);                                                             \
+        if (po == 3) GHMM_EMS(MP, 3);                                                             \
+        else if (po == 2) GHMM_EMS(MP, 2);                                                        \
         else if (po == 1) GHMM_EMS(MP, 1);                                                        \
         else GHMM_EMS(MP, 0);                                                                     \
     } while (0)
@@ -1237,7 +1240,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
         case 32: GHMM_EMS3(32); break;
         default: GHMM_EMS3(64); break;
         }
-        ctx->b_is_log = (mode == 2);
+        ctx->b_is_log = mode >= 2;
         return launch_ok("k_emission_sched");
     }
     if (mode == 0 && m->mfma_ok && ctx->kernels != 1) {
@@ -1275,7 +1278,7 @@ static int run_emission(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int mode, 
                                m->N, m->M, m->D, c->F, c->X, m->mean, m->inv_var, m->wk, m->logwk,
                                b, post, ctx->lognorm, only_if, m->epoch);
     }
-    ctx->b_is_log = (mode == 2);
+    ctx->b_is_log = mode >= 2;
     return launch_ok("k_emission");
 }
 
@@ -1319,13 +1322,13 @@ static int fb_lanes(const ghmm_model *m, int *L)
 
 // models of more than 64 states: is A (zero = 0) or log A (zero = -inf) band-diagonal?  Decided on
 // the device at every pass (the M-step may have changed it), read by the wide kernels behind it.
-static int wide_band_flag(ghmm_ctx *ctx, const ghmm_model *m, const double *A, double zero)
+static int wide_band_flag(ghmm_ctx *ctx, int N, const double *A, double zero)
 {
     int rc;
     if (!ctx->wide_flag && (rc = ctx->wide_flag.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->wide_flag, 0, sizeof(int), ctx->stream));
-    const long long n = (long long)m->N * m->N;
-    hipLaunchKernelGGL(k_wide_band, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->N, A, zero,
+    const long long n = (long long)N * N;
+    hipLaunchKernelGGL(k_wide_band, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, N, A, zero,
                        ctx->wide_flag);
     return launch_ok("k_wide_band");
 }
@@ -1348,7 +1351,7 @@ static int run_forward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool with_b
     ctx->beta_valid = false;
     if (L == 0) { // more than 64 states: one wave per utterance, the reference's order (ghmm_wide.hpp)
         ctx->loglik_pieces = false;
-        if ((rc = wide_band_flag(ctx, m, m->A, 0.0))) return rc;
+        if ((rc = wide_band_flag(ctx, m->N, m->A, 0.0))) return rc;
         kscope ks(ctx, GHMM_K_FORWARD);
         hipLaunchKernelGGL(k_forward_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)4 * m->N * sizeof(double),
                            ctx->stream, m->N, c->U, m->A, ctx->b, c->off, ctx->alpha, ctx->scale, ctx->sinv, ln,
@@ -1403,7 +1406,7 @@ static int run_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool want_
     int L, rc;
     if ((rc = fb_lanes(m, &L))) return rc;
     if (L == 0) {
-        if ((rc = wide_band_flag(ctx, m, m->A, 0.0))) return rc;
+        if ((rc = wide_band_flag(ctx, m->N, m->A, 0.0))) return rc;
         if ((rc = lds_attr(ctx, (const void *)k_backward_wide))) return rc; // (64 KB at 512 states)
         kscope ks(ctx, GHMM_K_BACKWARD);
         hipLaunchKernelGGL(k_backward_wide, dim3((unsigned)c->U), dim3(WAVE),
@@ -2137,7 +2140,7 @@ static int run_viterbi(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, int L, int3
         return GHMM_OK;
     }
     if (L) return run_viterbi_lanes(ctx, m->N, m->logA, c, path_host, score_host);
-    if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
+    if ((rc = wide_band_flag(ctx, m->N, m->logA, -INFINITY))) return rc;
     { // one wave per utterance
         kscope ks(ctx, GHMM_K_VITERBI);
         hipLaunchKernelGGL(k_viterbi_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)2 * m->N * sizeof(double),
@@ -2192,8 +2195,8 @@ static int fold_stream(ghmm_ctx *ctx, size_t n, bool log_domain)
     return launch_ok(log_domain ? "k_add_streams" : "k_mul_streams");
 }
 
-// emission of every stream (mode 0, or 2 for log b); ctx->b ends up holding the product (mode 2: the sum
-// of logs), ctx->post_s[p] stream p's posteriors
+// emission of every stream (mode 0, or 2 / 3 for log b); ctx->b ends up holding the product (modes 2 and 3:
+// the sum of logs), ctx->post_s[p] stream p's posteriors
 static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P,
                             bool want_post, int mode = 0)
 {
@@ -2209,7 +2212,7 @@ static int streams_emission(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpu
     for (int p = 0; p < P && !rc; p++) {
         rc = run_emission(ctx, models[p], corpora[p], mode, p == 0 ? ctx->b : ctx->b_stream,
                           want_post ? ctx->post_s[p] : nullptr);
-        if (!rc && p > 0 && FN) rc = fold_stream(ctx, FN, mode == 2);
+        if (!rc && p > 0 && FN) rc = fold_stream(ctx, FN, mode >= 2);
     }
     // the product belongs to stream 0's (model, corpus) pair as far as the row API is concerned
     ctx->em_m = models[0];
@@ -2475,7 +2478,7 @@ static int logscore_word(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *
     } else if ((rc = streams_emission(ctx, models, corpora, P, false, 2)))
         return rc;
     if (L == 0) {
-        if ((rc = wide_band_flag(ctx, m, m->logA, -INFINITY))) return rc;
+        if ((rc = wide_band_flag(ctx, m->N, m->logA, -INFINITY))) return rc;
         {
             kscope ks(ctx, GHMM_K_FORWARD);
             hipLaunchKernelGGL(k_logforward_wide, dim3((unsigned)c->U), dim3(WAVE), (size_t)4 * m->N * sizeof(double),
@@ -2515,6 +2518,95 @@ extern "C" int ghmm_logscore_streams(ghmm_ctx *ctx, ghmm_model *const *models, g
     if ((rc = fb_lanes(models[0], &L))) return rc;
     if (corpora[0]->U == 0) return GHMM_OK;
     return logscore_word(ctx, models, corpora, P, L, final_state, loglik_host);
+}
+
+// ---- the Baum-Welch E-step in the log domain (ghmm_estep_log, ghmm_estep_log_streams and, through
+// ghmm_fullhost.hpp, ghmm_estep_full_log; definitions in include/ghmm.h)
+
+// The log-domain lattice and its utterance sums on a model's log A (N states, at most WIDE_MAX) and the
+// log b in the workspace: k_logfb_fwd / k_logfb_bwd with one state per lane up to 64 states, beyond that
+// k_logfb_wide_fwd / k_logfb_wide_bwd with one wave per utterance.  Both launches count under
+// GHMM_K_FORWARD: one bracket each, or (one_bracket: ghmm_estep_full_log's record) one around the two.
+static int run_log_lattice(ghmm_ctx *ctx, int N, const double *logA, ghmm_corpus *c, bool one_bracket)
+{
+    int rc;
+    if (c->U) {
+        const bool wide = N > 64;
+        const lane_grid lg(wide ? 64 : N, c->U);
+        if (wide) {
+            if ((rc = wide_band_flag(ctx, N, logA, -INFINITY))) return rc;
+            if ((rc = lds_attr(ctx, (const void *)k_logfb_wide_bwd))) return rc; // (56 KB at 512 states)
+        }
+        auto fwd = [&]() {
+            if (wide)
+                hipLaunchKernelGGL(k_logfb_wide_fwd, dim3((unsigned)c->U), dim3(WAVE), (size_t)4 * N * sizeof(double),
+                                   ctx->stream, N, c->U, logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk,
+                                   c->order, ctx->wide_flag);
+            else
+                GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_fwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, N,
+                                                       c->U, logA, ctx->b, c->off, ctx->alpha, ctx->loglik, ctx->logk,
+                                                       ctx->sink, c->order));
+            return launch_ok(wide ? "k_logfb_wide_fwd" : "k_logfb_fwd");
+        };
+        auto bwd = [&]() {
+            if (wide)
+                hipLaunchKernelGGL(k_logfb_wide_bwd, dim3((unsigned)c->U), dim3(WAVE),
+                                   (size_t)LOGFB_WIDE_BWD_ROWS * N * sizeof(double), ctx->stream, N, c->U,
+                                   (int)ctx->delta, logA, ctx->b, c->off, ctx->alpha, ctx->logk, ctx->beta, ctx->gamma,
+                                   ctx->part_xi, ctx->part_dena, ctx->part_denc, c->order, ctx->wide_flag);
+            else
+                GHMM_BY_LANES(lg.L, hipLaunchKernelGGL(k_logfb_bwd<LL>, dim3(lg.blocks), dim3(WAVE), 0, ctx->stream, N,
+                                                       c->U, (int)ctx->delta, logA, ctx->b, c->off, ctx->alpha,
+                                                       ctx->logk, ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena,
+                                                       ctx->part_denc, ctx->sink, c->order));
+            return launch_ok(wide ? "k_logfb_wide_bwd" : "k_logfb_bwd");
+        };
+        if (one_bracket) {
+            kscope ks(ctx, GHMM_K_FORWARD);
+            if ((rc = fwd()) || (rc = bwd())) return rc;
+        } else {
+            {
+                kscope ks(ctx, GHMM_K_FORWARD);
+                rc = fwd();
+            }
+            if (rc) return rc;
+            kscope ks(ctx, GHMM_K_FORWARD);
+            if ((rc = bwd())) return rc;
+        }
+        ctx->beta_valid = true; // ctx->beta holds lbe: ghmm_fetch starts no linear pass on these buffers
+    }
+    ctx->slots = c->U; // one partial per utterance
+    ctx->loglik_pieces = false;
+    return GHMM_OK;
+}
+
+// ghmm_viterbi's log b with the posteriors beside it (run_emission's mode 3), the lattice above on
+// m's log A, then ghmm_estep's statistics launches as they are
+extern "C" int ghmm_estep_log(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *s)
+{
+    int rc = use(ctx), L;
+    if (rc || (rc = check_pair(m, c)) || (rc = check_stats(m, s)) || (rc = fb_lanes(m, &L))) return rc;
+    if ((rc = ws_frames(ctx, m, c, true)) || (rc = ws_fb(ctx, m, c))) return rc;
+    if ((rc = run_emission(ctx, m, c, 3, ctx->b, ctx->post))) return rc;
+    if ((rc = run_log_lattice(ctx, m->N, m->logA, c, false))) return rc;
+    return run_accumulate(ctx, m, c, s, ctx->post);
+}
+
+extern "C" int ghmm_estep_log_streams(ghmm_ctx *ctx, ghmm_model *const *models, ghmm_corpus *const *corpora, int P,
+                                      ghmm_stats *const *stats)
+{
+    int rc = use(ctx), L;
+    if (rc || (rc = check_streams(ctx, models, corpora, P))) return rc;
+    ARG_CHECK(stats, "null statistics");
+    for (int p = 0; p < P; p++)
+        if ((rc = check_stats(models[p], stats[p]))) return rc;
+    if (P == 1) return ghmm_estep_log(ctx, models[0], corpora[0], stats[0]);
+    if ((rc = fb_lanes(models[0], &L))) return rc;
+    if ((rc = streams_emission(ctx, models, corpora, P, true, 3))) return rc;
+    if ((rc = ws_fb(ctx, models[0], corpora[0]))) return rc;
+    if ((rc = run_log_lattice(ctx, models[0]->N, models[0]->logA, corpora[0], false))) return rc;
+    for (int p = 0; p < P && !rc; p++) rc = run_accumulate(ctx, models[p], corpora[p], stats[p], ctx->post_s[p]);
+    return rc;
 }
 
 // the two vocabulary calls (`what` = the entry point's name in the checks' texts)

@@ -44,7 +44,8 @@ __global__ void k_prepare(int N, int M, const double *__restrict__ A, const doub
 // and come through the scalar cache.  MODE 0: linear densities exactly like the
 // reference (exp underflows where the reference's does).  MODE 1 (robust): densities
 // relative to the frame's largest exponent, lognorm[f] holds that exponent.
-// MODE 2: log b (for the Viterbi lattice), evaluated as m + log(sum exp(e - m)).
+// MODE 2: log b (for the Viterbi lattice), evaluated as m + log(sum exp(e - m)); with `post` (ghmm_estep_log)
+// the posteriors are those very terms over their sum, and log b keeps its bits.
 template <int MODE>
 __global__ void __launch_bounds__(WAVE)
 k_emission(int N, int M, int D, long long F, const double *__restrict__ X,

@@ -587,13 +587,15 @@ constexpr int EMS_WAVES = 16;
 // 8-byte loads per lane from one row pointer — which needs no slab (14 Gaussian tiles per chunk
 // instead of 8) and fits 128 registers, i.e. 16 waves.  States of 32 / 64 mixtures (12 waves either
 // way) gain 2.7 % from the larger chunks in the trainer's variant too.  Bit mask: bit OUT for
-// <= 16 mixtures, bit 3 + OUT for 32 / 64.
+// <= 16 mixtures, bit 3 + OUT for 32 / 64, OUT = 0 .. 2.  OUT = 3 (log b and posteriors) is the log-b
+// variant with stores added: it takes OUT = 2's bits, and with them its waves, chunk and LDS.
 #ifndef GHMM_EMS_DIRECT
 #define GHMM_EMS_DIRECT (1 | (1 << 3) | (1 << 4))
 #endif
+__host__ __device__ constexpr int ems_choice(int OUT) { return OUT == 3 ? 2 : OUT; }
 __host__ __device__ constexpr bool ems_direct(int MP, int OUT)
 {
-    return ((GHMM_EMS_DIRECT >> (OUT + (MP >= 32 ? 3 : 0))) & 1) != 0;
+    return ((GHMM_EMS_DIRECT >> (ems_choice(OUT) + (MP >= 32 ? 3 : 0))) & 1) != 0;
 }
 #ifndef GHMM_EMS_TC
 #define GHMM_EMS_TC 8 // most Gaussian tiles per chunk with the slab (each chunk reads the frames again)
@@ -835,9 +837,39 @@ __host__ __device__ inline size_t ems_lds_bytes(int TC, int DP, int waves, int M
            (size_t)TC * 16 * 8 + (size_t)TC * DP * 8 + EXP_TAB * 8 + (size_t)TC * 16 * 4 + (size_t)TC * 4 * 2 + 64;
 }
 
+// A lane's four posteriors of one tile, as OUT = 1 stores them below: a tile of 16 consecutive real
+// Gaussians from an even index (whole) as two aligned 16-byte stores, non-temporal under ntp; any other
+// slot by slot, guarded by its gmap entry (padding stores nothing).  gm4: the lane's four gmap entries.
+__device__ __forceinline__ void ems_store_post(double *__restrict__ post, long long fr, int G, const int *gm4,
+                                               bool whole, bool fok, int ntp, const double (&pv)[4])
+{
+    if (whole) {
+        if (fok) {
+            double *pp = post + (fr * G + gm4[0]);
+            if (ntp) {
+                // (the empty asm keeps the two arms apart: merged into one, hipcc drops the hint)
+                asm volatile("" ::: "memory");
+                __builtin_nontemporal_store((v2d){pv[0], pv[1]}, (v2d *)pp);
+                __builtin_nontemporal_store((v2d){pv[2], pv[3]}, (v2d *)(pp + 2));
+            } else {
+                *(v2d *)pp = (v2d){pv[0], pv[1]};
+                *(v2d *)(pp + 2) = (v2d){pv[2], pv[3]};
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int gm = gm4[r];
+            if (fok && gm >= 0) post[fr * G + gm] = pv[r];
+        }
+    }
+}
+
 // OUT 0: b (recogniser, RF:860-889); 1: b and posteriors (trainer, TF:1749-1783);
 // 2: log b for the Viterbi lattice, m + log(sum exp(e - m)) like the oracle's definition
-// (wkp then holds log wk).  condt: conditioning of every padded Gaussian around its tile's offset
+// (wkp then holds log wk); 3: OUT = 2's log b, operation for operation, and beside it the posteriors
+// post(i,m) = exp(e_m - mx_i) / sum_m' exp(e_m' - mx_i), the very terms of log b's own sum times the sum's
+// reciprocal (zeros where log b = -inf), stored as OUT = 1 stores its own (ghmm_estep_log).  condt: conditioning of every padded Gaussian around its tile's offset
 // (slots beyond COND_MAX are re-evaluated in direct form where their density is not 0).  tfull[tile]: the tile's 16 slots are 16 consecutive real Gaussians
 // starting at an even index and G is even (its posteriors go out as aligned 16-byte stores).
 template <int KS, int MP, int OUT>
@@ -1157,7 +1189,7 @@ k_emission_sched(int N, int M, int D, int NT, int TC, long long F, const double 
                             }
                     }
                 }
-                if (OUT == 2) {
+                if (OUT >= 2) {
                     // wkl holds log(wk) here: keep the exponents, exponentiate after the max
                     const v4d wk4 = *(const v4d *)(wkl + (ct + tt) * 16 + 4 * kq);
 #pragma unroll
@@ -1183,9 +1215,9 @@ k_emission_sched(int N, int M, int D, int NT, int TC, long long F, const double 
             // first state of this lane and whether the lane stores it (one lane per state)
             const int st0 = ((c0 + ct) * 16 + 4 * kq) >> LOGMP;
             const bool holder = MPL <= 4 || (kq & (MPL / 4 - 1)) == 0;
-            if (OUT == 2) {
+            if (OUT >= 2) {
                 // log b_i = m + log(sum exp(e - m)), m = the state's largest exponent
-                double m[NS], sm[NS], lb[NS];
+                double m[NS], sm[NS], lb[NS], st3[NS];
 #pragma unroll
                 for (int v = 0; v < NS; v++) {
                     double t = e[0][v * GS];
@@ -1205,16 +1237,39 @@ k_emission_sched(int N, int M, int D, int NT, int TC, long long F, const double 
                     exp_emis4(dlt, etab, ex);
 #pragma unroll
                     for (int r = 0; r < 4; r++) sm[r / GS] += ex[r];
+                    if (OUT == 3) {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) e[tt][r] = ex[r]; // (the exponents are done with)
+                    }
                 }
 #pragma unroll
                 for (int v = 0; v < NS; v++) {
                     const double st = kq_sum<MPL>(sm[v]);
                     lb[v] = m[v] < -1.0e299 ? -INFINITY : m[v] + log(st);
+                    if (OUT == 3) {
+                        // 1 / st by two Newton steps, as recip_post: a finite st is at least 1 (its largest term is
+                        // exp(0)) and at most M, so there is no subnormal or overflowing side to take care of
+                        double rr = __builtin_amdgcn_rcp(st);
+                        rr = fma(rr, fma(-st, rr, 1.0), rr);
+                        rr = fma(rr, fma(-st, rr, 1.0), rr);
+                        st3[v] = rr;
+                    }
                 }
                 if (fok && holder) {
 #pragma unroll
                     for (int v = 0; v < NS; v++)
                         if (st0 + v < N) b[fr * N + st0 + v] = lb[v];
+                }
+                if (OUT == 3) {
+                    // the posterior of every slot: its term of the sum times 1 / sum, zeros where log b = -inf
+#pragma unroll
+                    for (int tt = 0; tt < TPS; tt++) {
+                        double pv[4];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) pv[r] = lb[r / GS] == -INFINITY ? 0.0 : e[tt][r] * st3[r / GS];
+                        ems_store_post(post, fr, G, gml + (ct + tt) * 16 + 4 * kq, ((fum >> (ct + tt)) & 1u) != 0, fok,
+                                       ntp, pv);
+                    }
                 }
                 continue;
             }

@@ -11,7 +11,11 @@
  *
  * Differences, on purpose:
  *   - [initial_model] works (the reference reads argv[argc], a NULL, TF:218);
- *   - no MAX_* capacity limits (up to GHMM_MAX_STREAMS = 8 feature streams).
+ *   - no MAX_* capacity limits (up to GHMM_MAX_STREAMS = 8 feature streams);
+ *   - GHMM_LOG_TRAIN=1 in the environment takes ghmm_estep_log_streams for every iteration (finite
+ *     where a frame's linear densities underflow; any number of streams, GHMM_WORLD > 1 included: the
+ *     statistics vector and its all-reduce are the same) and says so in one line of output; the report
+ *     is the same.  Without the variable nothing changes.
  *
  * Built with -DGHMM_FULL_COV it is bin/hmm-continuous-train-full-fs, the full-covariance trainer
  * (TFF = train/source/hmm-full-fs/hmm_continuous_full_fs.c, main TFF:106-378): same argv, usage
@@ -480,13 +484,19 @@ int main(int argc, char **argv)
     }
     double lp[2] = {0.0, 0.0}; /* probab and exemplar_number of the pass (TF:318-320) */
 
+    /* GHMM_LOG_TRAIN=1: every iteration's E-step in the log domain (ghmm_estep_log_streams) */
+    const int log_train = env_int("GHMM_LOG_TRAIN", 0) != 0;
     printf("\r\nCreating HMM using Forward-Backward algorithm (Baum-Welch)");
+    if (log_train) printf("\r\nE-step in the log domain (GHMM_LOG_TRAIN)");
     double probab, old_probab = 1.0, variation; /* TF:151 */
     int iteration = 0;
     do {
         iteration++;
         printf("\r\nStarting training sequence (%d utterances, %zu frames)", n_utt, frames);
-        if ((rc = ghmm_estep_streams(ctx, model, corpus, P, stats))) die("E-step", rc);
+        /* (one stream: ghmm_estep or ghmm_estep_log itself) */
+        if ((rc = log_train ? ghmm_estep_log_streams(ctx, model, corpus, P, stats)
+                            : ghmm_estep_streams(ctx, model, corpus, P, stats)))
+            die("E-step", rc);
         /* the one exchange of the iteration: sum of the accumulators over ranks (one vector per stream) */
         for (int p = 0; comm && p < P; p++)
             if ((rc = ghmm_stats_allreduce(ctx, stats[p], comm))) die("all-reduce", rc);

@@ -110,6 +110,8 @@ SYMBOLS = {
     "ghmm_logscore": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
     "ghmm_logscore_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
     "ghmm_logscore_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp], True),
+    "ghmm_estep_log": (C.c_int, [_vp, _vp, _vp, _vp], True),
+    "ghmm_estep_log_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp)], True),
     "ghmm_logscore_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _dp],
                                     True),
     "ghmm_fmodel_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)], True),
@@ -643,6 +645,11 @@ class Context:
     def estep(self, model, corpus, stats):
         _check(self.lib.ghmm_estep(self.h, model.h, corpus.h, stats.h), self.lib)
 
+    def estep_log(self, model, corpus, stats):
+        """the same E-step in the log domain (ghmm_estep_log): finite where estep's linear densities
+        underflow on a whole frame"""
+        _check(self.lib.ghmm_estep_log(self.h, model.h, corpus.h, stats.h), self.lib)
+
     def mstep(self, model, stats):
         _check(self.lib.ghmm_mstep(self.h, model.h, stats.h), self.lib)
 
@@ -665,6 +672,14 @@ class Context:
         pc = (_vp * P)(*[c.h for c in corpora])
         ps = (_vp * P)(*[s.h for s in stats])
         _check(self.lib.ghmm_estep_streams(self.h, pm, pc, P, ps), self.lib)
+
+    def estep_log_streams(self, models, corpora, stats):
+        """estep_log on several feature streams (ghmm_estep_log_streams)"""
+        P = len(models)
+        pm = (_vp * P)(*[m.h for m in models])
+        pc = (_vp * P)(*[c.h for c in corpora])
+        ps = (_vp * P)(*[s.h for s in stats])
+        _check(self.lib.ghmm_estep_log_streams(self.h, pm, pc, P, ps), self.lib)
 
     def score_streams(self, models, corpora):
         P = len(models)
