@@ -496,6 +496,46 @@ int ghmm_viterbi_streams_batch(ghmm_ctx *ctx, ghmm_model *const *models, int n_m
 int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                            ghmm_corpus *const *corpora, int n_streams, int32_t *word_host,
                            int32_t *path_host, double *score_host);
+/* Connected words: which STRING of words was it, and how does it align (n_streams >= 1).  The reference
+ * has no such decoder.  One max-plus lattice over the states of all words at once, on the vocabulary's
+ * log b[F][NS] (word k = 0 .. K-1 has N_k states in columns bo_k .. bo_k + N_k - 1; log A_k is stream
+ * 0's, -inf where a = 0); p = word_penalty:
+ *   d_0(k,j)  = (j == 0 ? 0 : -inf) + log b_{k,j}(0)        every word may start the utterance; no penalty
+ *   e_{t-1}   = d_{t-1}(w, N_w - 1),  w = w_{t-1} = pick_k d_{t-1}(k, N_k - 1)
+ *   in_t(k,j) = max_i (d_{t-1}(k,i) + log a^k_ij), the candidates in ascending i, a later one wins only
+ *               on a strict >, best starts at -inf with predecessor 0: ghmm_viterbi's step, the same bits
+ *   x_t       = e_{t-1} + p
+ *   d_t(k,0)  = (x_t > in_t(k,0) ? x_t : in_t(k,0)) + log b_{k,0}(t)    the entry wins only on a strict >:
+ *                                                      a tie stays in the word; a NaN x_t never enters
+ *   d_t(k,j)  = in_t(k,j) + log b_{k,j}(t)             j > 0
+ *   score_u   = d_{T-1}(w, N_w - 1),  w = pick_k d_{T-1}(k, N_k - 1)
+ * pick is ghmm_recognise_streams' rule (best = 0; k = 1 .. K-1 in order takes over if s[k] > s[best], or if
+ * s[best] is NaN and s[k] is not), which is the order: a beats b if a's value is greater; or b's is NaN
+ * and a's is not; or neither value beats the other and a's word is lower.
+ * The trace starts in the last state of the final pick, whatever its score, and follows the
+ * back-pointers; where the back-pointer of (t, k, 0) is the entry, frame t begins a word and the trace
+ * continues at (t-1, w_{t-1}, N_w - 1).
+ *   word_host[F]   the word per frame
+ *   path_host[F]   the state within that word
+ *   begin_host[F]  1 on the first frame of every word instance (frame 0 of an utterance included), else
+ *                  0: what tells "five five" from one long "five"
+ *   score_host[U]  the score per utterance; T = 0 scores 0 and writes no frame entries
+ * Consequences: with p = -inf nothing ever enters, and word, path and score are the bits of
+ * ghmm_recognise_streams (its word_host[u] on every frame of u, its score of that word), begin is 1 at
+ * every utterance's first frame only.  A word of one state is both its own entry and its own end.  A
+ * finite positive penalty is allowed.
+ * The vocabulary layout, the gathers, the emission launches and folds, GHMM_BUF_B afterwards and U = 0
+ * (touches nothing) are the batch calls'.  Then ONE launch under GHMM_K_VITERBI holds the lattice and the
+ * trace (one workgroup per utterance, csrc/ghmm_connect.hpp): 2 n_streams - 1 launches under
+ * GHMM_K_EMISSION, one under GHMM_K_VITERBI, one wait for the stream.  A second identical call repeats
+ * every byte.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_recognise_streams refuses
+ * (a word of more than 64 states and GHMM_OPT_ROBUST with n_streams > 1 included; all four destinations
+ * are needed when U > 0); a NaN or +inf penalty gives GHMM_ERR_ARG; more than 2048 states in the
+ * vocabulary (NS; what the kernel keeps in LDS) gives GHMM_ERR_UNSUPPORTED. */
+int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                         ghmm_corpus *const *corpora, int n_streams, double word_penalty,
+                         int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host);
 /* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
  * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
  * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are
@@ -809,6 +849,17 @@ int ghmm_viterbi_full_streams_batch(ghmm_ctx *ctx, ghmm_fmodel *const *models, i
 int ghmm_recognise_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                 ghmm_corpus *const *corpora, int n_streams, int32_t *word_host,
                                 int32_t *path_host, double *score_host);
+/* ghmm_connect_streams (above) for full-covariance words: the same definition, outputs and lattice launch
+ * on ghmm_recognise_full_streams' log b[F][NS] (n_streams launches under GHMM_K_EMISSION, the folds being
+ * the emission's own epilogue, one under GHMM_K_VITERBI, one wait for the stream); with
+ * word_penalty = -inf word, path and score are that call's bits.  Refusals, each before anything is launched, grown or written: whatever
+ * ghmm_recognise_full_streams refuses (GHMM_OPT_ROBUST set included; all four destinations are needed
+ * when U > 0); a NaN or +inf penalty gives GHMM_ERR_ARG; more than 2048 states in the vocabulary gives
+ * GHMM_ERR_UNSUPPORTED. */
+int ghmm_connect_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                              ghmm_corpus *const *corpora, int n_streams, double word_penalty,
+                              int32_t *word_host, int32_t *path_host, int32_t *begin_host,
+                              double *score_host);
 
 /* -------------------------------------- several GPUs: the one collective */
 

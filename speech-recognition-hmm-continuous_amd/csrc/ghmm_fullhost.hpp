@@ -806,3 +806,22 @@ extern "C" int ghmm_recognise_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mo
     if (rc || corpora[0]->U == 0) return rc;
     return vocab_decode(ctx, v, n_models, corpora[0], word_host, path_host, score_host);
 }
+
+extern "C" int ghmm_connect_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                         ghmm_corpus *const *corpora, int P, double word_penalty,
+                                         int32_t *word_host, int32_t *path_host, int32_t *begin_host,
+                                         double *score_host)
+{
+    vocab_pass v;
+    const bool have_dest = word_host && path_host && begin_host && score_host;
+    // the vocabulary checks once ahead of fvocab_begin's own: the decoder's refusals need NS and come
+    // before anything is launched
+    int rc = use(ctx);
+    if (rc) return rc;
+    rc = vocab_checks(models, n_models, corpora, P, have_dest, __func__,
+                      [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); }, &v);
+    if (rc || (rc = connect_check(v, word_penalty, __func__))) return rc;
+    rc = fvocab_begin(ctx, models, n_models, corpora, P, have_dest, FC_LOG, __func__, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    return vocab_connect(ctx, v, n_models, corpora[0], word_penalty, word_host, path_host, begin_host, score_host);
+}

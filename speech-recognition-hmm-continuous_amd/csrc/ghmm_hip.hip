@@ -23,6 +23,7 @@
 #include "ghmm_mfma.hpp"
 #include "ghmm_pair.hpp"
 #include "ghmm_wide.hpp"
+#include "ghmm_connect.hpp"
 #include "ghmm_fullcov.hpp"
 
 extern "C" void ghmm_set_error(const char *fmt, ...); // ghmm_io.c
@@ -154,6 +155,10 @@ struct ghmm_ctx {
     dev_buf<char> bt_tab;
     dev_buf<double> bt_scale, bt_sinv, bt_ll; // the score table bt_ll[words][U] of both kinds
     dev_buf<int> best_word; // ghmm_recognise_streams / _full_streams: every utterance's winning word
+    // ghmm_connect_streams / _full_streams (k_connect): back-pointers [F][NS], and per frame the pick w_t,
+    // which the trace overwrites with the frame's word (the state and the begin mark travel in `path`)
+    dev_buf<unsigned char> cn_psi;
+    dev_buf<int> cn_word;
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     dev_buf<double> b_stream;
@@ -2459,6 +2464,21 @@ extern "C" int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, 
     if (corpora[0]->U == 0) return GHMM_OK;
     if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
     return vocab_decode(ctx, v, n_models, corpora[0], word_host, path_host, score_host);
+}
+
+extern "C" int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                    ghmm_corpus *const *corpora, int P, double word_penalty, int32_t *word_host,
+                                    int32_t *path_host, int32_t *begin_host, double *score_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P,
+                                word_host && path_host && begin_host && score_host, true, __func__, &v)) ||
+        (rc = connect_check(v, word_penalty, __func__)))
+        return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
+    return vocab_connect(ctx, v, n_models, corpora[0], word_penalty, word_host, path_host, begin_host, score_host);
 }
 
 // ---- the forward score in the log domain (ghmm_logscore and its three companions; definitions in

@@ -268,3 +268,58 @@ static int vocab_decode(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const 
     HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
+
+// ------------------------------------------------ connected words
+
+// The connected-word decoder's own refusals, behind the vocabulary checks that filled v and before
+// anything is launched, grown or written: the penalty, and what k_connect holds (a word's states in six
+// bits of its state table, the composite states in LDS).  Called by ghmm_connect_streams and
+// ghmm_connect_full_streams.
+static int connect_check(const vocab_pass &v, double penalty, const char *what)
+{
+    if (penalty != penalty || penalty == INFINITY) {
+        ghmm_set_error("%s: the word penalty is NaN or +inf", what);
+        return GHMM_ERR_ARG;
+    }
+    if (v.Nmax > 64 || v.NS > CONNECT_MAX_NS) {
+        ghmm_set_error("%s: %d states in all, the largest word %d: the connected-word lattice takes %d and 64",
+                       what, v.NS, v.Nmax, CONNECT_MAX_NS);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return GHMM_OK;
+}
+
+// The connected-word decoder behind its emission launches (U > 0, connect_check passed): k_connect, one
+// workgroup per utterance, lattice and trace in ONE launch on the log b[F][NS] in the workspace; then the
+// scores (bt_ll[U]), the word per frame and, in one byte per frame, the state (bits 0..5) with the begin
+// mark (bit 7), which the host takes apart.  One stream wait.
+static int vocab_connect(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const ghmm_corpus *c, double penalty,
+                         int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host)
+{
+    int rc;
+    if ((rc = ctx->cn_psi.grow((size_t)c->F * v.NS + 16)) || (rc = ctx->cn_word.grow((size_t)c->F)) ||
+        (rc = ctx->path.grow((size_t)c->F)) || (rc = ctx->bt_ll.grow((size_t)c->U)))
+        return rc;
+    const size_t lds = connect_lds(v.NS);
+    if (lds > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_connect))) return rc;
+    const int threads = std::min(CONNECT_THREADS, ((v.NS + WAVE - 1) / WAVE) * WAVE);
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_connect, dim3((unsigned)c->U), dim3((unsigned)threads), lds, ctx->stream, c->U, n_models,
+                           v.NS, v.dtab, (const double *)ctx->b, c->off, penalty, ctx->cn_psi, ctx->cn_word,
+                           ctx->path, ctx->bt_ll, c->order);
+    }
+    if ((rc = launch_ok("k_connect"))) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F) {
+        HIP_TRY(hipMemcpyAsync(word_host, ctx->cn_word, (size_t)c->F * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+        for (long long f = 0; f < c->F; f++) {
+            begin_host[f] = path_host[f] >> 7;
+            path_host[f] &= 63;
+        }
+    } else
+        HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}

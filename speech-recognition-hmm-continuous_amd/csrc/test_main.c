@@ -30,6 +30,12 @@
  * ghmm_logscore_full_streams and final_state = 0, the diagonal one with ghmm_logscore_streams_batch /
  * ghmm_logscore_streams and final_state = 1 (its final-state term kept); the same quantities, finite
  * where the linear densities underflow.  Without the variable nothing changes.
+ * With GHMM_CONNECTED=1 (and optionally GHMM_WORD_PENALTY=<double>, default 0) either program decodes
+ * every utterance as a STRING of the vocabulary's words instead (ghmm_connect_streams /
+ * ghmm_connect_full_streams): exactly one model set; the output file's first line says so, then one line
+ * per utterance, also on stdout: the feature file's name (stream 1's), the words' names in order, the
+ * score.  The word file is read for the utterance count as always; what it says was spoken is not used.
+ * Without the variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -103,6 +109,74 @@ static void rank_scores(const double *probab, int *index, int n)
 
 static FILE *f_out;
 
+/* GHMM_CONNECTED=1: the one model set's vocabulary (hm[k * GHMM_MAX_STREAMS + p]) on its P streams, every
+ * utterance decoded as a word string; one line per utterance to stdout and the output file */
+#ifdef GHMM_FULL_COV
+typedef ghmm_host_fmodel host_model_t;
+typedef ghmm_fmodel dev_model_t;
+#else
+typedef ghmm_host_model host_model_t;
+typedef ghmm_model dev_model_t;
+#endif
+static void run_connected(const host_model_t *hm, int word_number, int P, double *const *X, const int32_t *len,
+                          int n_utt, const int *D, double penalty, char *const *utt_name)
+{
+    int rc;
+    size_t F = 0;
+    for (int u = 0; u < n_utt; u++) F += (size_t)len[u];
+    ghmm_ctx *ctx;
+    if ((rc = ghmm_ctx_create(0, NULL, &ctx))) die("GPU context", rc);
+    ghmm_corpus *corpus[GHMM_MAX_STREAMS];
+    for (int p = 0; p < P; p++)
+        if ((rc = ghmm_corpus_create(ctx, X[p], len, n_utt, D[p], &corpus[p]))) die("corpus", rc);
+    dev_model_t **flat = (dev_model_t **)calloc((size_t)word_number * P, sizeof(dev_model_t *));
+    int32_t *wd = (int32_t *)malloc((F ? F : 1) * 3 * sizeof(int32_t)), *st = wd + (F ? F : 1), *bg = st + (F ? F : 1);
+    double *sc = (double *)malloc((size_t)n_utt * sizeof(double));
+    if (!flat || !wd || !sc) die("memory", GHMM_ERR_ALLOC);
+    for (int k = 0; k < word_number; k++)
+        for (int p = 0; p < P; p++) {
+            const host_model_t *m = &hm[(size_t)k * GHMM_MAX_STREAMS + p];
+            if (m->D != D[p]) {
+                printf("model %s has %d coefficients, data has %d \n", m->word, m->D, D[p]);
+                exit(1);
+            }
+            dev_model_t **slot = &flat[(size_t)k * P + p];
+#ifdef GHMM_FULL_COV
+            if ((rc = ghmm_fmodel_create(ctx, m->N, m->M, m->D, slot))) die("model", rc);
+            if ((rc = ghmm_fmodel_set(ctx, *slot, m->A, m->c, m->mean, m->inv_cov, m->det))) die("model", rc);
+#else
+            if ((rc = ghmm_model_create(ctx, m->N, m->M, m->D, slot))) die("model", rc);
+            if ((rc = ghmm_model_set(ctx, *slot, m->A, m->c, m->mean, m->inv_var, m->det))) die("model", rc);
+#endif
+        }
+#ifdef GHMM_FULL_COV
+    rc = ghmm_connect_full_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
+#else
+    rc = ghmm_connect_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
+#endif
+    if (rc) die("decoding", rc);
+    size_t f = 0;
+    for (int u = 0; u < n_utt; u++) {
+        FILE *to[2] = {stdout, f_out};
+        for (int o = 0; o < 2; o++) {
+            fprintf(to[o], "%s :", utt_name[u]);
+            for (int t = 0; t < len[u]; t++)
+                if (bg[f + t]) fprintf(to[o], " %s", hm[(size_t)wd[f + t] * GHMM_MAX_STREAMS].word);
+            fprintf(to[o], " : %f\n", sc[u]);
+        }
+        f += (size_t)len[u];
+    }
+    for (int k = 0; k < word_number * P; k++)
+#ifdef GHMM_FULL_COV
+        ghmm_fmodel_destroy(ctx, flat[k]);
+#else
+        ghmm_model_destroy(ctx, flat[k]);
+#endif
+    for (int p = 0; p < P; p++) ghmm_corpus_destroy(ctx, corpus[p]);
+    ghmm_ctx_destroy(ctx);
+    free(flat); free(wd); free(sc);
+}
+
 /* writing_result_word, RF:1111-1150 */
 static void report_word(int correct, int error, int second, int word_number, const char *spoken,
                         const int *wrong_word, char **word, double cpu_time, int word_frames)
@@ -142,6 +216,14 @@ int main(int argc, char **argv)
     int rc;
     const char *env_log = getenv("GHMM_LOG_SCORE");
     const int log_score = env_log && strcmp(env_log, "1") == 0;
+    const char *env_con = getenv("GHMM_CONNECTED"), *env_pen = getenv("GHMM_WORD_PENALTY");
+    const int connected = env_con && strcmp(env_con, "1") == 0;
+    const double word_penalty = (connected && env_pen) ? atof(env_pen) : 0.0;
+    if (connected && K != 1) {
+        printf("GHMM_CONNECTED=1 takes exactly one model set (given: %d) \n", K);
+        exit(1);
+    }
+    char **utt_name = NULL; /* connected decoding: every utterance's feature file (stream 1's) */
 
     /* models: one list per set, the same vocabulary in every set */
 #ifdef GHMM_FULL_COV
@@ -239,6 +321,7 @@ int main(int argc, char **argv)
             cap_u = cap_u ? 2 * cap_u : 64;
             spoken = realloc(spoken, (size_t)cap_u * sizeof *spoken);
             for (int j = 0; j < K; j++) len[j] = (int32_t *)realloc(len[j], (size_t)cap_u * sizeof(int32_t));
+            if (connected) utt_name = (char **)realloc(utt_name, (size_t)cap_u * sizeof(char *));
         }
         snprintf(spoken[n_utt], sizeof spoken[n_utt], "%s", w);
         for (int j = 0; j < K; j++)
@@ -256,6 +339,7 @@ int main(int argc, char **argv)
                     exit(1);
                 }
                 if (p == 0) len[j][n_utt] = T;
+                if (connected && p == 0 && !(utt_name[n_utt] = strdup(path))) die("memory", GHMM_ERR_ALLOC);
                 if (T != len[j][n_utt]) {
                     printf("file %s has %d frames, parameter 1 of the same utterance has %d \n", path, T, len[j][n_utt]);
                     exit(1);
@@ -279,6 +363,20 @@ int main(int argc, char **argv)
     if (!f_out) {
         printf("can't open file %s \n", output_file);
         exit(1);
+    }
+    if (connected) {
+#ifdef GHMM_FULL_COV
+        fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name);
+#else
+        fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name);
+#endif
+        if (ferror(f_out) || fclose(f_out) != 0) {
+            printf("writing error on file %s \n", output_file);
+            exit(1);
+        }
+        return 0;
     }
 #ifdef GHMM_FULL_COV
     /* writing_header, RC:1019-1033 (coef_model is a double there) */

@@ -107,6 +107,10 @@ SYMBOLS = {
     "ghmm_viterbi_streams_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp], True),
     "ghmm_recognise_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _dp],
                                True),
+    "ghmm_connect_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_double, _ip, _ip,
+                                       _ip, _dp], True),
+    "ghmm_connect_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_double, _ip,
+                                            _ip, _ip, _dp], True),
     "ghmm_logscore": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
     "ghmm_logscore_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
     "ghmm_logscore_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp], True),
@@ -517,6 +521,22 @@ def rendezvous_file(path, rank, world, timeout_s=120.0, id_bytes=None):
     return buf.raw
 
 
+def word_segments(word, begin, lens):
+    """What connect_streams decoded, per utterance the list of (word, first_frame, last_frame) with the
+    frames counted inside the utterance: a word instance runs from a frame with begin == 1 to the frame
+    before the next one.  An empty utterance gives an empty list."""
+    out, f0 = [], 0
+    for T in lens:
+        T = int(T)
+        starts = [t for t in range(T) if begin[f0 + t]]
+        if T and (not starts or starts[0] != 0):
+            raise ValueError("an utterance's first frame must begin a word")
+        ends = [t - 1 for t in starts[1:]] + [T - 1]
+        out.append([(int(word[f0 + a]), a, b) for a, b in zip(starts, ends)])
+        f0 += T
+    return out
+
+
 def stats_len(N, M, D):
     return N * N + 2 * N + N * M * (2 * D + 1) + 2
 
@@ -723,6 +743,25 @@ class Context:
                                                word.ctypes.data_as(_ip), path.ctypes.data_as(_ip), _d(score)),
                self.lib)
         return word, path, score
+
+    def _connect(self, fn, vocab, corpora, penalty):
+        F = corpora[0].frames
+        word, path, begin = (np.empty(F, dtype=np.int32) for _ in range(3))
+        score = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(fn(self.h, self._vocab_handles(vocab), len(vocab), self._stream_handles(corpora), len(corpora),
+                  float(penalty), word.ctypes.data_as(_ip), path.ctypes.data_as(_ip), begin.ctypes.data_as(_ip),
+                  _d(score)), self.lib)
+        return word, path, begin, score
+
+    def connect_streams(self, vocab, corpora, penalty=0.0):
+        """(word[F], path[F], begin[F], score[U]): every utterance decoded as a string of the vocabulary's
+        words by one Viterbi lattice over all of them; `penalty` is added at every word entry after the
+        first.  begin is 1 on the first frame of every word instance (word_segments takes it apart)"""
+        return self._connect(self.lib.ghmm_connect_streams, vocab, corpora, penalty)
+
+    def connect_full_streams(self, vocab, corpora, penalty=0.0):
+        """connect_streams for full-covariance words"""
+        return self._connect(self.lib.ghmm_connect_full_streams, vocab, corpora, penalty)
 
     # ---- the forward score of diagonal models in the log domain
     def logscore(self, model, corpus, final_state=False):

@@ -1,0 +1,237 @@
+"""The cases of the connected-word decoder (ghmm_connect_streams, ghmm_connect_full_streams; k_connect) and a
+float64 numpy restatement of its definition in include/ghmm.h.  Shared by test_connect_host.py, which
+checks on the CPU that the restatement is the definition (against an enumeration of all composite paths)
+and that the cases keep the margin under which a differing path cannot be blamed on rounding, and by
+test_connect_gpu.py.  Plain numpy and the oracle, no GPU, no tests.
+
+An utterance is the concatenation of fullstreams_ref.stream_frames walks through a stated word sequence,
+one walk of a stated length per word.  The smallest shapes at which the kernel can go wrong:
+  narrow  vocab_cases' narrow words: K = 3, N = (5, 16, 9), P = 3, word 1 ergodic.  NS = 30: one wave.
+          Spoken (0), (1, 2), (2, 0, 1), (0, 0); lengths 0, 1, 2, 7, 8, 9, 17, 40, 40.
+  mixed   vocab_cases' mixed words: K = 4, N = (3, 16, 17, 6), P = 2, word 1 ergodic, Nmax = 17.
+  wide    vocab_cases' wide words: N = (33, 64), NS = 97: two waves, a word that straddles them, the
+          dense step on word 0's columns.  One utterance of 5 frames, shorter than either word: no word
+          end is reached, every pick is over -inf alone.
+  many    K = 70 words of 3 states, P = 1, (M, D) = (1, 2).  NS = 210: four waves, the pick spans all.
+  ones    three one-state words with A = [[1]]: a word is both its own entry and its own end.
+  dup     mixed with word 3 a copy of word 0: every pick and every entry between the two takes word 0
+          (GHMM_OPT_KERNELS = 1 only, where equal Gaussians give equal bits).
+  full    fullvocab_cases' narrow words (its smallest vocabulary: NS = 30), two composed utterances and
+          one single word.
+Penalties: 0 and -5 on every case, -inf on every case, +3 and -1e4 on narrow."""
+import numpy as np
+
+import fullvocab_cases as FV
+import vocab_cases as V
+from fullcov_support import offsets
+from fullstreams_ref import stream_frames
+
+ENTRY = -1          # psi of a first state entered from the previous frame's pick
+GAP = V.GAP
+
+#        name: (where the words come from, [(spoken words, frames per word)], seed)
+UTTS = {
+    "narrow": [((0,), (0,)), ((0,), (1,)), ((0,), (2,)), ((0,), (7,)), ((0,), (8,)), ((2,), (9,)),
+               ((0, 0), (8, 9)), ((1, 2), (22, 18)), ((2, 0, 1), (12, 8, 20))],
+    "mixed": [((0, 3), (6, 10)), ((2, 1), (20, 20)), ((3,), (5,)), ((1, 0, 3), (18, 5, 9)), ((0,), (0,))],
+    "wide": [((1, 0), (70, 40)), ((0,), (5,)), ((0, 1), (36, 66)), ((0,), (0,))],
+    "many": [((5, 69, 33), (4, 5, 4)), ((64,), (6,)), ((0, 65), (3, 3)), ((17,), (1,))],
+    "ones": [((0, 1, 2, 1), (3, 3, 3, 3)), ((2,), (1,)), ((0,), (0,))],
+    "full": [((0, 2), (8, 12)), ((2, 0), (14, 9)), ((1,), (20,))],
+}
+UTTS["dup"] = UTTS["mixed"]
+SEEDS = {"narrow": 611, "mixed": 612, "wide": 613, "many": 614, "ones": 615, "dup": 612, "full": 616}
+DIAGONAL = ("narrow", "mixed", "wide", "many", "ones", "dup")
+NONTIE = ("narrow", "mixed", "wide", "many", "full")      # compared with the restatement on both tiers
+ALL = DIAGONAL + ("full",)
+
+
+def penalties(name):
+    return (0.0, -5.0, -np.inf) + ((3.0, -1e4) if name == "narrow" else ())
+
+
+def _words(G, name, rng):
+    if name in ("narrow", "mixed", "wide"):
+        return V.make(G, name).words
+    if name == "dup":
+        words = V.make(G, "mixed").words
+        words[3] = [h.copy() for h in words[0]]
+        return words
+    if name == "full":
+        return FV.make(G, "narrow").words
+    if name == "many":
+        from fullcov_support import banded
+        return [[V.rand_model(G, rng, 3, 1, 2, banded(rng, 3), word=f"w{k}")] for k in range(70)]
+    return [[V.rand_model(G, rng, 1, 2, 3, np.ones((1, 1)), word=f"w{k}")] for k in range(3)]       # ones
+
+
+def make(G, name):
+    """vocab_cases.Case (full: fullvocab_cases.Case) with .spoken[u] = the word sequence of utterance u
+    (empty for T = 0) and .name"""
+    rng = np.random.default_rng(SEEDS[name])
+    words = _words(G, name, rng)
+    P = len(words[0])
+    parts, lens, spoken = [[] for _ in range(P)], [], []
+    for seq, seg in UTTS[name]:
+        for k, T in zip(seq, seg):
+            x = stream_frames(rng, words[k], [int(T)])
+            for p in range(P):
+                parts[p].append(x[p])
+        lens.append(int(sum(seg)))
+        spoken.append(tuple(seq) if sum(seg) else ())
+    Xs = [np.concatenate(x) for x in parts]
+    case = (FV.Case if name == "full" else V.Case)(words, Xs, lens)
+    case.spoken, case.name = spoken, name
+    return case
+
+
+# ------------------------------------------------------------- the definition in float64
+
+def log_a(A):
+    with np.errstate(divide="ignore"):
+        return np.where(A > 0, np.log(np.where(A > 0, A, 1.0)), -np.inf)
+
+
+def beats(av, ak, bv, bk):
+    """the order of include/ghmm.h: a beats b"""
+    if av > bv or (np.isnan(bv) and not np.isnan(av)):
+        return True
+    if bv > av or (np.isnan(av) and not np.isnan(bv)):
+        return False
+    return ak < bk
+
+
+def pick(s):
+    """(winner, gap) of a score list under k_vocab_best's rule; gap = winner - best of the others where
+    both are finite, else inf"""
+    best = 0
+    for k in range(1, len(s)):
+        if s[k] > s[best] or (np.isnan(s[best]) and not np.isnan(s[k])):
+            best = k
+    rest = [v for k, v in enumerate(s) if k != best and np.isfinite(v)]
+    gap = s[best] - max(rest) if rest and np.isfinite(s[best]) else np.inf
+    return best, gap
+
+
+def _margin(win, other):
+    return win - other if np.isfinite(win) and np.isfinite(other) else np.inf
+
+
+def decode_log(logAs, logb, p):
+    """One utterance: the recursion and the trace of include/ghmm.h on logb[T][NS] (word k's columns in
+    order) and the words' log A, penalty p.  Returns (word[T], path[T], begin[T], score, gap): gap = the
+    smallest difference, along the traced path, between the winning candidate and the runner-up at every
+    decision (the predecessor within the word, entry against stay, every pick the trace uses, the final
+    pick); inf where there is no finite runner-up."""
+    Ns = [a.shape[0] for a in logAs]
+    bo = np.concatenate([[0], np.cumsum(Ns)]).astype(int)
+    K, T = len(Ns), len(logb)
+    if T == 0:
+        z = np.zeros(0, dtype=np.int32)
+        return z, z.copy(), z.copy(), 0.0, np.inf
+    with np.errstate(all="ignore"):
+        d = [np.where(np.arange(N) == 0, 0.0, -np.inf) + logb[0, bo[k]:bo[k] + N] for k, N in enumerate(Ns)]
+        psi = [[np.zeros(N, dtype=int) for N in Ns]]
+        gin = [[np.full(N, np.inf) for N in Ns]]        # the predecessor within the word
+        gent = [np.full(K, np.inf)]                     # entry against stay
+        w, gpick = np.zeros(T, dtype=int), np.full(T, np.inf)
+        for t in range(1, T):
+            w[t - 1], gpick[t - 1] = pick([d[k][-1] for k in range(K)])
+            x = d[w[t - 1]][-1] + p
+            nd, npsi, ngin, ngent = [], [], [], np.full(K, np.inf)
+            for k, N in enumerate(Ns):
+                cand = d[k][:, None] + logAs[k]                      # [i][j]
+                cand = np.where(np.isnan(cand), -np.inf, cand)       # a NaN never wins a strict >
+                arg = np.argmax(cand, axis=0)                        # the first maximum; 0 where all are -inf
+                top = np.sort(cand, axis=0)[::-1]
+                best = top[0].copy()
+                g = np.full(N, np.inf)
+                if N > 1:
+                    g = np.where(np.isfinite(top[0]) & np.isfinite(top[1]), top[0] - top[1], np.inf)
+                if x > best[0]:
+                    ngent[k] = _margin(x, best[0])
+                    best[0], arg[0] = x, ENTRY
+                else:
+                    ngent[k] = _margin(best[0], x)
+                nd.append(best + logb[t, bo[k]:bo[k] + N])
+                npsi.append(arg)
+                ngin.append(g)
+            d = nd
+            psi.append(npsi)
+            gin.append(ngin)
+            gent.append(ngent)
+        w[T - 1], gpick[T - 1] = pick([d[k][-1] for k in range(K)])
+    k = int(w[T - 1])
+    score, gap = d[k][-1], gpick[T - 1]
+    s = Ns[k] - 1
+    word, path, begin = (np.zeros(T, dtype=np.int32) for _ in range(3))
+    for t in range(T - 1, -1, -1):
+        word[t], path[t] = k, s
+        if t == 0:
+            begin[t] = 1
+            break
+        bp = psi[t][k][s]
+        if s == 0:
+            gap = min(gap, gent[t][k])
+        if bp == ENTRY:
+            begin[t] = 1
+            gap = min(gap, gpick[t - 1])
+            k = int(w[t - 1])
+            s = Ns[k] - 1
+        else:
+            gap = min(gap, gin[t][k][s])
+            s = int(bp)
+    return word, path, begin, float(score), float(gap)
+
+
+def decode(case, logb, p):
+    """decode_log over a case's utterances on logb[F][NS]: (word[F], path[F], begin[F], score[U], gap[U])"""
+    logAs = [log_a(np.asarray(w[0].A, dtype=np.float64)) for w in case.words]
+    off = offsets(case.lens)
+    outs = [decode_log(logAs, logb[off[u]:off[u + 1]], p) for u in range(case.U)]
+    cat = [np.concatenate([o[i] for o in outs]).astype(np.int32) for i in range(3)]
+    return cat[0], cat[1], cat[2], np.array([o[3] for o in outs]), np.array([o[4] for o in outs])
+
+
+def oracle_log_b(case):
+    """log b[F][NS] in float64: the oracle's (full: fullstreams_ref's) summed log emission, word by word"""
+    if case.name == "full":
+        import fullstreams_ref as S
+        cols = [np.asarray(S.log_emission(hms, case.Xs, np.float64)[0], dtype=np.float64) for hms in case.words]
+    else:
+        cols = [V.log_b(hms, case.Xs) for hms in case.words]
+    return np.concatenate(cols, axis=1) if case.F else np.zeros((0, case.NS))
+
+
+def strings(word, begin, lens):
+    """per utterance the decoded word sequence"""
+    off = offsets(lens)
+    return [tuple(int(word[f]) for f in range(off[u], off[u + 1]) if begin[f]) for u in range(len(lens))]
+
+
+# The utterances that the restatement decodes to their spoken sequence on the oracle's log b, per case the
+# utterances at p = 0 and at p = -5: what qualifying() gives, asserted to be exactly this by
+# test_connect_host.py, and asserted of the device by test_connect_gpu.py.  (An utterance too short for
+# any word end to be reached is word 0 throughout: narrow's utterance 1 and wide's utterance 1 qualify so.)
+QUALIFY = {
+    "narrow": {0.0: [1, 3, 4, 5, 6, 7, 8], -5.0: [1, 3, 4, 5, 6, 7, 8]},
+    "mixed": {0.0: [0, 1, 3], -5.0: [0, 1, 3]},
+    "wide": {0.0: [0, 1, 2], -5.0: [0, 1, 2]},
+    "many": {0.0: [2], -5.0: []},
+    "full": {0.0: [0, 1, 2], -5.0: [0, 1, 2]},
+}
+
+
+def qualifying(case):
+    """[(penalty, utterance)] over p = 0, -5 and the utterances of at least one frame"""
+    lb = oracle_log_b(case)
+    out = []
+    for p in (0.0, -5.0):
+        word, _, begin, _, _ = decode(case, lb, p)
+        got = strings(word, begin, case.lens)
+        out += [(p, u) for u in range(case.U) if case.lens[u] and got[u] == case.spoken[u]]
+    return out
+
+
+__all__ = ["ALL", "DIAGONAL", "NONTIE", "GAP", "ENTRY", "UTTS", "penalties", "make", "log_a", "beats", "pick",
+           "decode_log", "decode", "oracle_log_b", "strings", "QUALIFY", "qualifying"]
