@@ -536,6 +536,50 @@ int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_model
 int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                          ghmm_corpus *const *corpora, int n_streams, double word_penalty,
                          int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host);
+/* Forced alignment: WHERE does each word of a known transcript lie (n_streams >= 1).  The reference has no
+ * such call.  seq_off[U + 1], seq[seq_off[U]]: utterance u's transcript is the words
+ * seq[seq_off[u] .. seq_off[u+1]): L_u instances, instance i = word k_i with N_i states.  The vocabulary
+ * layout, the gathers, the emission launches and folds, and GHMM_BUF_B afterwards are
+ * ghmm_connect_streams': the WHOLE vocabulary's log b[F][NS] is computed, not only the transcript's words
+ * (gathering only the words a batch uses is not done).  The composite states of u are s = 0 .. S_u - 1,
+ * S_u = sum_i N_i, instance i owning a contiguous run of them; state (i, j) reads column bo_{k_i} + j of
+ * log b; log A is word k_i's, stream 0's, -inf where a = 0:
+ *   d_0(i,j)  = (i == 0 && j == 0 ? 0 : -inf) + log b_{k_i,j}(0)
+ *   in_t(i,j) = max_{i'} (d_{t-1}(i,i') + log a_{i'j}), the candidates in ascending i', a later one wins only
+ *               on a strict >, best starts at -inf with predecessor 0: ghmm_viterbi's step, the same bits
+ *   x_t(i)    = d_{t-1}(i-1, N_{i-1} - 1)          i > 0; no penalty term: the value itself
+ *   d_t(i,0)  = (i > 0 && x_t(i) > in_t(i,0) ? x_t(i) : in_t(i,0)) + log b(t)    the entry wins only on a
+ *                                                  strict >: a tie stays in the word; a NaN never enters
+ *   d_t(i,j)  = in_t(i,j) + log b(t)               j > 0
+ *   score_u   = d_{T-1}(L_u - 1, N_{L_u-1} - 1)
+ * The trace starts in the last state of the last instance, whatever its score, and follows the
+ * back-pointers as ghmm_connect_streams' does; an entry back-pointer at (t, i, 0) continues at
+ * (t-1, i-1, N_{i-1} - 1).  The outputs have ghmm_connect_streams' shape:
+ *   word_host[F]   the word of the instance per frame
+ *   path_host[F]   the state within the word
+ *   begin_host[F]  1 on the first frame of every instance (frame 0 of an utterance included), else 0
+ *   score_host[U]  the score per utterance
+ * T = 0 scores 0 and writes no frame entries, whatever its transcript (an empty one is allowed there, and
+ * the cap below is not applied to it).  A score of -inf says that the utterance is too short for its
+ * transcript (fewer frames than the shortest path through its instances) or that no path exists; the
+ * frame entries are then what the trace gives on back-pointers of -inf candidates and carry no meaning.
+ * Consequences:
+ *   (a) a one-word transcript (k) gives score == ghmm_viterbi_streams_batch's [k][u] bit for bit under
+ *       either GHMM_OPT_KERNELS; where ghmm_recognise_streams picks word k, its path;
+ *   (b) with the strings that ghmm_connect_streams decodes at penalty 0 as transcripts, score == that
+ *       call's score (== as values); where the optimum is unique, word, path and begin are its;
+ *   (c) for any transcript, score <= ghmm_connect_streams' penalty-0 score.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_recognise_streams refuses
+ * (all four destinations and both transcript arrays are needed when U > 0); GHMM_ERR_ARG for
+ * seq_off[0] != 0, a decreasing seq_off, a word outside 0 .. n_models-1, an empty transcript on an
+ * utterance with T > 0; GHMM_ERR_UNSUPPORTED for an utterance of T > 0 whose S_u exceeds 2048 (what the
+ * kernel keeps in LDS) or a word of more than 64 states.  U = 0 touches nothing.
+ * 2 n_streams - 1 launches under GHMM_K_EMISSION, ONE under GHMM_K_VITERBI (lattice and trace, one
+ * workgroup per utterance, csrc/ghmm_align.hpp), one wait for the stream.  A second identical call repeats
+ * every byte. */
+int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                       ghmm_corpus *const *corpora, int n_streams, const int32_t *seq, const int32_t *seq_off,
+                       int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host);
 /* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
  * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
  * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are
@@ -860,6 +904,14 @@ int ghmm_connect_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_m
                               ghmm_corpus *const *corpora, int n_streams, double word_penalty,
                               int32_t *word_host, int32_t *path_host, int32_t *begin_host,
                               double *score_host);
+/* ghmm_align_streams (above) for full-covariance words: the same definition, outputs, refusals and lattice
+ * launch on ghmm_recognise_full_streams' log b[F][NS] (n_streams launches under GHMM_K_EMISSION, one under
+ * GHMM_K_VITERBI, one wait for the stream); consequences (a) to (c) hold against
+ * ghmm_viterbi_full_streams_batch, ghmm_recognise_full_streams and ghmm_connect_full_streams. */
+int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                            ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
+                            const int32_t *seq_off, int32_t *word_host, int32_t *path_host,
+                            int32_t *begin_host, double *score_host);
 
 /* -------------------------------------- several GPUs: the one collective */
 

@@ -24,6 +24,7 @@
 #include "ghmm_pair.hpp"
 #include "ghmm_wide.hpp"
 #include "ghmm_connect.hpp"
+#include "ghmm_align.hpp"
 #include "ghmm_fullcov.hpp"
 
 extern "C" void ghmm_set_error(const char *fmt, ...); // ghmm_io.c
@@ -159,6 +160,9 @@ struct ghmm_ctx {
     // which the trace overwrites with the frame's word (the state and the begin mark travel in `path`)
     dev_buf<unsigned char> cn_psi;
     dev_buf<int> cn_word;
+    // ghmm_align_streams / _full_streams (k_align): the call's tables, poff[U] | seq_off[U + 1] | seq, uploaded
+    // ahead of its launch (vocab_align); its back-pointers and words per frame go through cn_psi and cn_word
+    dev_buf<char> al_tab;
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     dev_buf<double> b_stream;
@@ -2479,6 +2483,24 @@ extern "C" int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, in
     if (corpora[0]->U == 0) return GHMM_OK;
     if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
     return vocab_connect(ctx, v, n_models, corpora[0], word_penalty, word_host, path_host, begin_host, score_host);
+}
+
+extern "C" int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                  ghmm_corpus *const *corpora, int P, const int32_t *seq, const int32_t *seq_off,
+                                  int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host)
+{
+    dvocab v;
+    align_plan pl;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P,
+                                word_host && path_host && begin_host && score_host && seq && seq_off, true, __func__,
+                                &v)))
+        return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = align_check(models, n_models, P, corpora[0], v, seq, seq_off, __func__, &pl)) ||
+        (rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v)))
+        return rc;
+    return vocab_align(ctx, v, corpora[0], pl, seq, seq_off, word_host, path_host, begin_host, score_host);
 }
 
 // ---- the forward score in the log domain (ghmm_logscore and its three companions; definitions in

@@ -323,3 +323,113 @@ static int vocab_connect(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const
         HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
+
+// ------------------------------------------------ forced alignment
+
+// What align_check works out of a call's transcripts for vocab_align: the utterances' back-pointer
+// offsets (rows of S_u bytes: poff[u] = the sum of T * S over the utterances before u), their total, and
+// the largest S_u among the utterances of at least one frame (the launch's LDS and waves).
+struct align_plan {
+    std::vector<long long> poff;
+    long long psi_bytes = 0;
+    int Smax = 0;
+};
+
+// The forced alignment's own refusals, behind the vocabulary checks that filled v and before anything is
+// launched, grown or written (U > 0, both transcript arrays present): the transcripts' shape and words,
+// and what k_align holds (a word's states in six bits of its state table, an utterance's composite
+// states in LDS).  An utterance of no frames may have any transcript of known words, an empty one
+// included: no lattice is built for it.  Called by ghmm_align_streams and ghmm_align_full_streams.
+template <class Model>
+static int align_check(Model *const *models, int n_models, int P, const ghmm_corpus *c, const vocab_pass &v,
+                       const int32_t *seq, const int32_t *seq_off, const char *what, align_plan *pl)
+{
+    if (seq_off[0] != 0) {
+        ghmm_set_error("%s: seq_off[0] is %d, not 0", what, (int)seq_off[0]);
+        return GHMM_ERR_ARG;
+    }
+    for (int u = 0; u < c->U; u++)
+        if (seq_off[u + 1] < seq_off[u]) {
+            ghmm_set_error("%s: seq_off decreases at utterance %d", what, u);
+            return GHMM_ERR_ARG;
+        }
+    for (int32_t n = 0; n < seq_off[c->U]; n++)
+        if (seq[n] < 0 || seq[n] >= n_models) {
+            ghmm_set_error("%s: transcript entry %d is word %d of a vocabulary of %d", what, (int)n, (int)seq[n],
+                           n_models);
+            return GHMM_ERR_ARG;
+        }
+    for (int u = 0; u < c->U; u++)
+        if (c->len[u] > 0 && seq_off[u + 1] == seq_off[u]) {
+            ghmm_set_error("%s: utterance %d has %d frames and an empty transcript", what, u, (int)c->len[u]);
+            return GHMM_ERR_ARG;
+        }
+    if (v.Nmax > 64) {
+        ghmm_set_error("%s: a word of %d states: the alignment lattice takes 64", what, v.Nmax);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    pl->poff.assign((size_t)c->U, 0);
+    pl->psi_bytes = 0;
+    pl->Smax = 0;
+    for (int u = 0; u < c->U; u++) {
+        pl->poff[u] = pl->psi_bytes;
+        if (c->len[u] <= 0) continue;
+        long long S = 0;
+        for (int32_t n = seq_off[u]; n < seq_off[u + 1]; n++) S += models[(size_t)seq[n] * P]->N;
+        if (S > ALIGN_MAX_S) {
+            ghmm_set_error("%s: utterance %d: its transcript has %lld states, the alignment lattice takes %d", what,
+                           u, S, ALIGN_MAX_S);
+            return GHMM_ERR_UNSUPPORTED;
+        }
+        pl->Smax = std::max(pl->Smax, (int)S);
+        pl->psi_bytes += (long long)c->len[u] * S;
+    }
+    return GHMM_OK;
+}
+
+// The forced alignment behind its emission launches (U > 0, align_check passed): the call's tables
+// (poff[U] | seq_off[U + 1] | seq) into the context's al_tab ahead of the launch on the same stream, then
+// k_align, one workgroup per utterance, lattice and trace in ONE launch on the log b[F][NS] in the
+// workspace; then the scores (bt_ll[U]), the word per frame and, in one byte per frame, the state (bits
+// 0..5) with the begin mark (bit 7), which the host takes apart.  The back-pointers and the word per frame
+// go through the connected-word decoder's scratch (cn_psi, cn_word): both calls write what they read.
+// One stream wait.
+static int vocab_align(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c, const align_plan &pl,
+                       const int32_t *seq, const int32_t *seq_off, int32_t *word_host, int32_t *path_host,
+                       int32_t *begin_host, double *score_host)
+{
+    int rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "the transcripts and word_host are the device's ints");
+    const size_t U = (size_t)c->U, n_seq = (size_t)seq_off[c->U];
+    const size_t off_at = U * 8, seq_at = off_at + (U + 1) * 4, tab_bytes = seq_at + n_seq * 4;
+    if ((rc = ctx->cn_psi.grow((size_t)pl.psi_bytes + 16)) || (rc = ctx->cn_word.grow((size_t)c->F)) ||
+        (rc = ctx->path.grow((size_t)c->F)) || (rc = ctx->bt_ll.grow(U)) || (rc = ctx->al_tab.grow(tab_bytes)))
+        return rc;
+    // (pageable sources: the copies complete before the calls return them)
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab, pl.poff.data(), U * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab + off_at, seq_off, (U + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_seq) HIP_TRY(hipMemcpyAsync(ctx->al_tab + seq_at, seq, n_seq * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int Smax = std::max(pl.Smax, 1);
+    const size_t lds = align_lds(Smax);
+    if (lds > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_align))) return rc;
+    const int threads = std::min(CONNECT_THREADS, ((Smax + WAVE - 1) / WAVE) * WAVE);
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_align, dim3((unsigned)c->U), dim3((unsigned)threads), lds, ctx->stream, c->U, v.NS, v.dtab,
+                           (const double *)ctx->b, c->off, (const long long *)ctx->al_tab.p,
+                           (const int *)(ctx->al_tab + off_at), (const int *)(ctx->al_tab + seq_at), ctx->cn_psi,
+                           ctx->cn_word, ctx->path, ctx->bt_ll, c->order, Smax);
+    }
+    if ((rc = launch_ok("k_align"))) return rc;
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F) {
+        HIP_TRY(hipMemcpyAsync(word_host, ctx->cn_word, (size_t)c->F * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+        for (long long f = 0; f < c->F; f++) {
+            begin_host[f] = path_host[f] >> 7;
+            path_host[f] &= 63;
+        }
+    } else
+        HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}

@@ -36,6 +36,12 @@
  * per utterance, also on stdout: the feature file's name (stream 1's), the words' names in order, the
  * score.  The word file is read for the utterance count as always; what it says was spoken is not used.
  * Without the variable nothing changes.
+ * With GHMM_ALIGN=1 either program aligns every utterance with its known transcript instead
+ * (ghmm_align_streams / ghmm_align_full_streams): exactly one model set; every token of the word file is
+ * that utterance's transcript, the words' names joined by '+' (three+five+five), an unknown name is an
+ * error that names it; the output file's first line says forced alignment, then one line per utterance,
+ * also on stdout: feature_file : word first last  word first last ... : score (frames counted inside the
+ * utterance).  Together with GHMM_CONNECTED=1 it is refused.  Without the variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -110,7 +116,9 @@ static void rank_scores(const double *probab, int *index, int n)
 static FILE *f_out;
 
 /* GHMM_CONNECTED=1: the one model set's vocabulary (hm[k * GHMM_MAX_STREAMS + p]) on its P streams, every
- * utterance decoded as a word string; one line per utterance to stdout and the output file */
+ * utterance decoded as a word string; one line per utterance to stdout and the output file.
+ * GHMM_ALIGN=1 (seq_off != NULL): every utterance aligned with its transcript seq[seq_off[u] .. seq_off[u+1])
+ * instead, the line holding every word instance's first and last frame */
 #ifdef GHMM_FULL_COV
 typedef ghmm_host_fmodel host_model_t;
 typedef ghmm_fmodel dev_model_t;
@@ -119,7 +127,8 @@ typedef ghmm_host_model host_model_t;
 typedef ghmm_model dev_model_t;
 #endif
 static void run_connected(const host_model_t *hm, int word_number, int P, double *const *X, const int32_t *len,
-                          int n_utt, const int *D, double penalty, char *const *utt_name)
+                          int n_utt, const int *D, double penalty, char *const *utt_name, const int32_t *seq,
+                          const int32_t *seq_off)
 {
     int rc;
     size_t F = 0;
@@ -150,18 +159,29 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
 #endif
         }
 #ifdef GHMM_FULL_COV
-    rc = ghmm_connect_full_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
+    rc = seq_off ? ghmm_align_full_streams(ctx, flat, word_number, corpus, P, seq, seq_off, wd, st, bg, sc)
+                 : ghmm_connect_full_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
 #else
-    rc = ghmm_connect_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
+    rc = seq_off ? ghmm_align_streams(ctx, flat, word_number, corpus, P, seq, seq_off, wd, st, bg, sc)
+                 : ghmm_connect_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
 #endif
-    if (rc) die("decoding", rc);
+    if (rc) die(seq_off ? "alignment" : "decoding", rc);
     size_t f = 0;
     for (int u = 0; u < n_utt; u++) {
         FILE *to[2] = {stdout, f_out};
         for (int o = 0; o < 2; o++) {
             fprintf(to[o], "%s :", utt_name[u]);
-            for (int t = 0; t < len[u]; t++)
-                if (bg[f + t]) fprintf(to[o], " %s", hm[(size_t)wd[f + t] * GHMM_MAX_STREAMS].word);
+            for (int t = 0, n = 0; t < len[u]; t++) {
+                if (!bg[f + t]) continue;
+                const char *name = hm[(size_t)wd[f + t] * GHMM_MAX_STREAMS].word;
+                if (!seq_off) {
+                    fprintf(to[o], " %s", name);
+                    continue;
+                }
+                int last = t;
+                while (last + 1 < len[u] && !bg[f + last + 1]) last++;
+                fprintf(to[o], "%s %s %d %d", n++ ? " " : "", name, t, last);
+            }
             fprintf(to[o], " : %f\n", sc[u]);
         }
         f += (size_t)len[u];
@@ -223,6 +243,17 @@ int main(int argc, char **argv)
         printf("GHMM_CONNECTED=1 takes exactly one model set (given: %d) \n", K);
         exit(1);
     }
+    const char *env_al = getenv("GHMM_ALIGN");
+    const int align = env_al && strcmp(env_al, "1") == 0;
+    if (align && connected) {
+        printf("GHMM_ALIGN=1 and GHMM_CONNECTED=1 exclude each other \n");
+        exit(1);
+    }
+    if (align && K != 1) {
+        printf("GHMM_ALIGN=1 takes exactly one model set (given: %d) \n", K);
+        exit(1);
+    }
+    char **utt_words = NULL; /* alignment: every utterance's token of the word file, its transcript */
     char **utt_name = NULL; /* connected decoding: every utterance's feature file (stream 1's) */
 
     /* models: one list per set, the same vocabulary in every set */
@@ -321,9 +352,11 @@ int main(int argc, char **argv)
             cap_u = cap_u ? 2 * cap_u : 64;
             spoken = realloc(spoken, (size_t)cap_u * sizeof *spoken);
             for (int j = 0; j < K; j++) len[j] = (int32_t *)realloc(len[j], (size_t)cap_u * sizeof(int32_t));
-            if (connected) utt_name = (char **)realloc(utt_name, (size_t)cap_u * sizeof(char *));
+            if (connected || align) utt_name = (char **)realloc(utt_name, (size_t)cap_u * sizeof(char *));
+            if (align) utt_words = (char **)realloc(utt_words, (size_t)cap_u * sizeof(char *));
         }
         snprintf(spoken[n_utt], sizeof spoken[n_utt], "%s", w);
+        if (align && !(utt_words[n_utt] = strdup(w))) die("memory", GHMM_ERR_ALLOC);
         for (int j = 0; j < K; j++)
             for (int p = 0; p < Pj[j]; p++) {
                 if (fscanf(ff[j][p], "%4095s", path) != 1) {
@@ -339,7 +372,7 @@ int main(int argc, char **argv)
                     exit(1);
                 }
                 if (p == 0) len[j][n_utt] = T;
-                if (connected && p == 0 && !(utt_name[n_utt] = strdup(path))) die("memory", GHMM_ERR_ALLOC);
+                if ((connected || align) && p == 0 && !(utt_name[n_utt] = strdup(path))) die("memory", GHMM_ERR_ALLOC);
                 if (T != len[j][n_utt]) {
                     printf("file %s has %d frames, parameter 1 of the same utterance has %d \n", path, T, len[j][n_utt]);
                     exit(1);
@@ -364,13 +397,50 @@ int main(int argc, char **argv)
         printf("can't open file %s \n", output_file);
         exit(1);
     }
+    if (align) {
+        /* the transcripts: every token's names, joined by '+', as indices into the vocabulary */
+        int32_t *seq = NULL, *seq_off = (int32_t *)malloc(((size_t)n_utt + 1) * sizeof(int32_t));
+        size_t n_seq = 0, cap_seq = 0;
+        if (!seq_off) die("memory", GHMM_ERR_ALLOC);
+        seq_off[0] = 0;
+        for (int u = 0; u < n_utt; u++) {
+            for (char *tok = strtok(utt_words[u], "+"); tok; tok = strtok(NULL, "+")) {
+                int k = 0;
+                while (k < word_number && strcmp(tok, word[k]) != 0) k++;
+                if (k == word_number) {
+                    printf("utterance %s: word %s of its transcript is not in the vocabulary \n", utt_name[u], tok);
+                    exit(1);
+                }
+                if (n_seq == cap_seq) {
+                    cap_seq = cap_seq ? 2 * cap_seq : 256;
+                    if (!(seq = (int32_t *)realloc(seq, cap_seq * sizeof(int32_t)))) die("memory", GHMM_ERR_ALLOC);
+                }
+                seq[n_seq++] = k;
+            }
+            seq_off[u + 1] = (int32_t)n_seq;
+        }
+        if (!seq && !(seq = (int32_t *)calloc(1, sizeof(int32_t)))) die("memory", GHMM_ERR_ALLOC);
+#ifdef GHMM_FULL_COV
+        fprintf(f_out, "Forced alignment using Continuous HMM (full covariance matrix): Viterbi over every utterance's transcript \n");
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off);
+#else
+        fprintf(f_out, "Forced alignment using Continuous HMM (diagonal covariance matrix): Viterbi over every utterance's transcript \n");
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off);
+#endif
+        if (ferror(f_out) || fclose(f_out) != 0) {
+            printf("writing error on file %s \n", output_file);
+            exit(1);
+        }
+        free(seq); free(seq_off);
+        return 0;
+    }
     if (connected) {
 #ifdef GHMM_FULL_COV
         fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name);
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL);
 #else
         fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name);
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL);
 #endif
         if (ferror(f_out) || fclose(f_out) != 0) {
             printf("writing error on file %s \n", output_file);

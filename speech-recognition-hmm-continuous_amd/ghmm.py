@@ -111,6 +111,10 @@ SYMBOLS = {
                                        _ip, _dp], True),
     "ghmm_connect_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_double, _ip,
                                             _ip, _ip, _dp], True),
+    "ghmm_align_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip, _ip,
+                                     _dp], True),
+    "ghmm_align_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip,
+                                          _ip, _dp], True),
     "ghmm_logscore": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
     "ghmm_logscore_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
     "ghmm_logscore_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp], True),
@@ -537,6 +541,32 @@ def word_segments(word, begin, lens):
     return out
 
 
+def cut_segments(Xs, lens, segments, n_words, score=None):
+    """A connected corpus cut at word_segments' boundaries into one isolated-word corpus per word, what
+    Corpus and the trainers accept: Xs[p] = stream p's frames [F][D_p], lens[u] = utterance u's frames,
+    segments = word_segments(word, begin, lens).  Returns per word k = 0 .. n_words-1 the pair
+    (Xs_k, lens_k): Xs_k[p] = the frames of k's instances one after the other in stream p (utterance by
+    utterance, in time order), lens_k the instances' lengths; a word that never occurs has arrays of no
+    frames.  With score given (align_streams' per utterance) an utterance whose score is not finite is
+    left out: its alignment carries no meaning."""
+    Xs = [np.asarray(X) for X in Xs]
+    parts = [[[] for _ in Xs] for _ in range(n_words)]
+    out_lens = [[] for _ in range(n_words)]
+    f0 = 0
+    for u, T in enumerate(lens):
+        T = int(T)
+        if score is None or np.isfinite(score[u]):
+            for k, a, b in segments[u]:
+                if not (0 <= k < n_words and 0 <= a <= b < T):
+                    raise ValueError(f"utterance {u}: segment {(k, a, b)} outside {n_words} words or {T} frames")
+                for p, X in enumerate(Xs):
+                    parts[k][p].append(X[f0 + a:f0 + b + 1])
+                out_lens[k].append(b - a + 1)
+        f0 += T
+    return [([np.concatenate(parts[k][p]) if parts[k][p] else X[:0].copy() for p, X in enumerate(Xs)],
+             np.asarray(out_lens[k], dtype=np.int32)) for k in range(n_words)]
+
+
 def stats_len(N, M, D):
     return N * N + 2 * N + N * M * (2 * D + 1) + 2
 
@@ -762,6 +792,31 @@ class Context:
     def connect_full_streams(self, vocab, corpora, penalty=0.0):
         """connect_streams for full-covariance words"""
         return self._connect(self.lib.ghmm_connect_full_streams, vocab, corpora, penalty)
+
+    def _align(self, fn, vocab, corpora, transcripts):
+        F, U = corpora[0].frames, corpora[0].n_utt
+        if len(transcripts) != U:
+            raise ValueError(f"{len(transcripts)} transcripts for {U} utterances")
+        seq_off = np.zeros(U + 1, dtype=np.int32)
+        seq_off[1:] = np.cumsum([len(t) for t in transcripts])
+        seq = np.array([k for t in transcripts for k in t] + [0], dtype=np.int32)     # (never of size 0)
+        word, path, begin = (np.empty(F, dtype=np.int32) for _ in range(3))
+        score = np.empty(U, dtype=np.float64)
+        _check(fn(self.h, self._vocab_handles(vocab), len(vocab), self._stream_handles(corpora), len(corpora),
+                  seq.ctypes.data_as(_ip), seq_off.ctypes.data_as(_ip), word.ctypes.data_as(_ip),
+                  path.ctypes.data_as(_ip), begin.ctypes.data_as(_ip), _d(score)), self.lib)
+        return word, path, begin, score
+
+    def align_streams(self, vocab, corpora, transcripts):
+        """(word[F], path[F], begin[F], score[U]): every utterance aligned with its known transcript,
+        transcripts[u] = the sequence of its words' indices into vocab.  The outputs have connect_streams'
+        shape (word_segments takes them apart, cut_segments cuts the corpus at them); a score of -inf says
+        the utterance is too short for its transcript, its frame entries then carry no meaning"""
+        return self._align(self.lib.ghmm_align_streams, vocab, corpora, transcripts)
+
+    def align_full_streams(self, vocab, corpora, transcripts):
+        """align_streams for full-covariance words"""
+        return self._align(self.lib.ghmm_align_full_streams, vocab, corpora, transcripts)
 
     # ---- the forward score of diagonal models in the log domain
     def logscore(self, model, corpus, final_state=False):
