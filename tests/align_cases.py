@@ -17,7 +17,16 @@ what was spoken), some with further utterances behind them, composed the same wa
   short   narrow's corpus under other transcripts, most of them longer than their utterance: -inf.
   cap     many's vocabulary, ONE utterance of 682 three-state instances on 2200 frames: S = 2046, the
           launch with more than 48 KB of LDS, eight states per thread.
-  full    as it is."""
+  full    as it is.
+  cap-mixed  many's vocabulary, the cap's utterance among small ones, in this order: a 2-word one (S = 6),
+          T = 0 with an empty transcript, cap's 682 instances on 2200 frames (S = 2046), a 1-word one and a
+          20-word one.  All five run with 256 threads and LDS rows 2046 apart, the last two keep their
+          back-pointers behind the long one's 4.5 MB, order[] puts the long one first.
+  thick   connect_cases' thick (NS = 308, the ergodic words 1 and 23) + 20 instances alternating words 1
+          and 23 on 110 frames: S = 280, the dense step at s >= 256, in a thread's second pass, with an
+          instance that straddles 256.
+  holes   connect_cases' holes: full-covariance words with NaN and -inf columns in log b.  Not among ALL
+          (the host conditions there ask for a finite log b); HOLES names its transcripts."""
 import numpy as np
 
 import connect_cases as CC
@@ -41,12 +50,27 @@ EXTRA = {
     "short": ("narrow", [], 0),
     "cap": ("many", [(tuple((11 * i + 5) % 70 for i in range(682)), (4,) * 154 + (3,) * 528)], 716),
     "full": ("full", [], 0),
+    "cap-mixed": ("many", [((12, 40), (5, 6)), ((), ()),
+                           (tuple((11 * i + 5) % 70 for i in range(682)), (4,) * 154 + (3,) * 528),
+                           ((33,), (7,)), (tuple((7 * i + 3) % 70 for i in range(20)), (5, 4) * 10)], 717),
+    "thick": ("thick", [((1, 23) * 10, (6, 5) * 10)], 718),
+    "holes": ("holes", [], 0),
+}
+ALONE = ("cap", "cap-mixed")        # the further utterances are the case's only ones
+CAP_MIXED_LONG = 2                  # cap-mixed's utterance of 682 instances
+# holes' utterances have 50, 60, 12, 2 and 0 frames; words 0, 9 and 19 end in a NaN column, words 4 and 13
+# have a column of -inf.  name: (transcripts, what the scores must be)
+HOLES = {
+    "spoken": ([(2, 5), (11, 3, 16), (0,), (1,), ()], ("finite", "finite", "nan", "-inf", "0")),
+    "ends-in-nan": ([(2, 9), (11, 3, 19), (0,), (1,), ()], ("nan", "nan", "nan", "-inf", "0")),
+    "nan-in-the-middle": ([(3, 9, 6), (11, 0, 16), (0,), (1,), ()], ("-inf", "-inf", "nan", "-inf", "0")),
+    "through-minus-inf": ([(3, 4, 6), (13, 3), (0,), (1,), ()], ("-inf", "-inf", "nan", "-inf", "0")),
 }
 # short: narrow's lengths are 0, 1, 2, 7, 8, 9, 17, 40, 40 and its words have 5, 16 (ergodic) and 9 states
 SHORT = [(), (0, 2), (0, 2), (0, 2), (2, 0), (0, 2, 0), (2, 0, 2), (0, 2, 0), (2, 1, 0)]
-DIAGONAL = ("narrow", "mixed", "wide", "many", "ones", "short", "cap")
+DIAGONAL = ("narrow", "mixed", "wide", "many", "ones", "short", "cap", "cap-mixed", "thick")
 ALL = DIAGONAL + ("full",)
-SMALL = tuple(n for n in ALL if n != "cap")      # what the tests loop over freely
+SMALL = tuple(n for n in ALL if n not in ALONE + ("thick",))      # what the tests loop over freely
 
 
 def make(G, name):
@@ -60,7 +84,7 @@ def make(G, name):
         P = case.P
         parts = [[X] for X in case.Xs]
         lens = [int(T) for T in case.lens]
-        if name == "cap":
+        if name in ALONE:
             parts, lens, spoken = [[] for _ in range(P)], [], []
         for seq, seg in extra:
             assert len(seq) == len(seg)
@@ -181,5 +205,5 @@ def oracle_log_b(case):
     return CC.oracle_log_b(case)
 
 
-__all__ = ["ALL", "DIAGONAL", "SMALL", "GAP", "MAX_BELOW_GAP", "MAX_S", "ENTRY", "EXTRA", "SHORT", "make", "log_as",
+__all__ = ["ALL", "DIAGONAL", "SMALL", "ALONE", "CAP_MIXED_LONG", "HOLES", "GAP", "MAX_BELOW_GAP", "MAX_S", "ENTRY", "EXTRA", "SHORT", "make", "log_as",
            "states_of", "align_log", "align", "compared", "oracle_log_b"]

@@ -18,6 +18,27 @@ one walk of a stated length per word.  The smallest shapes at which the kernel c
           (GHMM_OPT_KERNELS = 1 only, where equal Gaussians give equal bits).
   full    fullvocab_cases' narrow words (its smallest vocabulary: NS = 30), two composed utterances and
           one single word.
+Past one composite state per thread (k_connect runs 256 threads), one stream and small (M, D) each:
+  thick   K = 28, N = (7, 16, 9, 12)[k % 4], (M, D) = (2, 3).  NS = 308: threads 0..51 own two states, five
+          of them a word end in their second pass (none two ends: that is crowd's and cap's).  Words 1
+          and 23 are ergodic; word 23 owns the composite states 252..263: its dense step reads the
+          previous row on both sides of s = 256.  One utterance of 3 frames, shorter than its word.
+  crowd   K = 300, N = (2, 3, 4)[k % 3], banded, (M, D) = (1, 2).  NS = 900: word numbers beyond one byte
+          and beyond the thread count.  (No one-state words: with A = [[1]] and p = 0 stay and entry tie.)
+  cap     32 words of 64 states, (M, D) = (1, 3).  NS = 2048, the cap: more than 48 KB of LDS, eight states
+          and up to eight word ends per thread.  Word 5 has columns off the band (vocab_cases._limited).
+          One word on exactly 64 frames (a single path); one utterance of 10 frames reaches no word end:
+          every pick is over -inf alone, across four waves, and gives word 0.
+  ones2048  K = 2048 one-state words with A = [[1]]: word k is the k % 5-th of five models, the SAME host
+          object (a device builds five models and repeats their handles).  Every thread owns eight word
+          ends; under GHMM_OPT_KERNELS = 1 the copies' columns are equal bits and every pick an exact
+          tie of 409 or 410.  Few frames: the restatement walks 2048 words per frame.
+  holes   full-covariance, (M, D) = (2, 4), K = 20, N = (8, 16, 24)[k % 3], NS = 312, with non-finite
+          log b: det = 0 in every mixture of the LAST state of words 0, 9 and 19 (their word ends are NaN
+          in every frame); c = 0 in state 2 of the banded words 4 and 13 (a column of -inf: they are never
+          passed); word 7 ergodic (state 0 does not reach its last state in one step) with det = 0 in
+          state 8: its dense step meets NaN candidates.  One utterance speaks word 0; one has 2 frames:
+          every healthy end is still -inf, and -inf beats NaN.
 Penalties: 0 and -5 on every case, -inf on every case, +3 and -1e4 on narrow."""
 import numpy as np
 
@@ -38,12 +59,27 @@ UTTS = {
     "many": [((5, 69, 33), (4, 5, 4)), ((64,), (6,)), ((0, 65), (3, 3)), ((17,), (1,))],
     "ones": [((0, 1, 2, 1), (3, 3, 3, 3)), ((2,), (1,)), ((0,), (0,))],
     "full": [((0, 2), (8, 12)), ((2, 0), (14, 9)), ((1,), (20,))],
+    "thick": [((5, 23), (14, 20)), ((23, 1, 10), (18, 24, 14)), ((2, 23, 27), (14, 18, 18)), ((12,), (12,)),
+              ((0,), (0,)), ((3,), (3,))],
+    "crowd": [((299, 3, 257), (6, 5, 7)), ((256, 150, 299, 12), (5, 6, 7, 5)), ((7, 257, 128, 256), (6, 7, 5, 6)),
+              ((280, 1, 290), (5, 6, 7)), ((40,), (1,)), ((0,), (0,))],
+    "cap": [((3, 17), (80, 75)), ((5,), (40,)), ((9,), (64,)), ((20,), (10,)), ((0,), (0,))],
+    "ones2048": [((0, 1, 2, 3), (2, 2, 2, 2)), ((3, 4), (3, 2)), ((4,), (3,)), ((0,), (0,))],
+    "holes": [((2, 5), (30, 20)), ((11, 3, 16), (28, 12, 20)), ((0,), (12,)), ((1,), (2,)), ((0,), (0,))],
 }
 UTTS["dup"] = UTTS["mixed"]
-SEEDS = {"narrow": 611, "mixed": 612, "wide": 613, "many": 614, "ones": 615, "dup": 612, "full": 616}
+SEEDS = {"narrow": 611, "mixed": 612, "wide": 613, "many": 614, "ones": 615, "dup": 612, "full": 616,
+         "thick": 811, "crowd": 812, "cap": 813, "ones2048": 815, "holes": 816}
 DIAGONAL = ("narrow", "mixed", "wide", "many", "ones", "dup")
 NONTIE = ("narrow", "mixed", "wide", "many", "full")      # compared with the restatement on both tiers
 ALL = DIAGONAL + ("full",)
+# more than one composite state per thread: compared with the restatement on both tiers, as NONTIE
+BEYOND = ("thick", "crowd", "cap")
+FULLCOV = ("full", "holes")                                # the cases of full-covariance words
+THICK_NS, CROWD_NS, CAP_WORDS, ONES_MODELS = (7, 16, 9, 12), (2, 3, 4), 32, 5
+HOLES_NS = (8, 16, 24)
+HOLES_NAN_END, HOLES_INF, HOLES_DENSE, HOLES_DENSE_NAN = (0, 9, 19), (4, 13), 7, 8
+HOLES_UNHEALTHY = HOLES_NAN_END + HOLES_INF + (HOLES_DENSE,)
 
 
 def penalties(name):
@@ -62,7 +98,42 @@ def _words(G, name, rng):
     if name == "many":
         from fullcov_support import banded
         return [[V.rand_model(G, rng, 3, 1, 2, banded(rng, 3), word=f"w{k}")] for k in range(70)]
+    if name in BEYOND + ("ones2048", "holes"):
+        return _beyond(G, name, rng)
     return [[V.rand_model(G, rng, 1, 2, 3, np.ones((1, 1)), word=f"w{k}")] for k in range(3)]       # ones
+
+
+def _beyond(G, name, rng):
+    from fullcov_support import banded, ergodic, rand_fmodel
+    if name == "thick":
+        return [[V.rand_model(G, rng, N, 2, 3, ergodic(rng, N) if k in (1, 23) else banded(rng, N), word=f"w{k}")]
+                for k, N in ((k, THICK_NS[k % 4]) for k in range(28))]
+    if name == "crowd":
+        return [[V.rand_model(G, rng, CROWD_NS[k % 3], 1, 2, banded(rng, CROWD_NS[k % 3]), word=f"w{k}")]
+                for k in range(300)]
+    if name == "cap":
+        return [[V.rand_model(G, rng, 64, 1, 3, V._limited(rng, 64) if k == 5 else banded(rng, 64), word=f"w{k}")]
+                for k in range(CAP_WORDS)]
+    if name == "ones2048":
+        five = [[V.rand_model(G, rng, 1, 2, 3, np.ones((1, 1)), word=f"w{k}")] for k in range(ONES_MODELS)]
+        return [five[k % ONES_MODELS] for k in range(2048)]
+    words = []                                                                                  # holes
+    for k in range(20):
+        N = HOLES_NS[k % 3]
+        A = None
+        if k == HOLES_DENSE:
+            A = ergodic(rng, N)
+            A[0, N - 1] = 0.0
+            A /= A.sum(1, keepdims=True)
+        h = rand_fmodel(G, rng, N, 2, 4, A, spread=1.0, asym=False, word=f"w{k}")
+        if k in HOLES_NAN_END:
+            h.det[N - 1, :] = 0.0
+        if k in HOLES_INF:
+            h.c[2, :] = 0.0
+        if k == HOLES_DENSE:
+            h.det[HOLES_DENSE_NAN, :] = 0.0
+        words.append([h])
+    return words
 
 
 def make(G, name):
@@ -80,7 +151,7 @@ def make(G, name):
         lens.append(int(sum(seg)))
         spoken.append(tuple(seq) if sum(seg) else ())
     Xs = [np.concatenate(x) for x in parts]
-    case = (FV.Case if name == "full" else V.Case)(words, Xs, lens)
+    case = (FV.Case if name in FULLCOV else V.Case)(words, Xs, lens)
     case.spoken, case.name = spoken, name
     return case
 
@@ -194,13 +265,28 @@ def decode(case, logb, p):
 
 
 def oracle_log_b(case):
-    """log b[F][NS] in float64: the oracle's (full: fullstreams_ref's) summed log emission, word by word"""
-    if case.name == "full":
+    """log b[F][NS] in float64: the oracle's (full-covariance: fullstreams_ref's) summed log emission, word
+    by word; a word that is the same host object as an earlier one (ones2048) takes that one's columns"""
+    if case.name in FULLCOV:
         import fullstreams_ref as S
-        cols = [np.asarray(S.log_emission(hms, case.Xs, np.float64)[0], dtype=np.float64) for hms in case.words]
+        one = lambda hms: np.asarray(S.log_emission(hms, case.Xs, np.float64)[0], dtype=np.float64)
     else:
-        cols = [V.log_b(hms, case.Xs) for hms in case.words]
+        one = lambda hms: V.log_b(hms, case.Xs)
+    seen = {}
+    cols = [seen[id(hms)] if id(hms) in seen else seen.setdefault(id(hms), one(hms)) for hms in case.words]
     return np.concatenate(cols, axis=1) if case.F else np.zeros((0, case.NS))
+
+
+def holes_pattern(case, lb):
+    """(the NaN columns, the -inf columns) that holes' models ask for; asserts that lb[F][NS] holds NaN in
+    exactly the former, -inf in exactly the latter and finite values elsewhere, in every frame"""
+    nan = [case.bo[k + 1] - 1 for k in HOLES_NAN_END] + [case.bo[HOLES_DENSE] + HOLES_DENSE_NAN]
+    inf = [case.bo[k] + 2 for k in HOLES_INF]
+    want_nan, want_inf = (np.isin(np.arange(case.NS), c)[None, :].repeat(case.F, 0) for c in (nan, inf))
+    assert np.array_equal(np.isnan(lb), want_nan), "log b is not NaN in exactly the columns of det = 0"
+    assert np.array_equal(lb == -np.inf, want_inf), "log b is not -inf in exactly the columns of c = 0"
+    assert np.isfinite(lb[~want_nan & ~want_inf]).all(), "log b is not finite in the other columns"
+    return sorted(int(c) for c in nan), sorted(int(c) for c in inf)
 
 
 def strings(word, begin, lens):
@@ -219,6 +305,9 @@ QUALIFY = {
     "wide": {0.0: [0, 1, 2], -5.0: [0, 1, 2]},
     "many": {0.0: [2], -5.0: []},
     "full": {0.0: [0, 1, 2], -5.0: [0, 1, 2]},
+    "thick": {0.0: [0, 3], -5.0: [3]},
+    "crowd": {0.0: [], -5.0: []},         # (300 words of one 2-d Gaussian per state: nothing is recognised)
+    "cap": {0.0: [0, 1, 2], -5.0: [0, 1, 2]},
 }
 
 
@@ -233,5 +322,5 @@ def qualifying(case):
     return out
 
 
-__all__ = ["ALL", "DIAGONAL", "NONTIE", "GAP", "ENTRY", "UTTS", "penalties", "make", "log_a", "beats", "pick",
-           "decode_log", "decode", "oracle_log_b", "strings", "QUALIFY", "qualifying"]
+__all__ = ["ALL", "DIAGONAL", "NONTIE", "BEYOND", "FULLCOV", "GAP", "ENTRY", "UTTS", "penalties", "make", "log_a", "beats", "pick",
+           "decode_log", "decode", "oracle_log_b", "holes_pattern", "strings", "QUALIFY", "qualifying"]

@@ -50,7 +50,7 @@ class Device:
 
     def __init__(self, G, ctx, case):
         self.G, self.ctx, self.case = G, ctx, case
-        self.full = case.name == "full"
+        self.full = case.name in CC.FULLCOV
         mk = ctx.full_model if self.full else ctx.model
         self.dms = [[mk(h) for h in w] for w in case.words]
         self.corpora = [ctx.corpus(X, case.lens) for X in case.Xs]
@@ -150,7 +150,7 @@ def against_the_restatement(d, transcripts=None):
 # ------------------------------------------------------------- 1. against the restatement
 
 @pytest.mark.parametrize("t", [0, 1])
-@pytest.mark.parametrize("name", AC.SMALL)
+@pytest.mark.parametrize("name", AC.SMALL + ("thick",))
 def test_against_the_restatement(G, ctx, devices, name, t):
     d = devices(name)
     with tier(G, ctx, t):
@@ -175,6 +175,61 @@ def test_the_cap(G, ctx, devices, t):
         assert AC.states_of(d.case, more[0]) == 2049
         assert code(G, lambda: d.align(more)) == G.ERR_UNSUPPORTED
         assert "2048" in ctx.lib.ghmm_last_error().decode()
+
+
+@pytest.mark.parametrize("t", [0, 1])
+def test_the_cap_among_small_utterances(G, ctx, devices, t):
+    """cap-mixed: S = 2046 in one launch with S = 6, 3 and 60 and an utterance of no frames.  Every block
+    runs 256 threads on LDS rows 2046 apart, most of them unused; the last two utterances keep their
+    back-pointers behind the long one's 4.5 MB.  Compared as test_the_cap compares; and every small
+    utterance's outputs are the bytes of the same utterance aligned in a launch without the long one"""
+    d = devices("cap-mixed")
+    case = d.case
+    long = AC.CAP_MIXED_LONG
+    keep = [u for u in range(case.U) if u != long]
+    off = offsets(case.lens)
+    at = np.concatenate([np.arange(off[u], off[u + 1]) for u in keep])
+    corpora = [ctx.corpus(X[at], case.lens[keep]) for X in case.Xs]
+    try:
+        with tier(G, ctx, t):
+            word, path, begin, score = against_the_restatement(d)
+            assert np.isfinite(score).all() and score[1] == 0.0
+            sw, sp, sb, ss = d.align([case.transcripts[u] for u in keep], corpora=corpora)
+        assert same(word[at], sw) and same(path[at], sp) and same(begin[at], sb) and same(score[keep], ss)
+    finally:
+        for c in corpora:
+            c.close()
+
+
+# ------------------------------------------------------------- 1b. log b that is not finite
+
+@pytest.mark.parametrize("t", [0, 1])
+def test_nan_and_minus_inf_columns(G, ctx, devices, t):
+    """connect_cases' holes: NaN (det = 0) and -inf (c = 0) columns in log b.  First the precondition on the
+    fetched log b.  Then: a transcript that ends in a NaN word end scores NaN; one with such a word in the
+    middle -inf (the NaN entry candidate never enters); one through a column of -inf scores -inf; the
+    spoken ones are finite, and on them consequences (b) and (c) hold against connect at penalty 0
+    wherever connect's score is finite.  All outputs are align_cases.align's on the fetched log b"""
+    d = devices("holes")
+    case = d.case
+    kinds = {"finite": np.isfinite, "nan": np.isnan, "-inf": lambda x: x == -INF, "0": lambda x: x == 0.0}
+    with tier(G, ctx, t):
+        for name, (trs, want) in AC.HOLES.items():
+            word, path, begin, score = against_the_restatement(d, trs)
+            nan, inf = CC.holes_pattern(case, d.log_b())        # the precondition
+            print("tier", t, name, "NaN columns", nan, "-inf columns", inf)
+            assert all(kinds[k](x) for k, x in zip(want, score)), (name, score)
+        cword, cpath, cbegin, cscore = d.connect(0.0)
+        fin = np.isfinite(cscore) & (case.lens > 0)
+        assert fin[:3].all()
+        strings = CC.strings(cword, cbegin, case.lens)
+        word, path, begin, score = d.align(strings)
+        assert np.array_equal(score[fin], cscore[fin]), (score, cscore)                 # (b)
+        gap = AC.align(case, d.log_b(), strings)[4]
+        at = np.repeat((gap > 0) & fin, case.lens)
+        assert same(word[at], cword[at]) and same(path[at], cpath[at]) and same(begin[at], cbegin[at])
+        spoken = d.align()[3]
+        assert not np.any(spoken[fin] > cscore[fin]), (spoken, cscore)                  # (c)
 
 
 # ------------------------------------------------------------- 2. the consequences of the definition

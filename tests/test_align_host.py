@@ -155,6 +155,18 @@ def test_shapes(cases, name):
     if name == "cap":
         assert case.U == 1 and len(case.transcripts[0]) == 682 and S == [2046] and case.lens[0] == 2200
         assert 2046 * 40 > 48 * 1024 and 2046 + 3 > AC.MAX_S
+    if name == "cap-mixed":
+        assert S == [6, 0, 2046, 3, 60] and case.lens.tolist() == [11, 0, 2200, 7, 90]
+        assert case.transcripts[1] == () and AC.CAP_MIXED_LONG == 2
+        assert case.transcripts[2] == tuple((11 * i + 5) % 70 for i in range(682))
+        assert case.lens[0] * S[0] + case.lens[2] * S[2] > 4.5e6        # where the last two's back-pointers begin
+    if name == "thick":
+        assert case.transcripts[:6] == [seq if sum(seg) else () for seq, seg in CC.UTTS["thick"]]
+        assert case.transcripts[-1] == (1, 23) * 10 and S[-1] == 280 and case.lens[-1] == 110
+        # instance 18 (word 1) owns the composite states 252 .. 267: it straddles 256; both words are dense
+        assert sum(case.Ns[k] for k in case.transcripts[-1][:18]) == 252 and case.Ns[1] == 16
+        for k in (1, 23):
+            assert np.any(np.tril(case.words[k][0].A, -1) != 0)
     assert max(S) <= AC.MAX_S
 
 
@@ -227,3 +239,37 @@ def test_cut_segments():
     assert [k for k, (_, l) in enumerate(part) if len(l)] == [7] and part[7][0][0][:, 0].tolist() == [6.0]
     with pytest.raises(ValueError):
         G.cut_segments([X0], lens, [[(9, 0, 1)], [], [], []], 8)
+
+
+# ------------------------------------------------------------- log b that is not finite
+
+def test_holes_transcripts_score_as_they_are_named(G):
+    """connect_cases' holes on the reference's log b: a transcript that ends in a NaN word end scores NaN;
+    one with such a word in the middle -inf (the NaN entry candidate never enters); one through a word with
+    a column of -inf scores -inf; the spoken ones are finite above the margin, and consequences (b) and
+    (c) hold against the decoder at penalty 0 where its score is finite"""
+    case = AC.make(G, "holes")
+    lb = AC.oracle_log_b(case)
+    kinds = {"finite": np.isfinite, "nan": np.isnan, "-inf": lambda x: x == -INF, "0": lambda x: x == 0.0}
+    assert set(AC.HOLES) == {"spoken", "ends-in-nan", "nan-in-the-middle", "through-minus-inf"}
+    assert AC.HOLES["spoken"][0] == case.transcripts
+    for name, (trs, want) in AC.HOLES.items():
+        word, path, begin, score, gap = AC.align(case, lb, trs)
+        print(name, score, gap)
+        assert all(kinds[k](x) for k, x in zip(want, score)), (name, score)
+        assert np.all(gap[case.lens > 0] > AC.GAP), (name, gap)
+    trs = AC.HOLES["ends-in-nan"][0]
+    assert trs[0][-1] == 9 and trs[1][-1] == 19 and AC.HOLES["nan-in-the-middle"][0][0][1] == 9
+    assert AC.HOLES["nan-in-the-middle"][0][1][1] == 0
+    assert all(set(t) & set(CC.HOLES_INF) for t in AC.HOLES["through-minus-inf"][0][:2])
+    # long enough but for the non-finite columns: more frames than states
+    for name in ("nan-in-the-middle", "through-minus-inf"):
+        assert all(AC.states_of(case, t) <= T for t, T in list(zip(AC.HOLES[name][0], case.lens))[:2])
+    cw, cp, cb, cs, cgap = CC.decode(case, lb, 0.0)
+    fin = np.isfinite(cs) & (case.lens > 0)
+    assert fin[:3].all()
+    strings = CC.strings(cw, cb, case.lens)
+    score = AC.align(case, lb, strings)[3]
+    assert np.array_equal(score[fin], cs[fin])
+    spoken = AC.align(case, lb)[3]
+    assert np.all(~(spoken[fin] > cs[fin]))

@@ -48,9 +48,11 @@ class Device:
 
     def __init__(self, G, ctx, case):
         self.G, self.ctx, self.case = G, ctx, case
-        self.full = case.name == "full"
+        self.full = case.name in CC.FULLCOV
         mk = ctx.full_model if self.full else ctx.model
-        self.dms = [[mk(h) for h in w] for w in case.words]
+        made = {}       # a host model that stands for several words (ones2048) is one device model: its handle repeats
+        self.dms = [[made[id(h)] if id(h) in made else made.setdefault(id(h), mk(h)) for h in w] for w in case.words]
+        self.models = list(made.values())
         self.corpora = [ctx.corpus(X, case.lens) for X in case.Xs]
 
     def connect(self, p, dms=None, corpora=None):
@@ -65,7 +67,7 @@ class Device:
         return self.ctx.fetch(self.G.BUF_B, (self.case.F, self.case.NS))
 
     def close(self):
-        for o in [m for w in self.dms for m in w] + self.corpora:
+        for o in self.models + self.corpora:
             o.close()
 
 
@@ -118,7 +120,7 @@ def check_shape_of_a_decoding(case, word, path, begin):
 # ------------------------------------------------------------- 1. against the restatement
 
 @pytest.mark.parametrize("t", [0, 1])
-@pytest.mark.parametrize("name", CC.NONTIE)
+@pytest.mark.parametrize("name", CC.NONTIE + CC.BEYOND)
 def test_against_the_restatement(G, ctx, devices, name, t):
     d = devices(name)
     case = d.case
@@ -140,13 +142,33 @@ def test_against_the_restatement(G, ctx, devices, name, t):
                 assert begin.sum() == (case.lens > 0).sum()
 
 
+def check_one_state_closed_form(case, lb, word, path, begin, score):
+    """one-state words with A = [[1]] at p = 0: every d_t(k) = e_{t-1} + log b_k(t).  A maximiser of the
+    previous frame stays (the tie goes to the word), every other word enters from the lowest maximiser"""
+    off = offsets(case.lens)
+    for u, T in enumerate(case.lens):
+        if T == 0:
+            assert score[u] == 0.0
+            continue
+        b = lb[off[u]:off[u + 1]]
+        ds = [b[0]]
+        for x in b[1:]:
+            ds.append(ds[-1].max() + x)
+        assert score[u] == ds[-1].max() and word[off[u + 1] - 1] == int(np.argmax(ds[-1]))
+        for f in range(1, T):
+            k, prev = word[off[u] + f], ds[f - 1]
+            if prev[k] == prev.max():
+                assert begin[off[u] + f] == 0 and word[off[u] + f - 1] == k, (u, f)
+            else:
+                assert begin[off[u] + f] == 1 and word[off[u] + f - 1] == int(np.argmax(prev)), (u, f)
+    assert np.all(path == 0)
+
+
 @pytest.mark.parametrize("t", [0, 1])
 def test_one_state_words_follow_from_the_log_b_exactly(G, ctx, devices, t):
-    """A = [[1]] and p = 0: every d_t(k) = e_{t-1} + log b_k(t).  A maximiser of the previous frame stays
-    (the tie goes to the word), every other word enters from the lowest maximiser"""
+    """A = [[1]] and p = 0: check_one_state_closed_form"""
     d = devices("ones")
     case = d.case
-    off = offsets(case.lens)
     with tier(G, ctx, t):
         for p in CC.penalties("ones"):
             word, path, begin, score = d.connect(p)
@@ -154,24 +176,33 @@ def test_one_state_words_follow_from_the_log_b_exactly(G, ctx, devices, t):
             rw, rp, rb, rs, _ = CC.decode(case, lb, p)
             assert same(word, rw) and same(path, rp) and same(begin, rb) and same(score, rs), p
             check_shape_of_a_decoding(case, word, path, begin)
-            if p != 0.0:
-                continue
-            for u, T in enumerate(case.lens):
-                if T == 0:
-                    assert score[u] == 0.0
-                    continue
-                b = lb[off[u]:off[u + 1]]
-                ds = [b[0]]
-                for x in b[1:]:
-                    ds.append(ds[-1].max() + x)
-                assert score[u] == ds[-1].max() and word[off[u + 1] - 1] == int(np.argmax(ds[-1]))
-                for f in range(1, T):
-                    k, prev = word[off[u] + f], ds[f - 1]
-                    if prev[k] == prev.max():
-                        assert begin[off[u] + f] == 0 and word[off[u] + f - 1] == k, (u, f)
-                    else:
-                        assert begin[off[u] + f] == 1 and word[off[u] + f - 1] == int(np.argmax(prev)), (u, f)
-            assert np.all(path == 0)
+            if p == 0.0:
+                check_one_state_closed_form(case, lb, word, path, begin, score)
+
+
+@pytest.mark.parametrize("t", [0, 1])
+def test_2048_one_state_words(G, ctx, devices, t):
+    """ones2048: K = NS = 2048, every thread folds eight word ends of its own, then the butterfly, then the
+    four partials.  log A is exactly 0 on both sides, so everything is compared exactly.  Under
+    GHMM_OPT_KERNELS = 1 the copies of a model have equal bits: every pick is a tie of 409 or 410 words and
+    goes to the lowest, a word below 5"""
+    d = devices("ones2048")
+    case = d.case
+    assert len(d.models) == 5 and case.K == 2048
+    with tier(G, ctx, t):
+        for p in CC.penalties("ones2048"):
+            word, path, begin, score = d.connect(p)
+            lb = d.log_b()
+            if t == 1:
+                for a in range(5):
+                    assert same(lb[:, a::5], np.repeat(lb[:, a:a + 1], lb[:, a::5].shape[1], axis=1)), a
+            rw, rp, rb, rs, _ = CC.decode(case, lb, p)
+            assert same(word, rw) and same(path, rp) and same(begin, rb) and same(score, rs), p
+            check_shape_of_a_decoding(case, word, path, begin)
+            if p == 0.0:
+                check_one_state_closed_form(case, lb, word, path, begin, score)
+            if t == 1:
+                assert np.all(word < 5), p
 
 
 def test_equal_words_take_the_lower_one(G, ctx, devices):
@@ -190,10 +221,39 @@ def test_equal_words_take_the_lower_one(G, ctx, devices):
             assert 3 not in word and 0 in word
 
 
+# ------------------------------------------------------------- 1b. log b that is not finite
+
+@pytest.mark.parametrize("t", [0, 1])
+def test_nan_and_minus_inf_columns(G, ctx, devices, t):
+    """holes: full-covariance words whose det = 0 (NaN) and c = 0 (-inf) put non-finite columns into log b.
+    First the precondition, on the fetched log b: NaN in exactly these columns, -inf in exactly those.
+    Then the rules of include/ghmm.h on the device: a NaN word end loses every pick to a value that is
+    not NaN (-inf included), a NaN never wins a strict > in the dense step, a NaN pick never enters"""
+    d = devices("holes")
+    case = d.case
+    with tier(G, ctx, t):
+        for p in CC.penalties("holes"):
+            word, path, begin, score = d.connect(p)
+            lb = d.log_b()
+            nan, inf = CC.holes_pattern(case, lb)       # the precondition: what the emission launches wrote
+            print("tier", t, "p", p, "NaN columns", nan, "-inf columns", inf)
+            rw, rp, rb, rs, gap = CC.decode(case, lb, p)
+            print("scores", score, "gaps on the device's log b", gap)
+            assert np.all(gap[:3] > CC.GAP), gap
+            assert same(word, rw) and same(path, rp) and same(begin, rb), (t, p)
+            scores_close(score, rs)
+            check_shape_of_a_decoding(case, word, path, begin)
+            assert np.isfinite(score[:3]).all() and score[3] == -INF and score[4] == 0.0
+            fin = np.repeat(np.isfinite(score), case.lens)
+            assert not np.isin(word[fin], CC.HOLES_NAN_END).any()
+            off = offsets(case.lens)
+            assert word[off[3]:off[4]].tolist() == [1, 1]       # -inf beats word 0's NaN: the lowest -inf end
+
+
 # ------------------------------------------------------------- 2. p = -inf is the isolated-word decoder
 
 @pytest.mark.parametrize("t", [0, 1])
-@pytest.mark.parametrize("name", CC.ALL)
+@pytest.mark.parametrize("name", CC.ALL + CC.BEYOND)
 def test_without_entries_it_is_recognise_bit_for_bit(G, ctx, devices, name, t):
     d = devices(name)
     case = d.case
@@ -239,17 +299,28 @@ def timed(G, ctx, call):
     return out, kt
 
 
-@pytest.mark.parametrize("name", ["narrow", "many", "full"])
+@pytest.mark.parametrize("name", ["narrow", "many", "full", "crowd", "cap"])
 def test_launch_counts_and_a_second_call(G, ctx, devices, name):
     """2 P - 1 launches under GHMM_K_EMISSION (full-covariance: P, the folds are the emission's own
-    epilogue) and ONE under GHMM_K_VITERBI: lattice and trace together; a second identical call repeats
-    every byte"""
+    epilogue) and ONE under GHMM_K_VITERBI: lattice and trace together, the launch with more than 48 KB of
+    LDS (cap) as well; a second identical call repeats every byte"""
     d = devices(name)
     P = d.case.P
     first = d.connect(-5.0) + (d.log_b(),)
     second, kt = timed(G, ctx, lambda: d.connect(-5.0))
     assert kt == {"emission": P if d.full else 2 * P - 1, "viterbi": 1}
     assert all(same(a, b) for a, b in zip(first, second + (d.log_b(),)))
+
+
+def test_across_the_48_kb_threshold_and_back(G, ctx, devices):
+    """cap's call (73 824 bytes of LDS, the largest back-pointer table), then narrow's (one wave, a small
+    table in the same buffer), then cap's again: the first and the third are the same bytes"""
+    big, small = devices("cap"), devices("narrow")
+    first = big.connect(-5.0) + (big.log_b(),)
+    between = small.connect(-5.0)
+    third = big.connect(-5.0) + (big.log_b(),)
+    assert all(same(a, b) for a, b in zip(first, third))
+    assert all(same(a, b) for a, b in zip(between, small.connect(-5.0)))
 
 
 def test_other_calls_in_between_change_nothing(G, ctx, devices):

@@ -2,7 +2,10 @@
 declared; connect_cases' restatement of the connected-word recursion is the definition (it equals an
 enumeration of ALL composite paths on a tiny vocabulary, the score bit for bit, the path under the tie
 rules); the cases, on the oracle's float64 log b, keep the margin under which a differing path cannot be
-blamed on rounding; and the composed utterances that decode to what was spoken are the recorded ones.
+blamed on rounding; the composed utterances that decode to what was spoken are the recorded ones; the cases
+beyond one composite state per thread reach what they are there for (word 23 on both sides of state 256,
+word numbers above 255 through the pick and the trace, no word end in 10 frames at the cap); and holes'
+reference log b holds NaN and -inf where its models ask for them, with the decoding the rules name.
 The margins are conditions on the inputs, not measurements: if a seed fails them, the seed changes, not
 the bound."""
 import itertools
@@ -132,6 +135,30 @@ def test_pick_is_the_order():
         assert all(CC.beats(s[best], best, s[k], k) for k in range(len(s)) if k != best), s
 
 
+def test_an_all_nan_pick_is_word_0_and_the_trace_starts_there():
+    """the rules of include/ghmm.h where every word end of the last frame is NaN: the final pick is word 0
+    (all NaN gives word 0), the score its NaN, and the trace starts in word 0's last state, whatever its
+    score; with the ends NaN in every frame no pick ever enters and the utterance stays in word 0; and a
+    word end of -inf beats the NaN ones"""
+    logAs = [CC.log_a(np.array([[0.6, 0.4], [0.0, 1.0]])), CC.log_a(np.ones((1, 1))),
+             CC.log_a(np.array([[0.5, 0.5], [0.0, 1.0]]))]
+    rng = np.random.default_rng(11)
+    logb = rng.normal(-3.0, 1.0, (4, 5))
+    logb[3, [1, 2, 4]] = np.nan                 # the three ends, in the last frame alone
+    for p in (0.0, -5.0, -INF):
+        word, path, begin, score, gap = CC.decode_log(logAs, logb, p)
+        assert np.isnan(score) and word[3] == 0 and path[3] == 1, p
+    # ... and in every frame: nothing ever enters, word 0 is walked from its first state
+    logb[:, [1, 2, 4]] = np.nan
+    word, path, begin, score, gap = CC.decode_log(logAs, logb, 0.0)
+    assert np.isnan(score) and word.tolist() == [0] * 4 and begin.tolist() == [1, 0, 0, 0] and path[3] == 1
+    # -inf beats NaN: with word 1's end finite or -inf in the last frame, word 1 is picked
+    for v in (-2.0, -INF):
+        logb[3, 2] = v
+        word, path, begin, score, gap = CC.decode_log(logAs, logb, -INF)
+        assert word[3] == 1 and score == -INF
+
+
 # ------------------------------------------------------------- the cases
 
 @pytest.fixture(scope="module")
@@ -146,10 +173,49 @@ def cases(G):
     return get
 
 
-@pytest.mark.parametrize("name", CC.ALL)
+def dense_words(case):
+    """the words with a transition off {j - 1, j}: the ones that take k_connect's dense step"""
+    out = []
+    for k, w in enumerate(case.words):
+        i, j = np.indices(w[0].A.shape)
+        if np.any((np.asarray(w[0].A) != 0) & (i != j) & (i != j - 1)):
+            out.append(k)
+    return out
+
+
+@pytest.mark.parametrize("name", CC.ALL + CC.BEYOND + ("ones2048",))
 def test_shapes(cases, name):
     case, lb = cases(name)
     lens = sorted(int(T) for T in case.lens)
+    if name == "thick":
+        assert case.K == 28 and case.Ns == [(7, 16, 9, 12)[k % 4] for k in range(28)] and case.NS == 308
+        assert dense_words(case) == [1, 23] and case.bo[23] == 252 and case.bo[24] == 264     # straddles 256
+        assert lens == [0, 3, 12, 34, 50, 56] and case.spoken[5] == (3,) and case.Ns[3] > 3
+        assert sum(23 in s for s in case.spoken) == 3 and sorted(len(s) for s in case.spoken) == [0, 1, 1, 2, 3, 3]
+        assert case.P == 1 and (case.words[0][0].M, case.words[0][0].D) == (2, 3)
+    if name == "crowd":
+        assert case.K == 300 and case.Ns == [(2, 3, 4)[k % 3] for k in range(300)] and case.NS == 900
+        assert dense_words(case) == [] and case.P == 1 and (case.words[0][0].M, case.words[0][0].D) == (1, 2)
+        assert lens[:2] == [0, 1] and len(lens) == 6
+        for seq, seg in CC.UTTS[name][:4]:
+            assert 3 <= len(seq) <= 4 and all(5 <= T <= 7 for T in seg)
+        assert {299, 257, 256} <= {k for s in case.spoken for k in s}
+        assert min(k for s in case.spoken for k in s) < 10
+    if name == "cap":
+        assert case.K == 32 and set(case.Ns) == {64} and case.NS == 2048 and dense_words(case) == [5]
+        assert len({w[0].mean.tobytes() for w in case.words}) == 32       # 32 distinct words
+        assert case.lens.tolist() == [155, 40, 64, 10, 0] and case.F < 300
+        assert case.spoken[:3] == [(3, 17), (5,), (9,)]
+        assert case.P == 1 and (case.words[0][0].M, case.words[0][0].D) == (1, 3)
+        assert 2048 * 36 + 96 == 73824 > 48 * 1024                          # k_connect's LDS at the cap
+    if name == "ones2048":
+        assert case.K == case.NS == 2048 and set(case.Ns) == {1}
+        assert all(case.words[k] is case.words[k % 5] for k in range(2048))
+        assert len({id(w) for w in case.words}) == 5 and len({w[0].mean.tobytes() for w in case.words[:5]}) == 5
+        assert all(np.array_equal(w[0].A, [[1.0]]) for w in case.words[:5])
+        assert lens == [0, 3, 5, 8]
+        for a in range(5):          # the copies' columns of the oracle's log b are one column
+            assert np.all(lb[:, a::5] == lb[:, a:a + 1])
     if name == "narrow":
         assert case.Ns == [5, 16, 9] and case.P == 3 and lens == [0, 1, 2, 7, 8, 9, 17, 40, 40]
         assert set(case.spoken) >= {(0,), (1, 2), (2, 0, 1), (0, 0)}
@@ -170,7 +236,7 @@ def test_shapes(cases, name):
     assert lb.shape == (case.F, case.NS) and np.isfinite(lb).all()
 
 
-@pytest.mark.parametrize("name", CC.NONTIE)
+@pytest.mark.parametrize("name", CC.NONTIE + CC.BEYOND)
 def test_margins(cases, name):
     """every utterance of every non-tie case, under every penalty of the case, keeps more than GAP at every
     decision along its traced path"""
@@ -191,7 +257,7 @@ def test_one_word_takes_each_utterance_under_a_prohibitive_penalty(cases):
     assert all(len(s) == 0 for s, T in zip(CC.strings(word, begin, case.lens), case.lens) if not T)
 
 
-@pytest.mark.parametrize("name", CC.NONTIE)
+@pytest.mark.parametrize("name", CC.NONTIE + CC.BEYOND)
 def test_spoken_sequences_that_decode(cases, name):
     case, lb = cases(name)
     got = CC.qualifying(case)
@@ -200,3 +266,69 @@ def test_spoken_sequences_that_decode(cases, name):
     composed = [u for _, u in got if len(case.spoken[u]) > 1]
     if name in ("narrow", "mixed", "full"):
         assert composed, "no composed utterance decodes to what was spoken"
+
+
+# ------------------------------------------------------------- more than one composite state per thread
+
+def test_thick_walks_word_23_on_both_sides_of_state_256(cases):
+    """some decoded path passes through word 23's composite states below 256 and at or above it: the states
+    of a thread's first and second pass"""
+    case, lb = cases("thick")
+    seen = set()
+    for p in CC.penalties("thick"):
+        word, path, begin, _, _ = CC.decode(case, lb, p)
+        seen |= set((case.bo[word] + path)[word == 23].tolist())
+    print(sorted(seen))
+    assert min(seen) >= 252 and max(seen) <= 263 and any(s < 256 for s in seen) and any(s >= 256 for s in seen)
+    # ... and the pick at p = 0 takes word ends from both passes
+    word, _, begin, _, _ = CC.decode(case, lb, 0.0)
+    ends = {int(case.bo[k + 1] - 1) for s in CC.strings(word, begin, case.lens) for k in s}
+    assert any(s < 256 for s in ends) and any(s >= 256 for s in ends)
+
+
+def test_crowd_decodes_words_beyond_one_byte(cases):
+    """at p = 0 a word >= 256 is decoded on a frame that continues it (the number went through the trace),
+    and a word is entered from the pick of a word >= 256 (the number went through word[t - 1])"""
+    case, lb = cases("crowd")
+    word, path, begin, score, _ = CC.decode(case, lb, 0.0)
+    first = np.zeros(case.F, dtype=bool)
+    first[np.concatenate([[0], np.cumsum(case.lens)])[:-1][case.lens > 0]] = True
+    assert np.any((word >= 256) & (begin == 0))
+    entered = np.nonzero((begin == 1) & ~first)[0]
+    assert np.any(word[entered - 1] >= 256)
+    assert score[case.lens == 1] == -INF      # (no one-state words: one frame reaches no word end)
+
+
+def test_cap_reaches_no_word_end_in_10_frames_and_has_one_path_in_64(cases):
+    case, lb = cases("cap")
+    for p in CC.penalties("cap"):
+        word, path, begin, score, gap = CC.decode(case, lb, p)
+        off = np.concatenate([[0], np.cumsum(case.lens)])
+        assert score[3] == -INF and np.all(word[off[3]:off[4]] == 0) and begin[off[3]:off[4]].sum() == 1
+        assert np.array_equal(path[off[2]:off[3]], np.arange(64)) and word[off[2]] == word[off[3] - 1]
+        assert np.isfinite(score[:3]).all()
+
+
+# ------------------------------------------------------------- log b that is not finite
+
+def test_holes(cases):
+    case, lb = cases("holes")
+    assert case.K == 20 and case.Ns == [(8, 16, 24)[k % 3] for k in range(20)] and case.NS == 312 and case.P == 1
+    assert (case.words[0][0].M, case.words[0][0].D) == (2, 4)
+    assert dense_words(case) == [CC.HOLES_DENSE] and case.words[CC.HOLES_DENSE][0].A[0, -1] == 0.0
+    nan, inf = CC.holes_pattern(case, lb)
+    assert nan == [7, 112, 151, 311] and inf == [58, 202]
+    assert nan[0] // 64 != nan[2] // 64 and nan[3] >= 256           # other waves, a thread's second slot
+    assert case.lens.tolist() == [50, 60, 12, 2, 0] and case.spoken[2] == (0,)
+    assert not set(k for s in case.spoken[:2] for k in s) & set(CC.HOLES_UNHEALTHY)
+    for p in CC.penalties("holes"):
+        word, path, begin, score, gap = CC.decode(case, lb, p)
+        print(p, score, gap, CC.strings(word, begin, case.lens))
+        assert np.isfinite(score[:3]).all() and score[3] == -INF and score[4] == 0.0
+        assert np.all(gap[:3] > CC.GAP)
+        fin = np.repeat(np.isfinite(score), case.lens)
+        assert not np.isin(word[fin], CC.HOLES_NAN_END).any()
+        assert not np.isin(word, CC.HOLES_INF).any()                # (never passed: they cannot end)
+        off = np.concatenate([[0], np.cumsum(case.lens)])
+        # two frames: every healthy end is -inf, and -inf beats word 0's NaN: the lowest word whose end is -inf
+        assert word[off[3]:off[4]].tolist() == [1, 1] and begin[off[3]:off[4]].tolist() == [1, 0]
