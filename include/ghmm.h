@@ -580,6 +580,72 @@ int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
 int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                        ghmm_corpus *const *corpora, int n_streams, const int32_t *seq, const int32_t *seq_off,
                        int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host);
+/* Embedded Baum-Welch: the E-step on the composite model of every utterance's transcript (n_streams >= 1;
+ * diagonal models).  The reference has no such call.  models[k * n_streams + p], corpora[p], seq and
+ * seq_off are ghmm_align_streams' vocabulary and transcript layout; stats[k * n_streams + p] is a
+ * ghmm_stats_create vector of word k's stream-p shape (N_k, M_p, D_p), OVERWRITTEN, so that
+ * ghmm_mstep(models[k * n_streams + p], stats[k * n_streams + p]) works unchanged.  The composite
+ * states, their columns in log b and log A are ghmm_align_streams'; LSE as at ghmm_logscore; a
+ * transition with a_ij == 0 is not a term; LSE2(x, y) = hi + log1p(exp(lo - hi)), lo == -inf giving hi:
+ *   la_0(i,j)   = (i == 0 && j == 0 ? 0 : -inf) + log b(0)
+ *   in_t(i,j)   = LSE_{i' : a_i'j > 0} (la_{t-1}(i,i') + log a_i'j)        ghmm_estep_log's step, its bits
+ *   la_t(i,0)   = (i > 0 ? LSE2(in_t(i,0), la_{t-1}(i-1, N_{i-1}-1)) : in_t(i,0)) + log b(t)
+ *   la_t(i,j)   = in_t(i,j) + log b(t)                                     j > 0; the entry carries weight 0
+ *   lbe_{T-1}(i,j) = (i == L-1 && j == N_i-1 ? 0 : -inf)
+ *   w_t(i,j)    = log b_{i,j}(t+1) + lbe_{t+1}(i,j)
+ *   wi_t(i,j)   = LSE_{j' : a_jj' > 0} (log a_jj' + w_t(i,j'))             within the word: ghmm_estep_log's step
+ *   lbe_t(i,j)  = (j == N_i-1 && i < L-1) ? LSE2(wi_t(i,j), w_t(i+1,0)) : wi_t(i,j)
+ *   log P_u     = la_{T-1}(L-1, N_{L-1}-1)
+ *   log Z_u     = LSE_j la_{T-1}(L-1, j)                                   over the LAST instance's states
+ *   gamma_t(i,j)  = exp((la_t(i,j) + lbe_t(i,j)) - log Z_u)
+ *   xi_t(i;j,j')  = exp(((la_t(i,j) + log a_jj') + w_t(i,j')) - log Z_u)   t < T-1, a_jj' > 0, j <= j' <= j + delta
+ *   stay_t(i,j)   = exp((la_t(i,j) + wi_t(i,j)) - log Z_u)                 the share of gamma that stays in the word
+ * LSE2 is formed ONLY in the first state of an instance behind the first and in the last state of an
+ * instance before the last.  The sums of word k are tied over every instance i with k_i == k, in ascending
+ * instance order, then over the utterances in ghmm_estep_log's order (one partial per utterance):
+ *   gamma_t(k,j)    = sum_i gamma_t(i,j)          GHMM_BUF_GAMMA [F][NS]; 0 in the columns of absent words
+ *   num_a[k][j][j'] = sum_u sum_{t<T-1} sum_i xi_t(i;j,j')
+ *   den_a[k][j]     = sum_u sum_{t<T-1} sum_i stay_t(i,j)
+ *   den_c[k][j]     = sum_u sum_{t<T}   gamma_t(k,j)
+ *   num_c / num_mu / num_var of stream p: calc_mix_param on w = gamma_t(k,j) * post^p_t(k,j,m),
+ *                     ghmm_estep_log's posteriors
+ *   loglik = sum_u log P_u and n_utt = U: the same bits in EVERY stats[k * n_streams + p]
+ * den_a is built on stay, not gamma: the exit into the next instance has no parameter and receives no xi,
+ * so with stay the rows of the next A still sum to 1 (sum_j' num_a[k][j][j'] == den_a[k][j] to rounding
+ * wherever the band holds every a_jj' > 0); with gamma a word's last self-loop would shrink every
+ * iteration by the mass that left the word.  log Z_u over the last instance is ghmm_estep_log's
+ * normaliser carried over: a frame's gammas sum to exp(log P_u - log Z_u), the same value at every t.
+ * Where log Z_u is not finite (an utterance too short for its transcript, no path, a NaN column) the
+ * utterance adds nothing but its log P_u to loglik and 1 to n_utt, and its gamma rows are 0.  T = 0 adds 0
+ * to loglik and counts in n_utt; its transcript may be empty.  U = 0 gives all-zero vectors.  A word that
+ * no transcript holds gets zero sums and the common loglik and n_utt: ghmm_mstep on it would re-invert its
+ * variances (see ghmm_mstep), so a trainer skips it.
+ * Consequences:
+ *   (a) with n_models == 1 and one-word transcripts, under GHMM_OPT_KERNELS = 1, stats[p], GHMM_BUF_GAMMA,
+ *       GHMM_BUF_LOGLIK and GHMM_BUF_B are ghmm_estep_log_streams' on the same context, bit for bit;
+ *   (b) with one-word transcripts and any vocabulary, word k's sums are ghmm_estep_log_streams' on the
+ *       sub-corpus of its utterances, to rounding;
+ *   (c) a transcript (k, k) gives word k the sum of what two separate copies of the word would get.
+ * Asynchronous on the context's stream; a second identical call repeats every byte; GHMM_OPT_DELTA is
+ * honoured; GHMM_OPT_ROBUST has no effect with one stream and is refused with several, as in the
+ * vocabulary calls.  Afterwards GHMM_BUF_B holds log b[F][NS], GHMM_BUF_GAMMA the tied gamma[F][NS],
+ * GHMM_BUF_LOGLIK log P_u; GHMM_BUF_POST is served for n_streams == 1 and refused beyond, as after
+ * ghmm_estep_log_streams; GHMM_BUF_ALPHA, _BETA and _SCALE give GHMM_ERR_ARG (the composite la rows are
+ * ragged and nobody else's to read); the row API does not reuse any of these buffers.  A vector's mailbox
+ * is not written: ghmm_stats_loglik copies and waits.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_align_streams refuses (a
+ * word of more than 64 states, S_u > 2048 on an utterance with T > 0, an empty transcript with T > 0, a
+ * word outside the vocabulary, ...; both transcript arrays are needed when U > 0); GHMM_ERR_ARG for a
+ * null stats array or entry, a vector that is not word k's stream-p shape, or a full-covariance one.
+ * Full-covariance words are not taken (the lattice, csrc/ghmm_embed.hpp, sees only log b[F][NS] and the
+ * words' table, so such an entry point can follow).
+ * 2 n_streams - 1 launches under GHMM_K_EMISSION; TWO under GHMM_K_FORWARD (the lattice forwards and
+ * backwards, one workgroup per utterance); per stream ghmm_estep's statistics launches on the
+ * concatenated vocabulary under GHMM_K_MIXSTATS and GHMM_K_REDUCE, and one more under GHMM_K_REDUCE that
+ * hands every word its own blocks. */
+int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                             ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
+                             const int32_t *seq_off, ghmm_stats *const *stats);
 /* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
  * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
  * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are

@@ -25,6 +25,7 @@
 #include "ghmm_wide.hpp"
 #include "ghmm_connect.hpp"
 #include "ghmm_align.hpp"
+#include "ghmm_embed.hpp"
 #include "ghmm_fullcov.hpp"
 
 extern "C" void ghmm_set_error(const char *fmt, ...); // ghmm_io.c
@@ -163,6 +164,14 @@ struct ghmm_ctx {
     // ghmm_align_streams / _full_streams (k_align): the call's tables, poff[U] | seq_off[U + 1] | seq, uploaded
     // ahead of its launch (vocab_align); its back-pointers and words per frame go through cn_psi and cn_word
     dev_buf<char> al_tab;
+    // ghmm_estep_embed_streams (k_embed_fwd / k_embed_bwd): the composite la rows (ragged: S_u doubles per
+    // frame), the blocks' column-head tables [U][NS], and stream p's statistics of the concatenated model,
+    // from which k_embed_scatter fills the words' vectors.  embed_ws: the workspace holds that call's
+    // results, so alpha, beta and c_t are nobody's (ghmm_fetch refuses them); cleared by ws_full
+    dev_buf<double> em_la;
+    dev_buf<int> em_head;
+    dev_buf<double> em_vec[GHMM_MAX_STREAMS];
+    bool embed_ws = false;
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     dev_buf<double> b_stream;
@@ -1096,6 +1105,7 @@ static int ws_full(ghmm_ctx *ctx, int N, int M, const ghmm_corpus *c)
     ctx->U = c->U;
     ctx->N = N;
     ctx->G = N * M;
+    ctx->embed_ws = false;
     return GHMM_OK;
 }
 
@@ -1801,6 +1811,10 @@ static int fetch_impl(ghmm_ctx *ctx, int which, bool whole, size_t first, double
     const double *src = nullptr;
     size_t have = 0;
     size_t F = (size_t)ctx->F, N = (size_t)ctx->N, G = (size_t)ctx->G, U = (size_t)ctx->U;
+    if (ctx->embed_ws && (which == GHMM_BUF_ALPHA || which == GHMM_BUF_BETA || which == GHMM_BUF_SCALE)) {
+        ghmm_set_error("buffer %d: the embedded E-step's lattice rows are ragged and are not served", which);
+        return GHMM_ERR_ARG;
+    }
     switch (which) {
     case GHMM_BUF_B: src = ctx->b; have = F * N; break;
     case GHMM_BUF_POST:
@@ -2501,6 +2515,85 @@ extern "C" int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int 
         (rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v)))
         return rc;
     return vocab_align(ctx, v, corpora[0], pl, seq, seq_off, word_host, path_host, begin_host, score_host);
+}
+
+// ---- embedded Baum-Welch on word transcripts (ghmm_estep_embed_streams; definition in include/ghmm.h):
+// the vocabulary's gathers with the log tables, its emission in mode 3 (log b with every stream's
+// posteriors), the lattice over the transcripts' word instances (vocab_embed), ghmm_estep's statistics
+// launches once per stream on the CONCATENATED model into a vector of the context's, and one scatter per
+// stream of every word's diagonal blocks into its own vector
+extern "C" int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                        ghmm_corpus *const *corpora, int P, const int32_t *seq,
+                                        const int32_t *seq_off, ghmm_stats *const *stats)
+{
+    dvocab v;
+    align_plan pl;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, seq && seq_off, true, __func__, &v))) return rc;
+    ARG_CHECK_AS(__func__, stats, "null statistics");
+    for (int k = 0; k < n_models * P; k++)
+        if ((rc = check_stats(models[k], stats[k]))) return rc;
+    ghmm_corpus *c = corpora[0];
+    if (c->U == 0) { // no utterance: every sum is empty, loglik and n_utt are 0
+        for (int k = 0; k < n_models * P; k++) {
+            stats[k]->mbox_valid = false;
+            HIP_TRY(hipMemsetAsync(stats[k]->v, 0, stats[k]->n * 8, ctx->stream));
+        }
+        return GHMM_OK;
+    }
+    if ((rc = align_check(models, n_models, P, c, v, seq, seq_off, __func__, &pl))) return rc;
+    if ((rc = vocab_gather(ctx, models, n_models, P, true, &v))) return rc;
+    const size_t F = (size_t)c->F, FN = F * v.NS;
+    if ((rc = ws_frames(ctx, v.cats[0], c, P == 1))) return rc;
+    if (P > 1) {
+        if ((rc = ctx->b_stream.grow(FN))) return rc;
+        for (int p = 0; p < P; p++)
+            if ((rc = ctx->post_s[p].grow(FN * v.cats[p]->M))) return rc;
+    }
+    for (int p = 0; p < P; p++) {
+        if ((rc = run_emission(ctx, v.cats[p], corpora[p], 3, p == 0 ? ctx->b : ctx->b_stream,
+                               P == 1 ? ctx->post : ctx->post_s[p])))
+            return rc;
+        if (p > 0 && FN && (rc = fold_stream(ctx, FN, true))) return rc;
+    }
+    // the workspace belongs to the concatenated vocabulary: the row API does not reuse it, and what an
+    // earlier pass left in alpha, beta and c_t goes with nothing here
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = true;
+    ctx->post_valid = P == 1;
+    ctx->N = v.NS;
+    ctx->G = v.NS * v.cats[0]->M;
+    ctx->embed_ws = true;
+    std::vector<embed_dst> dst((size_t)n_models * P);
+    for (int p = 0; p < P; p++) {
+        int bo = 0;
+        for (int k = 0; k < n_models; k++) {
+            const ghmm_model *m = models[(size_t)k * P + p];
+            dst[(size_t)p * n_models + k] = {stats[(size_t)k * P + p]->v, m->N, bo};
+            bo += m->N;
+        }
+    }
+    const embed_dst *ddst;
+    if ((rc = vocab_embed(ctx, v, c, pl, seq, seq_off, dst.data(), dst.size(), &ddst))) return rc;
+    for (int p = 0; p < P; p++) {
+        ghmm_model *cat = v.cats[p];
+        ghmm_stats cs; // the concatenated model's vector: the context's, without a mailbox
+        cs.N = cat->N; cs.M = cat->M; cs.D = cat->D;
+        cs.n = ghmm_stats_len(cat->N, cat->M, cat->D);
+        if ((rc = ctx->em_vec[p].grow(cs.n))) return rc;
+        cs.v = ctx->em_vec[p];
+        if ((rc = run_accumulate(ctx, cat, corpora[p], &cs, P == 1 ? ctx->post : ctx->post_s[p]))) return rc;
+        {
+            kscope ks(ctx, GHMM_K_REDUCE);
+            hipLaunchKernelGGL(k_embed_scatter, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, cat->N, cat->M,
+                               cat->D, (const double *)cs.v, ddst + (size_t)p * n_models);
+        }
+        if ((rc = launch_ok("k_embed_scatter"))) return rc;
+        // (the words' vectors are not k_reduce_all's: its mailbox does not describe them)
+        for (int k = 0; k < n_models; k++) stats[(size_t)k * P + p]->mbox_valid = false;
+    }
+    return GHMM_OK;
 }
 
 // ---- the forward score in the log domain (ghmm_logscore and its three companions; definitions in

@@ -433,3 +433,72 @@ static int vocab_align(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c,
         HIP_TRY(stream_sync(ctx));
     return GHMM_OK;
 }
+
+// ------------------------------------------------ embedded Baum-Welch
+
+// The embedded E-step's lattice behind its emission launches (U > 0, align_check passed; pl.poff counts
+// la entries here: rows of S_u doubles): the call's tables (poff[U] | seq_off[U + 1] | seq, then from the
+// next 16-byte boundary the caller's n_dst scatter entries, returned in *ddst) into the context's al_tab
+// ahead of the launches on the same stream, then k_embed_fwd (la rows into em_la, log P_u into loglik,
+// log Z_u into logk) and k_embed_bwd (the tied gamma[F][NS] and one partial per utterance for a model of
+// NS states, as run_log_lattice leaves them for the statistics launches).  Both launches count under
+// GHMM_K_FORWARD.  Nothing waits.  Called by ghmm_estep_embed_streams; it knows no kind of Gaussian.
+static int vocab_embed(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c, const align_plan &pl,
+                       const int32_t *seq, const int32_t *seq_off, const embed_dst *dst, size_t n_dst,
+                       const embed_dst **ddst)
+{
+    int rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "the transcripts are the device's ints");
+    const size_t U = (size_t)c->U, n_seq = (size_t)seq_off[c->U], NS = (size_t)v.NS;
+    const size_t off_at = U * 8, seq_at = off_at + (U + 1) * 4, dst_at = ((seq_at + n_seq * 4 + 15) / 16) * 16;
+    const size_t tab_bytes = dst_at + n_dst * sizeof(embed_dst);
+    if ((rc = ctx->em_la.grow((size_t)pl.psi_bytes + 1)) || (rc = ctx->em_head.grow(U * NS)) ||
+        (rc = ctx->gamma.grow((size_t)c->F * NS)) || (rc = ctx->logk.grow(U)) ||
+        (rc = ctx->part_xi.grow(U * NS * (MAX_DELTA + 1))) || (rc = ctx->part_dena.grow(U * NS)) ||
+        (rc = ctx->part_denc.grow(U * NS)) || (rc = ctx->al_tab.grow(tab_bytes)))
+        return rc;
+    // (pageable sources: the copies complete before the calls return them)
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab, pl.poff.data(), U * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab + off_at, seq_off, (U + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_seq) HIP_TRY(hipMemcpyAsync(ctx->al_tab + seq_at, seq, n_seq * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab + dst_at, dst, n_dst * sizeof(embed_dst), hipMemcpyHostToDevice, ctx->stream));
+    *ddst = (const embed_dst *)(ctx->al_tab + dst_at);
+    const int Smax = std::max(pl.Smax, 1);
+    const size_t lds_f = embed_fwd_lds(Smax), lds_b = embed_bwd_lds(Smax);
+    const int threads = std::min(EMBED_THREADS, ((Smax + WAVE - 1) / WAVE) * WAVE);
+    const int passes = (Smax + threads - 1) / threads;
+    const long long *dpoff = (const long long *)ctx->al_tab.p;
+    const int *dseq_off = (const int *)(ctx->al_tab + off_at), *dseq = (const int *)(ctx->al_tab + seq_at);
+#define GHMM_EMBED_FWD(PS)                                                                                         \
+    do {                                                                                                           \
+        if (lds_f > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_embed_fwd<PS>))) return rc;                 \
+        kscope ks(ctx, GHMM_K_FORWARD);                                                                            \
+        hipLaunchKernelGGL(k_embed_fwd<PS>, dim3((unsigned)c->U), dim3((unsigned)threads), lds_f, ctx->stream, c->U, \
+                           v.NS, v.dtab, (const double *)ctx->b, c->off, dpoff, dseq_off, dseq, ctx->em_la,        \
+                           ctx->loglik, ctx->logk, c->order, Smax);                                                \
+    } while (0)
+    if (passes <= 1) GHMM_EMBED_FWD(1);
+    else if (passes <= 2) GHMM_EMBED_FWD(2);
+    else if (passes <= 4) GHMM_EMBED_FWD(4);
+    else GHMM_EMBED_FWD(8);
+#undef GHMM_EMBED_FWD
+    if ((rc = launch_ok("k_embed_fwd"))) return rc;
+#define GHMM_EMBED_BWD(PS)                                                                                         \
+    do {                                                                                                           \
+        if (lds_b > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_embed_bwd<PS>))) return rc;                 \
+        kscope ks(ctx, GHMM_K_FORWARD);                                                                            \
+        hipLaunchKernelGGL(k_embed_bwd<PS>, dim3((unsigned)c->U), dim3((unsigned)threads), lds_b, ctx->stream, c->U, \
+                           v.NS, (int)ctx->delta, v.dtab, (const double *)ctx->b, c->off, dpoff, dseq_off, dseq,   \
+                           (const double *)ctx->em_la, (const double *)ctx->logk, ctx->gamma, ctx->part_xi,        \
+                           ctx->part_dena, ctx->part_denc, ctx->em_head, c->order, Smax);                          \
+    } while (0)
+    if (passes <= 1) GHMM_EMBED_BWD(1);
+    else if (passes <= 2) GHMM_EMBED_BWD(2);
+    else if (passes <= 4) GHMM_EMBED_BWD(4);
+    else GHMM_EMBED_BWD(8);
+#undef GHMM_EMBED_BWD
+    if ((rc = launch_ok("k_embed_bwd"))) return rc;
+    ctx->slots = c->U; // one partial per utterance
+    ctx->loglik_pieces = false;
+    return GHMM_OK;
+}
