@@ -536,6 +536,54 @@ int ghmm_recognise_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_model
 int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                          ghmm_corpus *const *corpora, int n_streams, double word_penalty,
                          int32_t *word_host, int32_t *path_host, int32_t *begin_host, double *score_host);
+/* Connected words under a word-pair grammar: ghmm_connect_streams' vocabulary, corpora, lattice and
+ * outputs, with a score for every ordered pair of words instead of one flat penalty (n_streams >= 1; the
+ * reference has no such decoder).  K = n_models:
+ *   pair[K*K]  row-major: pair[w*K + k] is the log score of word k following word w
+ *   start[K]   start[k] scores word k opening the utterance; null means all 0
+ *   fin[K]     fin[k] scores word k closing the utterance; null means all 0
+ * -inf forbids; finite values of either sign are allowed.  On the vocabulary's log b[F][NS], in
+ * ghmm_connect_streams' notation:
+ *   d_0(k,j)  = (j == 0 ? start[k] : -inf) + log b_{k,j}(0)
+ *   in_t(k,j) = ghmm_connect_streams' in_t(k,j): ghmm_viterbi's step inside word k, the same bits
+ *   c_t(w,k)  = d_{t-1}(w, N_w - 1) + pair[w][k]
+ *   x_t(k)    = the best c_t(w,k) over w, best starting at -inf with predecessor word 0: a candidate wins
+ *               on a strictly greater value, among equal values the lower w wins, a NaN candidate never
+ *               wins (an order: any reduction tree gives the same answer)
+ *   d_t(k,0)  = (x_t(k) > in_t(k,0) ? x_t(k) : in_t(k,0)) + log b_{k,0}(t)    the entry wins only on a strict >
+ *   d_t(k,j)  = in_t(k,j) + log b_{k,j}(t)             j > 0
+ *   score_u   = d_{T-1}(w, N_w - 1) + fin[w],  w = pick_k (d_{T-1}(k, N_k - 1) + fin[k])
+ * pick is ghmm_recognise_streams' rule.  The trace starts in the last state of the final pick, whatever
+ * its score; where the back-pointer of (t, k, 0) is the entry, frame t begins a word and the trace
+ * continues at (t-1, w, N_w - 1) with w the predecessor word kept for (t, k).  word_host[F], path_host[F],
+ * begin_host[F] and score_host[U] have ghmm_connect_streams' shape; T = 0 scores 0 and writes no frame
+ * entries.  Where the score is not finite the frame entries are what the trace gives on back-pointers of
+ * -inf candidates and carry no meaning.
+ * Consequences:
+ *   (a) with pair == p everywhere and start == fin == 0 the score equals ghmm_connect_streams(p)'s as a
+ *       value (rounding is monotone: max_w fl(e_w + p) = fl(max_w e_w + p)); at p = 0 and p = -inf word,
+ *       path and begin are that call's bit for bit, ties included; at other p wherever the optimum is
+ *       unique beyond rounding;
+ *   (b) for a transcript of pairwise distinct words k_0 .. k_{L-1}, with start 0 at k_0, pair 0 at
+ *       (k_i, k_{i+1}), fin 0 at k_{L-1} and -inf everywhere else, the score equals ghmm_align_streams'
+ *       as a value; where it is finite, word, path and begin are that call's;
+ *   (c) for any grammar and any utterance with a finite score, the decoded string's first word has
+ *       start > -inf, every adjacent pair has pair > -inf, and the last word has fin > -inf.
+ * The vocabulary layout, the gathers, the emission launches and folds, GHMM_BUF_B afterwards and U = 0
+ * (touches nothing) are ghmm_connect_streams'.  The grammar travels to the device ahead of the launch on
+ * the context's stream; then ONE launch under GHMM_K_VITERBI holds the lattice and the trace (one
+ * workgroup per utterance, csrc/ghmm_grammar.hpp): 2 n_streams - 1 launches under GHMM_K_EMISSION, one
+ * under GHMM_K_VITERBI, one wait for the stream.  A second identical call repeats every byte.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_connect_streams refuses
+ * (more than 2048 states in the vocabulary, a word of more than 64 states, GHMM_OPT_ROBUST with
+ * n_streams > 1, a missing destination when U > 0); GHMM_ERR_ARG for a null pair when U > 0 and for a NaN
+ * or +inf anywhere in start, pair or fin; GHMM_ERR_UNSUPPORTED for K > GHMM_GRAMMAR_MAX_WORDS (the dense
+ * K x K table and a predecessor word in one byte; a sparse successor list is not offered). */
+#define GHMM_GRAMMAR_MAX_WORDS 256
+int ghmm_connect_grammar_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                 ghmm_corpus *const *corpora, int n_streams, const double *start,
+                                 const double *pair, const double *fin, int32_t *word_host,
+                                 int32_t *path_host, int32_t *begin_host, double *score_host);
 /* Forced alignment: WHERE does each word of a known transcript lie (n_streams >= 1).  The reference has no
  * such call.  seq_off[U + 1], seq[seq_off[U]]: utterance u's transcript is the words
  * seq[seq_off[u] .. seq_off[u+1]): L_u instances, instance i = word k_i with N_i states.  The vocabulary
@@ -970,6 +1018,14 @@ int ghmm_connect_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_m
                               ghmm_corpus *const *corpora, int n_streams, double word_penalty,
                               int32_t *word_host, int32_t *path_host, int32_t *begin_host,
                               double *score_host);
+/* ghmm_connect_grammar_streams (above) for full-covariance words: the same definition, outputs, grammar
+ * arrays, refusals and lattice launch on ghmm_recognise_full_streams' log b[F][NS] (n_streams launches
+ * under GHMM_K_EMISSION, one under GHMM_K_VITERBI, one wait for the stream); consequences (a) to (c) hold
+ * against ghmm_connect_full_streams and ghmm_align_full_streams.  GHMM_OPT_ROBUST set is refused as there. */
+int ghmm_connect_grammar_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                      ghmm_corpus *const *corpora, int n_streams, const double *start,
+                                      const double *pair, const double *fin, int32_t *word_host,
+                                      int32_t *path_host, int32_t *begin_host, double *score_host);
 /* ghmm_align_streams (above) for full-covariance words: the same definition, outputs, refusals and lattice
  * launch on ghmm_recognise_full_streams' log b[F][NS] (n_streams launches under GHMM_K_EMISSION, one under
  * GHMM_K_VITERBI, one wait for the stream); consequences (a) to (c) hold against

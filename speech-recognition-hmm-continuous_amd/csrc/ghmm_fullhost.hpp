@@ -826,6 +826,26 @@ extern "C" int ghmm_connect_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *mode
     return vocab_connect(ctx, v, n_models, corpora[0], word_penalty, word_host, path_host, begin_host, score_host);
 }
 
+extern "C" int ghmm_connect_grammar_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                                 ghmm_corpus *const *corpora, int P, const double *start,
+                                                 const double *pair, const double *fin, int32_t *word_host,
+                                                 int32_t *path_host, int32_t *begin_host, double *score_host)
+{
+    vocab_pass v;
+    const bool have_dest = word_host && path_host && begin_host && score_host;
+    // as in ghmm_connect_full_streams: the vocabulary checks once ahead of fvocab_begin's own, the
+    // decoder's refusals need NS and come before anything is launched
+    int rc = use(ctx);
+    if (rc) return rc;
+    rc = vocab_checks(models, n_models, corpora, P, have_dest, __func__,
+                      [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); }, &v);
+    if (rc || (rc = grammar_check(v, n_models, corpora[0]->U, start, pair, fin, __func__))) return rc;
+    rc = fvocab_begin(ctx, models, n_models, corpora, P, have_dest, FC_LOG, __func__, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    return vocab_connect_grammar(ctx, v, n_models, corpora[0], start, pair, fin, word_host, path_host, begin_host,
+                                 score_host);
+}
+
 extern "C" int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                        ghmm_corpus *const *corpora, int P, const int32_t *seq,
                                        const int32_t *seq_off, int32_t *word_host, int32_t *path_host,

@@ -24,6 +24,7 @@
 #include "ghmm_pair.hpp"
 #include "ghmm_wide.hpp"
 #include "ghmm_connect.hpp"
+#include "ghmm_grammar.hpp"
 #include "ghmm_align.hpp"
 #include "ghmm_embed.hpp"
 #include "ghmm_fullcov.hpp"
@@ -164,6 +165,11 @@ struct ghmm_ctx {
     // ghmm_align_streams / _full_streams (k_align): the call's tables, poff[U] | seq_off[U + 1] | seq, uploaded
     // ahead of its launch (vocab_align); its back-pointers and words per frame go through cn_psi and cn_word
     dev_buf<char> al_tab;
+    // ghmm_connect_grammar_streams / _full_streams (k_grammar): the call's grammar, start[K] | pair[K][K] |
+    // fin[K], uploaded ahead of its launch (vocab_connect_grammar), and the predecessor word per (frame,
+    // word) [F][K]; its back-pointers and words per frame go through cn_psi and cn_word
+    dev_buf<double> gr_tab;
+    dev_buf<unsigned char> gr_entw;
     // ghmm_estep_embed_streams (k_embed_fwd / k_embed_bwd): the composite la rows (ragged: S_u doubles per
     // frame), the blocks' column-head tables [U][NS], and stream p's statistics of the concatenated model,
     // from which k_embed_scatter fills the words' vectors.  embed_ws: the workspace holds that call's
@@ -2497,6 +2503,23 @@ extern "C" int ghmm_connect_streams(ghmm_ctx *ctx, ghmm_model *const *models, in
     if (corpora[0]->U == 0) return GHMM_OK;
     if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
     return vocab_connect(ctx, v, n_models, corpora[0], word_penalty, word_host, path_host, begin_host, score_host);
+}
+
+extern "C" int ghmm_connect_grammar_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                            ghmm_corpus *const *corpora, int P, const double *start,
+                                            const double *pair, const double *fin, int32_t *word_host,
+                                            int32_t *path_host, int32_t *begin_host, double *score_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P,
+                                word_host && path_host && begin_host && score_host, true, __func__, &v)) ||
+        (rc = grammar_check(v, n_models, corpora[0]->U, start, pair, fin, __func__)))
+        return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
+    return vocab_connect_grammar(ctx, v, n_models, corpora[0], start, pair, fin, word_host, path_host, begin_host,
+                                 score_host);
 }
 
 extern "C" int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,

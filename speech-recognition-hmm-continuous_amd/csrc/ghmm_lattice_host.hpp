@@ -324,6 +324,90 @@ static int vocab_connect(ghmm_ctx *ctx, const vocab_pass &v, int n_models, const
     return GHMM_OK;
 }
 
+// ------------------------------------------------ connected words under a word-pair grammar
+
+// The grammar decoder's own refusals, behind the vocabulary checks that filled v and before anything is
+// launched, grown or written: what k_grammar holds (connect_check's states; a predecessor word in a
+// byte, the dense K x K table), a missing table when there are utterances, and entries that are NaN or
+// +inf (-inf forbids; start and fin may be null: all 0).  Called by ghmm_connect_grammar_streams and
+// ghmm_connect_grammar_full_streams.
+static int grammar_check(const vocab_pass &v, int K, int U, const double *start, const double *pair,
+                         const double *fin, const char *what)
+{
+    int rc = connect_check(v, 0.0, what);
+    if (rc) return rc;
+    static_assert(GRAMMAR_MAX_K == GHMM_GRAMMAR_MAX_WORDS, "the header's cap is the kernel's");
+    if (K > GRAMMAR_MAX_K) {
+        ghmm_set_error("%s: a vocabulary of %d words: the dense word-pair table takes GHMM_GRAMMAR_MAX_WORDS = %d",
+                       what, K, GRAMMAR_MAX_K);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    if (!pair) {
+        ARG_CHECK_AS(what, U == 0, "null pair table");
+        return GHMM_OK;
+    }
+    const struct {
+        const double *p;
+        size_t n;
+        const char *name;
+    } arrays[3] = {{start, (size_t)K, "start"}, {pair, (size_t)K * K, "pair"}, {fin, (size_t)K, "fin"}};
+    for (const auto &a : arrays)
+        for (size_t i = 0; a.p && i < a.n; i++)
+            if (a.p[i] != a.p[i] || a.p[i] == INFINITY) {
+                ghmm_set_error("%s: %s[%zu] is NaN or +inf", what, a.name, i);
+                return GHMM_ERR_ARG;
+            }
+    return GHMM_OK;
+}
+
+// The grammar decoder behind its emission launches (U > 0, grammar_check passed): the grammar (start[K] |
+// pair[K][K] | fin[K]; a null start or fin as zeros) into the context's gr_tab ahead of the launch on the
+// same stream, then k_grammar, one workgroup per utterance, lattice and trace in ONE launch on the log
+// b[F][NS] in the workspace; then the scores, the word per frame and the state byte with the begin mark
+// as vocab_connect returns them.  The back-pointers and the word per frame go through the connected-word
+// decoder's scratch (cn_psi, cn_word): both calls write what they read.  One stream wait.
+static int vocab_connect_grammar(ghmm_ctx *ctx, const vocab_pass &v, int K, const ghmm_corpus *c, const double *start,
+                                 const double *pair, const double *fin, int32_t *word_host, int32_t *path_host,
+                                 int32_t *begin_host, double *score_host)
+{
+    int rc;
+    const size_t KK = (size_t)K * K;
+    if ((rc = ctx->cn_psi.grow((size_t)c->F * v.NS + 16)) || (rc = ctx->cn_word.grow((size_t)c->F)) ||
+        (rc = ctx->path.grow((size_t)c->F)) || (rc = ctx->bt_ll.grow((size_t)c->U)) ||
+        (rc = ctx->gr_entw.grow((size_t)c->F * K + 16)) || (rc = ctx->gr_tab.grow(KK + 2 * (size_t)K)))
+        return rc;
+    // (pageable sources: the copies complete before the calls return them)
+    double *dstart = ctx->gr_tab, *dpair = dstart + K, *dfin = dpair + KK;
+    if (start) HIP_TRY(hipMemcpyAsync(dstart, start, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(hipMemsetAsync(dstart, 0, (size_t)K * 8, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dpair, pair, KK * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (fin) HIP_TRY(hipMemcpyAsync(dfin, fin, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(hipMemsetAsync(dfin, 0, (size_t)K * 8, ctx->stream));
+    const size_t lds = grammar_lds(v.NS, K);
+    if (lds > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_grammar))) return rc;
+    const int threads = std::min(CONNECT_THREADS, ((v.NS + WAVE - 1) / WAVE) * WAVE);
+    {
+        kscope ks(ctx, GHMM_K_VITERBI);
+        hipLaunchKernelGGL(k_grammar, dim3((unsigned)c->U), dim3((unsigned)threads), lds, ctx->stream, c->U, K, v.NS,
+                           v.dtab, (const double *)ctx->b, c->off, (const double *)ctx->gr_tab.p,
+                           (int)grammar_staged(v.NS, K), ctx->cn_psi, ctx->gr_entw, ctx->cn_word, ctx->path, ctx->bt_ll,
+                           c->order);
+    }
+    if ((rc = launch_ok("k_grammar"))) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "word_host takes the device's ints as they are");
+    HIP_TRY(hipMemcpyAsync(score_host, ctx->bt_ll, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->F) {
+        HIP_TRY(hipMemcpyAsync(word_host, ctx->cn_word, (size_t)c->F * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = d2h_pageable(ctx, path_host, ctx->path, (size_t)c->F, true))) return rc;
+        for (long long f = 0; f < c->F; f++) {
+            begin_host[f] = path_host[f] >> 7;
+            path_host[f] &= 63;
+        }
+    } else
+        HIP_TRY(stream_sync(ctx));
+    return GHMM_OK;
+}
+
 // ------------------------------------------------ forced alignment
 
 // What align_check works out of a call's transcripts for vocab_align: the utterances' back-pointer

@@ -36,6 +36,15 @@
  * per utterance, also on stdout: the feature file's name (stream 1's), the words' names in order, the
  * score.  The word file is read for the utterance count as always; what it says was spoken is not used.
  * Without the variable nothing changes.
+ * With GHMM_GRAMMAR=<file> beside GHMM_CONNECTED=1 the string is decoded under a word-pair grammar
+ * (ghmm_connect_grammar_streams / ghmm_connect_grammar_full_streams).  The file is text: K, then the K
+ * start scores, then K rows of K pair scores (row w, column k: word k after word w, the words in the model
+ * list's order), then the K end scores; every token goes through strtod, which accepts -inf (forbidden).
+ * GHMM_WORD_PENALTY is added to every pair score.  The output file's first line names the grammar file.
+ * A file that is short or holds a token that is no number, GHMM_GRAMMAR without GHMM_CONNECTED=1 or with
+ * GHMM_ALIGN=1: a message and exit 1 before any model or feature file is read; a K that is not the
+ * model list's: the same as soon as the list has been counted, before any feature file is read.
+ * Without the variable nothing changes.
  * With GHMM_ALIGN=1 either program aligns every utterance with its known transcript instead
  * (ghmm_align_streams / ghmm_align_full_streams): exactly one model set; every token of the word file is
  * that utterance's transcript, the words' names joined by '+' (three+five+five), an unknown name is an
@@ -118,7 +127,8 @@ static FILE *f_out;
 /* GHMM_CONNECTED=1: the one model set's vocabulary (hm[k * GHMM_MAX_STREAMS + p]) on its P streams, every
  * utterance decoded as a word string; one line per utterance to stdout and the output file.
  * GHMM_ALIGN=1 (seq_off != NULL): every utterance aligned with its transcript seq[seq_off[u] .. seq_off[u+1])
- * instead, the line holding every word instance's first and last frame */
+ * instead, the line holding every word instance's first and last frame.
+ * GHMM_GRAMMAR (gram != NULL): start[K] | pair[K][K] | fin[K], the penalty already added to pair */
 #ifdef GHMM_FULL_COV
 typedef ghmm_host_fmodel host_model_t;
 typedef ghmm_fmodel dev_model_t;
@@ -128,7 +138,7 @@ typedef ghmm_model dev_model_t;
 #endif
 static void run_connected(const host_model_t *hm, int word_number, int P, double *const *X, const int32_t *len,
                           int n_utt, const int *D, double penalty, char *const *utt_name, const int32_t *seq,
-                          const int32_t *seq_off)
+                          const int32_t *seq_off, const double *gram)
 {
     int rc;
     size_t F = 0;
@@ -160,9 +170,14 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
         }
 #ifdef GHMM_FULL_COV
     rc = seq_off ? ghmm_align_full_streams(ctx, flat, word_number, corpus, P, seq, seq_off, wd, st, bg, sc)
+         : gram  ? ghmm_connect_grammar_full_streams(ctx, flat, word_number, corpus, P, gram, gram + word_number,
+                                                     gram + word_number + (size_t)word_number * word_number, wd, st,
+                                                     bg, sc)
                  : ghmm_connect_full_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
 #else
     rc = seq_off ? ghmm_align_streams(ctx, flat, word_number, corpus, P, seq, seq_off, wd, st, bg, sc)
+         : gram  ? ghmm_connect_grammar_streams(ctx, flat, word_number, corpus, P, gram, gram + word_number,
+                                                gram + word_number + (size_t)word_number * word_number, wd, st, bg, sc)
                  : ghmm_connect_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
 #endif
     if (rc) die(seq_off ? "alignment" : "decoding", rc);
@@ -195,6 +210,37 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
     for (int p = 0; p < P; p++) ghmm_corpus_destroy(ctx, corpus[p]);
     ghmm_ctx_destroy(ctx);
     free(flat); free(wd); free(sc);
+}
+
+/* GHMM_GRAMMAR: the file's K into *K_out and its start[K] | pair[K][K] | fin[K] as one array; a file that
+ * cannot be opened, is short or holds a token that is no number ends the program */
+static double *read_grammar(const char *path, int *K_out)
+{
+    FILE *f = open_read(path);
+    char tok[256], *end;
+    long K = 0;
+    if (fscanf(f, "%255s", tok) == 1) K = strtol(tok, &end, 10);
+    if (K < 1 || K > 1 << 20 || *end) {
+        printf("grammar file %s: its first token must be the number of words \n", path);
+        exit(1);
+    }
+    const size_t n = (size_t)K * (size_t)K + 2 * (size_t)K;
+    double *g = (double *)malloc(n * sizeof(double));
+    if (!g) die("memory", GHMM_ERR_ALLOC);
+    for (size_t i = 0; i < n; i++) {
+        if (fscanf(f, "%255s", tok) != 1) {
+            printf("grammar file %s is short: %zu of the %zu scores of %ld words \n", path, i, n, K);
+            exit(1);
+        }
+        g[i] = strtod(tok, &end);
+        if (end == tok || *end) {
+            printf("grammar file %s: score %zu (%s) is no number \n", path, i, tok);
+            exit(1);
+        }
+    }
+    fclose(f);
+    *K_out = (int)K;
+    return g;
 }
 
 /* writing_result_word, RF:1111-1150 */
@@ -253,6 +299,14 @@ int main(int argc, char **argv)
         printf("GHMM_ALIGN=1 takes exactly one model set (given: %d) \n", K);
         exit(1);
     }
+    const char *env_gram = getenv("GHMM_GRAMMAR");
+    double *gram = NULL;
+    int gram_K = 0;
+    if (env_gram && !connected) {
+        printf("GHMM_GRAMMAR takes GHMM_CONNECTED=1%s \n", align ? ", not GHMM_ALIGN=1" : "");
+        exit(1);
+    }
+    if (env_gram) gram = read_grammar(env_gram, &gram_K);
     char **utt_words = NULL; /* alignment: every utterance's token of the word file, its transcript */
     char **utt_name = NULL; /* connected decoding: every utterance's feature file (stream 1's) */
 
@@ -320,6 +374,12 @@ int main(int argc, char **argv)
         printf("no models in %s \n", argv[2]);
         exit(1);
     }
+    if (gram && gram_K != word_number) {
+        printf("grammar file %s is for %d words, the model list %s holds %d \n", env_gram, gram_K, argv[2], word_number);
+        exit(1);
+    }
+    if (gram) /* the flat penalty on top of every pair score */
+        for (size_t i = 0; i < (size_t)gram_K * gram_K; i++) gram[gram_K + i] += word_penalty;
     char **word = (char **)malloc((size_t)word_number * sizeof(char *));
 #ifdef GHMM_FULL_COV
     for (int k = 0; k < word_number; k++) word[k] = fhm[K - 1][(size_t)k * GHMM_MAX_STREAMS].word; /* RC:229 */
@@ -422,10 +482,10 @@ int main(int argc, char **argv)
         if (!seq && !(seq = (int32_t *)calloc(1, sizeof(int32_t)))) die("memory", GHMM_ERR_ALLOC);
 #ifdef GHMM_FULL_COV
         fprintf(f_out, "Forced alignment using Continuous HMM (full covariance matrix): Viterbi over every utterance's transcript \n");
-        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off);
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL);
 #else
         fprintf(f_out, "Forced alignment using Continuous HMM (diagonal covariance matrix): Viterbi over every utterance's transcript \n");
-        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off);
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL);
 #endif
         if (ferror(f_out) || fclose(f_out) != 0) {
             printf("writing error on file %s \n", output_file);
@@ -436,11 +496,13 @@ int main(int argc, char **argv)
     }
     if (connected) {
 #ifdef GHMM_FULL_COV
-        fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL);
+        if (gram) fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g, grammar %s \n", word_penalty, env_gram);
+        else fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram);
 #else
-        fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL);
+        if (gram) fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g, grammar %s \n", word_penalty, env_gram);
+        else fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram);
 #endif
         if (ferror(f_out) || fclose(f_out) != 0) {
             printf("writing error on file %s \n", output_file);

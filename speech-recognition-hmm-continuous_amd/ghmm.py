@@ -111,6 +111,10 @@ SYMBOLS = {
                                        _ip, _dp], True),
     "ghmm_connect_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_double, _ip,
                                             _ip, _ip, _dp], True),
+    "ghmm_connect_grammar_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp, _dp,
+                                               _ip, _ip, _ip, _dp], True),
+    "ghmm_connect_grammar_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp,
+                                                    _dp, _ip, _ip, _ip, _dp], True),
     "ghmm_align_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip, _ip,
                                      _dp], True),
     "ghmm_estep_embed_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
@@ -543,6 +547,43 @@ def word_segments(word, begin, lens):
     return out
 
 
+def bigram_log(transcripts, n_words, alpha=1.0):
+    """A word-pair grammar for connect_grammar_streams estimated from transcripts (sequences of word
+    indices below n_words; empty ones are skipped): (start[K], pair[K, K], fin[K]) in natural logs, K =
+    n_words.  Counts: s[k] = the transcripts that open with k; c[w, k] = the times k follows w; f[w] =
+    the transcripts that close with w (the end of a transcript is one more event of its last word's
+    row).  With additive smoothing alpha >= 0:
+        start[k]   = log((s[k]    + alpha) / (sum_k' s[k']            + alpha * K))
+        pair[w, k] = log((c[w, k] + alpha) / (sum_k' c[w, k'] + f[w]  + alpha * (K + 1)))
+        fin[w]     = log((f[w]    + alpha) / (sum_k' c[w, k'] + f[w]  + alpha * (K + 1)))
+    so that exp(start) sums to 1 and every row of exp(pair) together with exp(fin) of that row sums to 1.
+    A zero numerator gives -inf (alpha = 0: unseen events are forbidden), a row without any event as well."""
+    K = int(n_words)
+    if K < 1 or alpha < 0:
+        raise ValueError("bigram_log: n_words >= 1 and alpha >= 0")
+    s, c, f = np.zeros(K), np.zeros((K, K)), np.zeros(K)
+    for t in transcripts:
+        t = [int(k) for k in t]
+        if any(not 0 <= k < K for k in t):
+            raise ValueError(f"bigram_log: a word outside 0 .. {K - 1} in {t}")
+        if not t:
+            continue
+        s[t[0]] += 1
+        for w, k in zip(t[:-1], t[1:]):
+            c[w, k] += 1
+        f[t[-1]] += 1
+
+    def log_ratio(num, den):
+        num, den = np.broadcast_arrays(np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64))
+        out = np.full(num.shape, -np.inf)
+        ok = (num > 0) & (den > 0)
+        out[ok] = np.log(num[ok] / den[ok])
+        return out
+
+    row = c.sum(1) + f + alpha * (K + 1)
+    return log_ratio(s + alpha, s.sum() + alpha * K), log_ratio(c + alpha, row[:, None]), log_ratio(f + alpha, row)
+
+
 def cut_segments(Xs, lens, segments, n_words, score=None):
     """A connected corpus cut at word_segments' boundaries into one isolated-word corpus per word, what
     Corpus and the trainers accept: Xs[p] = stream p's frames [F][D_p], lens[u] = utterance u's frames,
@@ -794,6 +835,35 @@ class Context:
     def connect_full_streams(self, vocab, corpora, penalty=0.0):
         """connect_streams for full-covariance words"""
         return self._connect(self.lib.ghmm_connect_full_streams, vocab, corpora, penalty)
+
+    def _connect_grammar(self, fn, vocab, corpora, pair, start, fin):
+        K, F = len(vocab), corpora[0].frames
+        pair = np.ascontiguousarray(pair, dtype=np.float64)
+        if pair.shape != (K, K):
+            raise ValueError(f"pair has shape {pair.shape}, the vocabulary has {K} words")
+        rows = []
+        for name, a in (("start", start), ("fin", fin)):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            if a is not None and a.shape != (K,):
+                raise ValueError(f"{name} has shape {a.shape}, the vocabulary has {K} words")
+            rows.append(a)
+        word, path, begin = (np.empty(F, dtype=np.int32) for _ in range(3))
+        score = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(fn(self.h, self._vocab_handles(vocab), K, self._stream_handles(corpora), len(corpora), _d(rows[0]),
+                  _d(pair), _d(rows[1]), word.ctypes.data_as(_ip), path.ctypes.data_as(_ip),
+                  begin.ctypes.data_as(_ip), _d(score)), self.lib)
+        return word, path, begin, score
+
+    def connect_grammar_streams(self, vocab, corpora, pair, start=None, fin=None):
+        """connect_streams under a word-pair grammar, the same tuple (word_segments works on it):
+        pair[w, k] = the log score of word k following word w, start[k] of word k opening the utterance,
+        fin[k] of word k closing it (None: all 0); -inf forbids.  bigram_log estimates the three from
+        transcripts"""
+        return self._connect_grammar(self.lib.ghmm_connect_grammar_streams, vocab, corpora, pair, start, fin)
+
+    def connect_grammar_full_streams(self, vocab, corpora, pair, start=None, fin=None):
+        """connect_grammar_streams for full-covariance words"""
+        return self._connect_grammar(self.lib.ghmm_connect_grammar_full_streams, vocab, corpora, pair, start, fin)
 
     def _align(self, fn, vocab, corpora, transcripts):
         F, U = corpora[0].frames, corpora[0].n_utt
