@@ -1782,8 +1782,8 @@ static int run_accumulate(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_sta
         const int NGb = ra.Pm > 0 ? m->NT * 16 : G;
         kscope ks(ctx, GHMM_K_REDUCE);
         const int tile_blocks = ra.otile ? m->NT : 0; // the next model's tile offsets
-        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)(NGb + N * N + 2 * N + 1 + tile_blocks)), dim3(RD_THREADS), 0,
-                           ctx->stream, ra);
+        const long long blocks = (long long)NGb + (long long)N * N + 2 * N + 1 + tile_blocks;
+        hipLaunchKernelGGL(k_reduce_all, reduce_grid(blocks), dim3(RD_THREADS), 0, ctx->stream, ra);
     }
     return launch_ok("k_reduce_all");
 }

@@ -980,6 +980,16 @@ k_mixstats(int N, int M, int D, long long F, long long frames_per_block, int FS,
 //                         sums on the matrix-core tier too
 //   blocks [NG, NG+NU)    per-utterance partials of k_backward: num_a, den_a, den_c, loglik
 constexpr int RD_THREADS = 1024; // 128 feature lanes x 8 partial slices
+// A launch's extent along x is a 32-bit count of work-items: k_reduce_all's blocks, one per entry of num_a
+// among them, pass 2^32 / RD_THREADS at N = 2048 (ghmm_estep_embed_streams' concatenated vocabulary), and the
+// blocks beyond it were never run.  Its grid is (up to RD_MAX_GX, as many rows as it takes); a block's number
+// is blockIdx.x + blockIdx.y * gridDim.x, and the numbers past the last role do nothing.
+constexpr unsigned RD_MAX_GX = 1u << 21;
+inline dim3 reduce_grid(long long blocks)
+{
+    const unsigned gx = (unsigned)(blocks < (long long)RD_MAX_GX ? blocks : (long long)RD_MAX_GX);
+    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
+}
 
 __device__ inline double block_sum_fixed(double v, double *sh)
 {
@@ -1039,10 +1049,11 @@ __global__ void __launch_bounds__(RD_THREADS) k_reduce_all(reduce_args a)
     const int N = a.N, M = a.M, D = a.D, G = N * M, D1 = D + 1;
     const int NG = a.no_mix ? 0 : (a.Pm > 0 ? a.NT * 16 : G);
     const int tid = threadIdx.x;
+    const long long bid = blockIdx.x + (long long)blockIdx.y * gridDim.x; // (reduce_grid)
     double *num_a = a.stats, *den_a = num_a + (size_t)N * N, *den_c = den_a + N;
     double *num_c = den_c + N, *num_mu = num_c + G, *num_var = num_mu + (size_t)G * D;
-    if ((int)blockIdx.x < NG) {
-        const int gp = blockIdx.x;
+    if (bid < NG) {
+        const int gp = (int)bid;
         const int g = a.Pm > 0 ? a.gmap[gp] : gp;
         if (g < 0) return;
         constexpr int SL = RD_THREADS / 128;
@@ -1203,7 +1214,7 @@ __global__ void __launch_bounds__(RD_THREADS) k_reduce_all(reduce_args a)
         }
         return;
     }
-    const int q = blockIdx.x - NG, U = a.U;
+    const int q = (int)(bid - NG), U = a.U; // (a last row's numbers past every role end in the last branch: t >= NT)
     double v = 0.0;
     if (q < N * N) {
         int i = q / N, j = q % N, o = j - i;

@@ -26,7 +26,10 @@ what was spoken), some with further utterances behind them, composed the same wa
           and 23 on 110 frames: S = 280, the dense step at s >= 256, in a thread's second pass, with an
           instance that straddles 256.
   holes   connect_cases' holes: full-covariance words with NaN and -inf columns in log b.  Not among ALL
-          (the host conditions there ask for a finite log b); HOLES names its transcripts."""
+          (the host conditions there ask for a finite log b); HOLES names its transcripts.
+The cases of embed_cases alone (in none of the tuples below; embed_cases says what each reaches): wide128 (wide
+without its further utterance: S = 97), mid (mixed + two utterances that end on its word of 17 states), broad and broad256 (connect_cases'), pass4 (thick's vocabulary, S = 791),
+pass8 (many's, 342 instances: S = 1026) and deep (cap's 64-state words, S = 192)."""
 import numpy as np
 
 import connect_cases as CC
@@ -39,6 +42,10 @@ MAX_S = 2048
 # at most this many utterances of a case may have a gap of GAP or less on the oracle's log b and be left
 # out of the path comparison (test_align_host.py holds the cases to it; the seeds below meet it with 0)
 MAX_BELOW_GAP = 1
+
+# pass4: thick's ergodic words 1 (16 states) and 23 (12) recurring on 4 frames each, the banded word 4 (7 states,
+# 9 frames) after every fifth pair: 59 instances, S = 791, 261 frames
+PASS4_SEQ = ((1, 23) * 5 + (4,)) * 5 + (1, 23) * 2
 
 #        name: (connect_cases' case, [(further word sequence, frames per word)], seed of the further frames)
 EXTRA = {
@@ -55,8 +62,17 @@ EXTRA = {
                            ((33,), (7,)), (tuple((7 * i + 3) % 70 for i in range(20)), (5, 4) * 10)], 717),
     "thick": ("thick", [((1, 23) * 10, (6, 5) * 10)], 718),
     "holes": ("holes", [], 0),
+    # embed_cases' own (among none of the tuples below: the alignment tests do not walk them)
+    "wide128": ("wide", [], 0),
+    "mid": ("mixed", [((1, 2), (20, 22)), ((2,), (30,))], 723),
+    "broad": ("broad", [], 0),
+    "broad256": ("broad256", [], 0),
+    "pass4": ("thick", [(PASS4_SEQ, tuple(9 if k == 4 else 4 for k in PASS4_SEQ)), ((6, 23), (20, 6)), ((), ())], 719),
+    "pass8": ("many", [(tuple((11 * i + 5) % 70 for i in range(342)), (3,) * 300 + (4,) * 42),
+                       ((12, 40), (5, 6))], 722),      # (720: a cancelling num_mu, float64 spread 7e-9)
+    "deep": ("cap", [((3, 5, 17), (75, 40, 75)), ((9,), (70,))], 721),
 }
-ALONE = ("cap", "cap-mixed")        # the further utterances are the case's only ones
+ALONE = ("cap", "cap-mixed", "pass4", "pass8", "deep")        # the further utterances are the case's only ones
 CAP_MIXED_LONG = 2                  # cap-mixed's utterance of 682 instances
 # holes' utterances have 50, 60, 12, 2 and 0 frames; words 0, 9 and 19 end in a NaN column, words 4 and 13
 # have a column of -inf.  name: (transcripts, what the scores must be)

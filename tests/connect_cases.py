@@ -39,6 +39,12 @@ Past one composite state per thread (k_connect runs 256 threads), one stream and
           passed); word 7 ergodic (state 0 does not reach its last state in one step) with det = 0 in
           state 8: its dense step meets NaN candidates.  One utterance speaks word 0; one has 2 frames:
           every healthy end is still -inf, and -inf beats NaN.
+A vocabulary for embed_cases alone (no decoder test walks it: 90 words per frame are the restatement's cost):
+  broad   K = 90 words of 3 states, banded, (M, D) = (1, 2).  NS = 270: word 85 owns the columns 255..257,
+          words 86..89 lie past 256.  Word 87 spoken twice in one utterance, word 89 (column NS - 1), a
+          21-word utterance (S = 63: one wave), T = 0 and two frames for three states; word 88 and most of
+          the words below 85 are spoken nowhere.
+  broad256  K = 350 such words, NS = 1050, and one utterance of 65 words (S = 195: 256 threads).
 Penalties: 0 and -5 on every case, -inf on every case, +3 and -1e4 on narrow."""
 import numpy as np
 
@@ -65,11 +71,16 @@ UTTS = {
               ((280, 1, 290), (5, 6, 7)), ((40,), (1,)), ((0,), (0,))],
     "cap": [((3, 17), (80, 75)), ((5,), (40,)), ((9,), (64,)), ((20,), (10,)), ((0,), (0,))],
     "ones2048": [((0, 1, 2, 3), (2, 2, 2, 2)), ((3, 4), (3, 2)), ((4,), (3,)), ((0,), (0,))],
+    "broad": [((87, 2, 87, 85), (5, 4, 5, 5)), ((89, 40, 86), (4, 5, 4)),
+              (tuple((4 * i + 1) % 84 for i in range(21)), (4,) * 21), ((0,), (0,)), ((89,), (2,))],
+    "broad256": [((343, 2, 343, 341), (5, 4, 5, 5)), ((349, 40, 342), (4, 5, 4)),
+                 (tuple((5 * i + 1) % 340 for i in range(65)), (4, 3) * 32 + (4,)), ((0,), (0,))],
     "holes": [((2, 5), (30, 20)), ((11, 3, 16), (28, 12, 20)), ((0,), (12,)), ((1,), (2,)), ((0,), (0,))],
 }
 UTTS["dup"] = UTTS["mixed"]
 SEEDS = {"narrow": 611, "mixed": 612, "wide": 613, "many": 614, "ones": 615, "dup": 612, "full": 616,
-         "thick": 811, "crowd": 812, "cap": 813, "ones2048": 815, "holes": 816}
+         "thick": 811, "crowd": 812, "cap": 813, "ones2048": 815, "holes": 816, "broad": 817,
+         "broad256": 818}
 DIAGONAL = ("narrow", "mixed", "wide", "many", "ones", "dup")
 NONTIE = ("narrow", "mixed", "wide", "many", "full")      # compared with the restatement on both tiers
 ALL = DIAGONAL + ("full",)
@@ -77,6 +88,7 @@ ALL = DIAGONAL + ("full",)
 BEYOND = ("thick", "crowd", "cap")
 FULLCOV = ("full", "holes")                                # the cases of full-covariance words
 THICK_NS, CROWD_NS, CAP_WORDS, ONES_MODELS = (7, 16, 9, 12), (2, 3, 4), 32, 5
+BROAD_WORDS = {"broad": 90, "broad256": 350}
 HOLES_NS = (8, 16, 24)
 HOLES_NAN_END, HOLES_INF, HOLES_DENSE, HOLES_DENSE_NAN = (0, 9, 19), (4, 13), 7, 8
 HOLES_UNHEALTHY = HOLES_NAN_END + HOLES_INF + (HOLES_DENSE,)
@@ -95,9 +107,9 @@ def _words(G, name, rng):
         return words
     if name == "full":
         return FV.make(G, "narrow").words
-    if name == "many":
+    if name == "many" or name in BROAD_WORDS:
         from fullcov_support import banded
-        return [[V.rand_model(G, rng, 3, 1, 2, banded(rng, 3), word=f"w{k}")] for k in range(70)]
+        return [[V.rand_model(G, rng, 3, 1, 2, banded(rng, 3), word=f"w{k}")] for k in range(BROAD_WORDS.get(name, 70))]
     if name in BEYOND + ("ones2048", "holes"):
         return _beyond(G, name, rng)
     return [[V.rand_model(G, rng, 1, 2, 3, np.ones((1, 1)), word=f"w{k}")] for k in range(3)]       # ones

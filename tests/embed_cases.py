@@ -21,7 +21,27 @@ so that the linear densities of that frame underflow:
              second pass; most of the 28 words in no transcript.
   cap        one utterance of 682 three-state instances on 2200 frames: S = 2046.
   cap-mixed  the cap's utterance among small ones and T = 0.
-SMALL are the cases the long-double restatement walks freely; cap and cap-mixed take the float64 one.
+REACH, what no case above reaches in k_embed_fwd / k_embed_bwd (launch_shape restates the host's choice of threads
+and PASSES; test_embed_host.py holds every case to its role in a coverage table):
+  broad      90 banded 3-state words, NS = 270, transcripts of at most 21 words (S <= 63: 64 threads): the columns
+             from 4 x 64 = 256 up get their tied gamma through tie_gamma's table loop.  Word 85 straddles 256,
+             word 87 (columns 261..263) is spoken twice in one utterance, word 89 owns column NS - 1, word 88 and
+             most words below 85 are in no transcript; T = 0; two frames for three states.
+  broad256   the same with 350 words (NS = 1050 > 4 x 256) and a 65-word transcript (S = 195: 256 threads).
+  pass4      thick's vocabulary; 59 instances, the ergodic words 1 and 23 recurring on 4 frames each and the
+             banded word 4 on 9: S = 791 on 261 frames, k_embed_fwd<4> / k_embed_bwd<4> with dense words in a
+             thread's third and fourth state; beside it a two-word utterance and T = 0.
+  pass8      many's vocabulary; 342 instances on 3 and 4 frames each (a banded 3-state word takes 3 frames at
+             least, so T = 1068 and not below 1000): S = 1026, <8> at a size the long-double restatement walks;
+             beside it a two-word utterance.
+  wide       align_cases' wide: S = 161, 192 threads; its last words have 64 states.
+  wide128    wide without its further utterance: S = 97, 128 threads.
+  mid        mixed + two utterances that end on its word of 17 states: log Z through group_sum<32>.
+  deep       connect_cases.cap's 32 words of 64 states (NS = 2048), (3, 5, 17) on 190 frames and (9,) on 70:
+             S = 192; log Z over a last word of 64 states (group_sum<64>, j = 63); word 5 is the off-band
+             word; the table loop on 192 threads; and the one concatenated model here whose reduction
+             launch (a block per entry of num_a) passes 2^32 threads.
+SMALL and REACH are the cases the long-double restatement walks freely; cap and cap-mixed take the float64 one.
 
 The float64 restatement's distance from the long-double one, measured by test_embed_host.test_float64_spread
 on the oracle's log b and the restated posteriors, which prints per case the worst relative distance over the
@@ -29,6 +49,10 @@ finite log P_u and log Z_u | the worst block_dist over every word's and stream's
 tied gamma, and holds the second below RTOL / 8 = 1.25e-9:
     narrow  4.8e-16 | 4.0e-11      mixed  2.6e-16 | 3.7e-11      many   6.3e-16 | 1.2e-12
     ones    3.9e-17 | 1.4e-14      short  4.8e-16 | 3.4e-12      thick  2.5e-16 | 8.5e-13
+    broad   2.6e-16 | 1.1e-13      broad256 2.5e-16 | 8.0e-13    pass4  1.3e-15 | 7.6e-12
+    pass8   6.2e-16 | 1.4e-11     wide   8.8e-16 | 6.1e-11      wide128 4.8e-16 | 1.0e-10
+    mid     2.6e-16 | 1.4e-11      deep   7.2e-16 | 1.0e-12
+(pass8 under its first seed, 720, had 7.3e-9 in a num_mu entry that cancels to 2.6e-5; the seed was changed.)
 """
 import functools
 
@@ -41,12 +65,30 @@ import logscore_ref as R
 from fullcov_support import need_extended, offsets
 
 SMALL = ("narrow", "mixed", "many", "ones", "short", "thick")
+REACH = ("broad", "broad256", "pass4", "pass8", "wide", "wide128", "mid", "deep")
 BIG = ("cap", "cap-mixed")
-ALL = SMALL + BIG
+ALL = SMALL + REACH + BIG
 FAR_CASES = ("narrow", "many")
 DELTA_CASES = ("many", "narrow")        # one narrow (3-state banded words) and one with a dense word
 DELTAS = (0, 1, 2, 3)
 COMMON = ("num_a", "den_a", "den_c")
+# the band beyond 3, per case: MAX_DELTA and one below it on one state per thread (narrow), on two with a dense
+# word in the second (thick), MAX_DELTA on four (pass4); test_embed_host holds each to a non-zero num_a at o >= 4
+MAX_DELTA = 7
+WIDE_DELTAS = {"narrow": (5, 7), "thick": (2, 7), "pass4": (7,)}
+WAVE, THREADS = 64, 256
+
+
+def launch_shape(case, transcripts=None):
+    """what the host works out of a call (vocab_embed in csrc/ghmm_lattice_host.hpp): Smax over the utterances
+    of at least one frame, the threads, PASSES and whether the vocabulary's columns go past a thread's four
+    registers into tie_gamma's table loop"""
+    transcripts = case.transcripts if transcripts is None else transcripts
+    Smax = max([AC.states_of(case, t) for t, T in zip(transcripts, case.lens) if T] + [1])
+    threads = min(THREADS, -(-Smax // WAVE) * WAVE)
+    need = -(-Smax // threads)
+    passes = next(p for p in (1, 2, 4, 8) if need <= p)
+    return {"Smax": Smax, "threads": threads, "passes": passes, "table": case.NS > 4 * threads}
 
 
 def make(G, name, far=None):

@@ -11,6 +11,13 @@ the rest for the flat grammar), with one case more:
   k256    K = 256 words of 2 and 3 states (N = (2, 3)[k % 2]), banded, (M, D) = (1, 2).  NS = 640: the cap
           on K, predecessor words up to 255 in the byte, the table read from L2, a first state in every
           thread.  Utterances of at most 20 frames: the restatement walks 256 words per frame.
+  k100    K = 100 such words, NS = 250: 256 threads, so R = 2 slices per word, and the table is still read
+          from L2: three unrolled rounds of sixteen candidates and then a tail of two (w = 96 + r, 98 + r) in
+          every slice.  Under its random grammar the traced path enters words both from a tail candidate
+          (w >= 96) and from an unrolled round (test_grammar_host.py holds the seed to it).
+  k72     K = 72 such words, NS = 180: 192 threads, R = 2, and the table IS staged (52 176 bytes): four unrolled
+          rounds of eight and then a tail of four (w >= 64) in every slice, held the same way.  (many, the
+          other staged case with rounds and a tail, has no traced entry from a tail candidate.)
 Grammars (start, pair, fin), by name:
   flat:p      pair == p, start == fin == 0: ghmm_connect_streams(p)
   random      entries in [-6, 0], about 30 % of pair -inf, some -inf in start and fin; seeded per case
@@ -35,12 +42,23 @@ K256_NS = (2, 3)
 K256_UTTS = [((255, 3, 128), (6, 5, 7)), ((200, 254, 17, 255), (5, 4, 6, 5)), ((1,), (1,)), ((77, 130), (9, 8)),
              ((0,), (0,))]
 K256_SEED = 911
+K100_UTTS = [((99, 3, 64), (6, 5, 7)), ((70, 98, 17, 99), (5, 4, 6, 5)), ((1,), (1,)), ((37, 96), (9, 8)),
+             ((97, 12, 98), (5, 6, 5)), ((0,), (0,))]
+K100_SEED = 912
+K72_UTTS = [((71, 3, 64), (6, 5, 7)), ((50, 70, 17, 65), (5, 4, 6, 5)), ((1,), (1,)), ((37, 68), (9, 8)),
+            ((69, 12, 66), (5, 6, 5)), ((0,), (0,))]
+K72_SEED = 913
+# name: (K, utterances, seed) of the cases composed here
+OWN = {"k256": (MAX_K, K256_UTTS, K256_SEED), "k100": (100, K100_UTTS, K100_SEED), "k72": (72, K72_UTTS, K72_SEED)}
+# per case the first word of grammar_entry's tail: its random grammar's traced entries come from both sides of it
+TAIL_FROM = {"k100": 96, "k72": 64}
+THREADS, WAVE, STAGE_LDS, ITEMS = 256, 64, 64 << 10, 256
 
 # the seed of every case's random grammar (chosen so that MAX_BELOW_GAP holds on the oracle's log b)
 RANDOM_SEED = {"narrow": 21, "mixed": 22, "wide": 23, "many": 24, "ones": 25, "thick": 26, "cap": 27, "k256": 28,
-               "full": 29, "holes": 30, "crowd": 31, "dup": 32}
+               "full": 29, "holes": 30, "crowd": 31, "dup": 32, "k100": 39, "k72": 66}
 # the (case, grammar) pairs that test_grammar_gpu.py compares with the restatement
-SHAPES = ("narrow", "wide", "many", "thick", "k256", "cap")
+SHAPES = ("narrow", "wide", "many", "thick", "k256", "cap", "k100", "k72")
 GPU_GRAMMARS = {name: ("random", "norepeat", "flat:-5") for name in SHAPES}
 GPU_GRAMMARS["cap"] = ("random", "norepeat")       # (the restatement walks 32 words of 64 states per frame)
 GPU_GRAMMARS["ones"] = ("norepeat", "random")
@@ -59,14 +77,15 @@ CHAINS = {
 
 
 def make(G, name):
-    """connect_cases.make's Case (k256: the case above, composed the same way)"""
-    if name != "k256":
+    """connect_cases.make's Case (k256, k100: the cases above, composed the same way)"""
+    if name not in OWN:
         return CC.make(G, name)
-    rng = np.random.default_rng(K256_SEED)
+    K, utts, seed = OWN[name]
+    rng = np.random.default_rng(seed)
     words = [[V.rand_model(G, rng, K256_NS[k % 2], 1, 2, banded(rng, K256_NS[k % 2]), word=f"w{k}")]
-             for k in range(MAX_K)]
+             for k in range(K)]
     parts, lens, spoken = [], [], []
-    for seq, seg in K256_UTTS:
+    for seq, seg in utts:
         for k, T in zip(seq, seg):
             parts.append(stream_frames(rng, words[k], [int(T)])[0])
         lens.append(int(sum(seg)))
@@ -74,6 +93,23 @@ def make(G, name):
     case = V.Case(words, [np.concatenate(parts)], lens)
     case.spoken, case.name = spoken, name
     return case
+
+
+def entry_pass(NS, K):
+    """what the host and k_grammar work out of a vocabulary (csrc/ghmm_grammar.hpp): whether the pair table is
+    staged in LDS (grammar_staged), the slices R per word, and per slice r the unrolled rounds and the tail
+    iterations of grammar_entry: (staged, R, [(rounds, tail) for r in range(R)])"""
+    staged = NS * 36 + K * 16 + ITEMS * 12 + K * K * 8 <= STAGE_LDS
+    threads = min(THREADS, -(-NS // WAVE) * WAVE)
+    R = min(4, max(1, threads // K))
+    unroll = 8 if staged else 16
+    slices = []
+    for r in range(R):
+        rounds, w = 0, r
+        while w + (unroll - 1) * R < K:
+            rounds, w = rounds + 1, w + unroll * R
+        slices.append((rounds, len(range(w, K, R))))
+    return staged, R, slices
 
 
 # ------------------------------------------------------------- grammars
@@ -255,4 +291,4 @@ def allowed(case, word, begin, score, start, pair, fin):
 
 __all__ = ["ENTRY", "GAP", "MAX_K", "MAX_BELOW_GAP", "SHAPES", "GPU_GRAMMARS", "CHAINS", "FULLCOV", "RANDOM_SEED",
            "make", "flat", "random", "norepeat", "chain", "grammar", "decode_log", "decode", "log_as", "compared",
-           "oracle_log_b", "allowed"]
+           "oracle_log_b", "allowed", "entry_pass"]

@@ -6,8 +6,9 @@ here.  Under GHMM_OPT_KERNELS = 1 and under the default (matrix-core) tier unles
 
   lattice      the long-double restatement on the DEVICE's own log b and posteriors (one stream), per word with
                estep_log_ref.block_dist at RTOL and equal zero, -inf and NaN patterns: log P, the tied gamma,
-               num_a, den_a, den_c, num_c, num_mu, num_var; delta 0, 2, 3; the cap (float64 restatement): log P,
-               every frame's gamma sum against exp(log P - log Z), den_c
+               num_a, den_a, den_c, num_c, num_mu, num_var, over embed_cases' SMALL and REACH; delta 0, 2, 3 and
+               up to 7; the table columns after a call that filled them; every frame's gamma sum against
+               exp(log P - log Z); the cap (float64 restatement): log P, the gamma sums, den_c
   emission     BUF_B bit for bit what ghmm_align_streams leaves
   identities   bit for bit under GHMM_OPT_KERNELS = 1: consequence (a) with one and two streams, a second call,
                the same call after a connect_streams on another vocabulary, loglik and n_utt in every vector,
@@ -104,7 +105,12 @@ def devices(G, ctx):
 
 
 def restated(d, r, delta=1, ft=np.longdouble):
-    return EC.estep(d.case.words, d.case.Xs, d.case.lens, d.transcripts, delta, ft, logb=r["logb"], posts=r["posts"])
+    """the restatement on a run's own log b and posteriors, computed once per run and left unchanged"""
+    key = ("restated", delta, ft)
+    if key not in r:
+        r[key] = EC.estep(d.case.words, d.case.Xs, d.case.lens, d.transcripts, delta, ft, logb=r["logb"],
+                          posts=r["posts"])
+    return r[key]
 
 
 def check_against(d, r, ref, what):
@@ -134,8 +140,11 @@ def check_against(d, r, ref, what):
 
 @extended
 @pytest.mark.parametrize("tier", TIERS)
-@pytest.mark.parametrize("name", EC.SMALL)
+@pytest.mark.parametrize("name", EC.SMALL + EC.REACH)
 def test_lattice_against_the_long_double_restatement(G, ctx, devices, name, tier):
+    """SMALL, and REACH: tie_gamma's table loop on 64, 192 and 256 threads (broad, deep, broad256), four and
+    eight states per thread (pass4, pass8), 128 and 192 threads (wide128, wide), log Z over a last word of 17
+    and of 64 states (mid, deep; the gammas are normalised by it)"""
     d = devices(name, stream0=True)
     r = d.run(tier)
     worst = check_against(d, r, restated(d, r), f"{name} tier {tier}")
@@ -148,9 +157,11 @@ def test_lattice_against_the_long_double_restatement(G, ctx, devices, name, tier
 
 @extended
 @pytest.mark.parametrize("tier", TIERS)
-@pytest.mark.parametrize("delta", [x for x in EC.DELTAS if x != 1])
-@pytest.mark.parametrize("name", EC.DELTA_CASES)
+@pytest.mark.parametrize("name,delta", [(n, x) for n in EC.DELTA_CASES for x in EC.DELTAS if x != 1] +
+                         [(n, x) for n, xs in EC.WIDE_DELTAS.items() for x in xs])
 def test_lattice_under_other_deltas(G, ctx, devices, name, delta, tier):
+    """delta 0, 2, 3 on one state per thread; the band up to MAX_DELTA = 7 on one state per thread (narrow), on
+    two with a dense word in the second pass (thick) and on four (pass4): xi[p][o] for every p and o"""
     d = devices(name, stream0=True)
     r = d.run(tier, delta)
     check_against(d, r, restated(d, r, delta), f"{name} tier {tier} delta {delta}")
@@ -158,6 +169,58 @@ def test_lattice_under_other_deltas(G, ctx, devices, name, delta, tier):
         na = r["stats"][k][0]["num_a"]
         i, j = np.indices(na.shape)
         assert not np.any(na[(j < i) | (j > i + delta)]), "num_a outside the band"
+
+
+@extended
+@pytest.mark.parametrize("tier", TIERS)
+@pytest.mark.parametrize("name", ["broad", "broad256"])
+def test_the_table_columns_after_a_call_that_filled_them(G, ctx, devices, name, tier):
+    """tie_gamma's table loop and tie_out on a workspace that is not fresh: first the same vocabulary under
+    transcripts that speak a word past the registers' end which the case leaves out, then the case.  That
+    word's gamma columns are exactly 0 and its vector is all zero but for the common tail; the rest is the
+    restatement's.  (On a fresh buffer a skipped loop leaves the zeros that are asked for.)"""
+    d = devices(name, stream0=True)
+    case = d.case
+    nt = EC.launch_shape(case)["threads"]
+    held = EC.present(case)
+    late = next(k for k in range(case.K) if k not in held and case.bo[k] >= 4 * nt)
+    early = next(k for k in range(case.K) if k not in held)
+    # (three states a word: nine frames and more take three words, fewer take the late word alone, too short or not)
+    other = [() if T == 0 else (late, early, late) if T >= 9 else (late,) for T in case.lens]
+    cols = slice(case.bo[late], case.bo[late + 1])
+    with tier_of(G, ctx, tier):
+        d.call(other)
+        stale = ctx.fetch(G.BUF_GAMMA, (d.F, d.NS))
+        assert np.all(stale[:, cols].sum(0) > 0), "the first call left nothing in the columns"
+        assert np.any(d.st[late][0].download()[:-2])
+        d.call()
+        r = d.fetch_all()
+    assert not np.any(r["gamma"][:, cols])
+    assert not np.any(r["v"][late][0][:-2]) and same(r["v"][late][0][-2:], r["v"][held[0]][0][-2:])
+    check_against(d, r, restated(d, r), f"{name} tier {tier} after other transcripts")
+
+
+@extended
+@pytest.mark.parametrize("tier", TIERS)
+@pytest.mark.parametrize("name", ["pass8", "pass4", "deep", "mid"])
+def test_every_frames_gamma_sums_to_rho(G, ctx, devices, name, tier):
+    """the identity test_lattice_at_the_cap uses, with log Z from the long-double restatement (the device's is
+    not fetched): every frame's gamma sum is exp(log P - log Z).  A log Z summed over the wrong lanes (a last
+    word of 17 or 64 states) or a state's gamma lost in a later pass shifts it"""
+    d = devices(name, stream0=True)
+    r = d.run(tier)
+    ref = restated(d, r)
+    off = offsets(d.case.lens)
+    seen = 0
+    for u in range(d.U):
+        if d.case.lens[u] == 0 or not np.isfinite(float(ref["loglik"][u])):
+            continue
+        rho = float(np.exp(ref["loglik"][u] - ref["logZ"][u]))
+        assert rho > 0
+        sums = r["gamma"][off[u]:off[u + 1]].sum(1)
+        assert np.all(np.abs(sums - rho) <= RTOL * rho), (name, u, float(np.abs(sums - rho).max() / rho))
+        seen += 1
+    assert seen >= 2
 
 
 @pytest.mark.parametrize("tier", TIERS)
@@ -186,7 +249,7 @@ def test_lattice_at_the_cap(G, ctx, devices, name, tier):
 # ------------------------------------------------------------- 2. the emission
 
 @pytest.mark.parametrize("tier", TIERS)
-@pytest.mark.parametrize("name", ["narrow", "mixed", "many"])
+@pytest.mark.parametrize("name", ["narrow", "mixed", "many", "broad", "pass4", "deep"])
 def test_log_b_is_the_alignments(G, ctx, devices, name, tier):
     d = devices(name)
     r = d.run(tier)
@@ -501,7 +564,7 @@ def test_no_utterance_gives_all_zero_vectors(G, ctx, devices):
         d._run.clear()
 
 
-@pytest.mark.parametrize("name", ["narrow", "many"])
+@pytest.mark.parametrize("name", ["narrow", "many", "broad", "pass4", "deep"])
 def test_launch_counts_and_the_workspace_afterwards(G, ctx, devices, name):
     """2 P - 1 launches under GHMM_K_EMISSION, two under GHMM_K_FORWARD, per stream ghmm_estep's statistics
     launches (vector tier: one k_mixstats, one k_reduce_all) and the scatter under GHMM_K_REDUCE"""

@@ -1,7 +1,9 @@
 """The embedded Baum-Welch E-step without a GPU: embed_cases' restatement is the definition of include/ghmm.h
 (against an enumeration of every path through the composite model), it is estep_log_ref's E-step on one-word
 transcripts, the identities the header states hold on it, its float64 form stays close to the long-double
-one, the entry point is declared, bound and built, and the cases hold what test_embed_gpu.py leans on."""
+one, the entry point is declared, bound and built, the cases hold what test_embed_gpu.py leans on, and a
+coverage table of what the host works out of every case (threads, PASSES, the table loop, the last word's size,
+the passes that own a dense word) shows which branches of the two kernels the cases reach."""
 import ctypes
 import itertools
 import os
@@ -161,7 +163,7 @@ def test_rows_of_num_a_sum_to_den_a_and_frames_to_rho(G, name):
 
 
 @extended
-@pytest.mark.parametrize("name", EC.SMALL)
+@pytest.mark.parametrize("name", EC.SMALL + EC.REACH)
 def test_float64_spread(G, name):
     """the figures of embed_cases' docstring"""
     case, ld = EC.reference(G, name)
@@ -239,3 +241,106 @@ def test_the_cases_hold_what_their_descriptions_claim(G):
     dead = [u for u, r in enumerate(ref["utt"]) if r["T"] and r["logZ"] == -np.inf]
     assert len(dead) >= 3 and all(ref["loglik"][u] == -np.inf for u in dead)
     assert any(np.isfinite(r["logZ"]) and r["T"] for r in ref["utt"])
+
+
+# ------------------------------------------------------------- what the cases reach in the two kernels
+
+TOO_SHORT = {"broad": (4,), "wide": (1,), "wide128": (1,), "mid": (2,)}       # fewer frames than states on purpose: log P = -inf
+
+
+def _dense(c, k):
+    A = np.asarray(c.words[k][0].A)
+    i, j = np.indices(A.shape)
+    return bool(np.any((A > 0) & (j != i) & (j != i + 1)))
+
+
+def reach(c):
+    """a case's row of the coverage table: EC.launch_shape's figures, the size classes of the last words (the
+    arm of k_embed_fwd's log Z sum), the passes (0-based: state s is thread s % threads' pass s // threads) in
+    which a thread owns a state of a dense word, and whether an utterance repeats a word whose columns all lie
+    past a thread's four registers (tie_gamma's table loop walks a chain of two)"""
+    row = EC.launch_shape(c)
+    nt = row["threads"]
+    live = [t for t, T in zip(c.transcripts, c.lens) if T]
+    row["last"] = {16 if c.Ns[t[-1]] <= 16 else 32 if c.Ns[t[-1]] <= 32 else 64 for t in live}
+    row["dense_pass"] = set()
+    for t in live:
+        starts = np.concatenate([[0], np.cumsum([c.Ns[k] for k in t])])
+        for i, k in enumerate(t):
+            if _dense(c, k):
+                row["dense_pass"] |= {int(s) // nt for s in range(starts[i], starts[i + 1])}
+    row["repeat_in_table"] = any(t.count(k) > 1 and c.bo[k] >= 4 * nt for t in live for k in set(t))
+    return row
+
+
+def test_the_cases_cover_the_launch_shapes_and_the_branches_behind_them(G):
+    """the coverage table: what vocab_embed works out of every case (threads = min(256, Smax rounded up to 64),
+    PASSES = ceil(Smax / threads) rounded up to 1, 2, 4, 8) and the branches that follow from it"""
+    cases = {n: EC.make(G, n) for n in EC.ALL}
+    table = {n: reach(c) for n, c in cases.items()}
+    for n, r in table.items():
+        print(f"{n:10s} Smax {r['Smax']:5d} threads {r['threads']:3d} PASSES {r['passes']} table {int(r['table'])} "
+              f"last {sorted(r['last'])} dense in passes {sorted(r['dense_pass'])} repeat in table {int(r['repeat_in_table'])}")
+    assert {r["threads"] for r in table.values()} == {64, 128, 192, 256}
+    assert {r["passes"] for r in table.values()} == {1, 2, 4, 8}
+    assert {r["threads"] for r in table.values() if r["table"]} >= {64, 256}
+    assert set().union(*(r["last"] for r in table.values())) == {16, 32, 64}
+    assert any(p >= 2 for r in table.values() for p in r["dense_pass"])
+    assert any(r["table"] and r["repeat_in_table"] for r in table.values())
+    # ... and every new case in its own role
+    for n in ("broad", "broad256"):
+        c, r = cases[n], table[n]
+        nt = r["threads"]
+        assert r["table"] and r["repeat_in_table"] and nt == (64 if n == "broad" else 256), (n, r)
+        assert c.NS >= 4 * nt + 8 and set(c.Ns) == {3}
+        held = EC.present(c)
+        assert c.K - 1 in held, "column NS - 1 is in no transcript"
+        out = [k for k in range(c.K) if k not in held]
+        assert any(c.bo[k] >= 4 * nt for k in out) and any(c.bo[k + 1] <= 4 * nt for k in out)
+        assert any(c.bo[k] < 4 * nt < c.bo[k + 1] for k in held), "no spoken word straddles the registers' end"
+        assert any(T == 0 for T in c.lens)
+    assert max(len(t) for t in cases["broad"].transcripts) <= 21
+    assert table["pass4"]["passes"] == 4 and {2, 3} <= table["pass4"]["dense_pass"]
+    assert 0 in list(cases["pass4"].lens) and any(len(t) == 2 for t in cases["pass4"].transcripts)
+    assert table["pass8"]["passes"] == 8 and 1024 < table["pass8"]["Smax"] <= 1100
+    assert max(cases["pass8"].lens) < 1100 and len(cases["pass8"].lens) == 2
+    assert table["thick"]["passes"] == 2 and 1 in table["thick"]["dense_pass"]
+    assert table["wide"]["threads"] == 192 and table["wide128"]["threads"] == 128
+    d = cases["deep"]
+    assert table["deep"]["Smax"] == 192 and table["deep"]["last"] == {64} and set(d.Ns) == {64}
+    assert any(_dense(d, k) for k in EC.present(d)), "the off-band word is in no transcript"
+    # ... and its concatenated model's reduction (a block of 1024 threads per Gaussian, per entry of num_a, per
+    # state twice, one for the tail) is the one launch here whose blocks do not fit a 32-bit count of threads
+    blocks = {n: c.NS * c.words[0][0].M + c.NS ** 2 + 2 * c.NS + 1 for n, c in cases.items()}
+    assert [n for n, b in blocks.items() if b * 1024 >= 2 ** 32] == ["deep"]
+    assert max(max(AC.states_of(c, t) for t in c.transcripts) for c in cases.values()) <= AC.MAX_S
+
+
+@pytest.mark.parametrize("name", EC.REACH)
+def test_the_new_utterances_have_finite_scores_on_the_oracles_log_b(G, name):
+    """log Z is finite in every utterance of at least one frame, log P in all but those listed as too short"""
+    case = EC.make(G, name)
+    lb = AC.oracle_log_b(case)
+    As = [w[0].A for w in case.words]
+    off = offsets(case.lens)
+    for u, (t, T) in enumerate(zip(case.transcripts, case.lens)):
+        if T == 0:
+            continue
+        r = EC.lattice(As, case.bo, lb[off[u]:off[u + 1]], t, 0, np.float64)
+        assert np.isfinite(r["logZ"]), (name, u)
+        assert np.isfinite(r["logP"]) == (u not in TOO_SHORT.get(name, ())), (name, u, float(r["logP"]))
+
+
+@pytest.mark.parametrize("name,delta", [(n, d) for n, ds in EC.WIDE_DELTAS.items() for d in ds])
+def test_the_wide_bands_are_not_empty(G, name, delta):
+    """some word of the case has a non-zero num_a at the band's last offset (and so, at delta >= 4, at an offset
+    of 4 or more): without it a run at that delta proves nothing about xi[p][o] there"""
+    assert 2 <= delta <= EC.MAX_DELTA and EC.MAX_DELTA in EC.WIDE_DELTAS[name]
+    case, ref = EC.reference(G, name, delta, np.float64)
+    far = 0
+    for k in EC.present(case):
+        na = np.asarray(ref["stats"][k][0]["num_a"])
+        i, j = np.indices(na.shape)
+        assert not np.any(na[(j < i) | (j > i + delta)])
+        far += int(np.count_nonzero(na[j == i + delta]))
+    assert far > 0, (name, delta)

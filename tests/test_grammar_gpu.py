@@ -155,7 +155,8 @@ def test_against_the_restatement(G, ctx, devices, name, t):
     """narrow (one wave, P = 3, T = 0, 1 and 2), wide (a 64-state word across waves, dense columns), many
     (K = 70: more words than a wave has lanes; the table staged in LDS), thick (two states per thread),
     k256 (the cap on K, the table read from L2, predecessor words up to 255), cap (NS = 2048, more than
-    48 KB of LDS beside the grammar), ones (a word that is its own entry and end, no repeats allowed)"""
+    48 KB of LDS beside the grammar), k100 (the table read from L2 in two slices per word, unrolled rounds
+    and then a tail), k72 (the same from the staged table, 192 threads), ones (a word that is its own entry and end, no repeats allowed)"""
     d = devices(name)
     case = d.case
     with tier(G, ctx, t):
@@ -267,7 +268,7 @@ def timed(G, ctx, call):
     return out, kt
 
 
-@pytest.mark.parametrize("name", ["narrow", "many", "full", "k256", "cap"])
+@pytest.mark.parametrize("name", ["narrow", "many", "full", "k256", "cap", "k100", "k72"])
 def test_launch_counts_and_a_second_call(G, ctx, devices, name):
     """2 P - 1 launches under GHMM_K_EMISSION (full-covariance: P, the folds are the emission's own
     epilogue) and ONE under GHMM_K_VITERBI: lattice and trace together; a second identical call repeats

@@ -4,7 +4,8 @@ equals an enumeration of ALL composite paths with their word boundaries on a tin
 bit for bit, the path under the tie rules); consequences (a), (b) and (c) of include/ghmm.h hold for it
 against connect_cases' and align_cases' restatements; bigram_log counts what a hand counts; and every
 (case, grammar) pair that the GPU tests compare keeps, on the oracle's float64 log b, the margin under
-which a differing path cannot be blamed on rounding, in all utterances but at most one.
+which a differing path cannot be blamed on rounding, in all utterances but at most one; and the forms of
+the entry pass (table staged or read from L2, slices per word, unrolled rounds, tail) that the cases reach.
 The margins are conditions on the inputs, not measurements: if a seed fails them, the seed changes, not
 the bound."""
 import itertools
@@ -225,6 +226,38 @@ def test_the_random_grammars_forbid_and_the_k256_case_is_at_the_cap(cases):
     first[off[:-1][case.lens > 0]] = True
     entered = np.nonzero((begin == 1) & ~first)[0]
     assert len(entered) and word[entered - 1].max() >= 128
+
+
+def test_the_entry_pass_is_held_in_its_forms_and_k100_and_k72_decide_in_both_loops(cases):
+    """grammar_entry per case as grammar_cases.entry_pass restates the header's formulas: the table read from
+    L2 in sixteen full rounds (k256), in a tail alone with R = 4 (cap), in rounds followed by a tail with
+    R = 2 (k100); staged in LDS with rounds and a tail (many, k72).  Under k100's and k72's random grammars
+    the traced path takes a predecessor word from the tail (w >= TAIL_FROM) and one from an unrolled round,
+    in both slices (even and odd w)"""
+    table = {}
+    for name in ("k256", "cap", "k100", "many", "k72"):
+        case = cases(name)[0]
+        table[name] = GC.entry_pass(case.NS, case.K)
+        print(name, "K", case.K, "NS", case.NS, "(staged, R, [(unrolled rounds, tail iterations) per slice])", table[name])
+    assert table["k256"] == (False, 1, [(16, 0)])
+    assert table["cap"] == (False, 4, [(0, 8)] * 4)
+    assert table["k100"] == (False, 2, [(3, 2)] * 2)
+    assert table["k72"] == (True, 2, [(4, 4)] * 2)
+    staged, R, slices = table["many"]
+    assert staged and R == 3 and all(rounds > 0 for rounds, _ in slices)
+    for name, K, NS in (("k100", 100, 250), ("k72", 72, 180)):
+        case, lb = cases(name)
+        assert case.K == K and case.NS == NS and set(case.Ns) == {2, 3} and case.lens.max() <= 20
+        word, path, begin, score, gap = GC.decode(case, lb, *GC.grammar(case, "random"))
+        off = offsets(case.lens)
+        first = np.zeros(case.F, dtype=bool)
+        first[off[:-1][case.lens > 0]] = True
+        entered = np.nonzero((begin == 1) & ~first & GC.compared(case, gap))[0]
+        pred = word[entered - 1]
+        for r in range(2):
+            mine = pred[pred % 2 == r]
+            assert (mine >= GC.TAIL_FROM[name]).any() and (mine < GC.TAIL_FROM[name]).any(), (name, r, sorted(pred.tolist()))
+    assert 200 <= cases("k100")[0].NS
 
 
 # ------------------------------------------------------------- bigram_log
