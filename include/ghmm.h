@@ -90,10 +90,18 @@ enum {
      * device's, the default): for a caller whose stream is restricted to part of the device
      * (hipExtStreamCreateWithCUMask) */
     GHMM_OPT_CUS = 6,
-    /* read-only (ghmm_ctx_get_option; synchronises the stream): utterances the last gamma / xi
-     * pass of the default tier took again in the reference's own order of operations — no path
-     * into the last state, or forward and backward mass more than 200 decades apart at some
-     * frame (ghmm_pair.hpp, RANGE).  0 on data the model fits. */
+    /* read-only (ghmm_ctx_get_option; synchronises the stream): utterances the context's last
+     * gamma / xi pass took again in the reference's own order of operations — on the default
+     * tier no path into the last state, or forward and backward mass more than 200 decades apart
+     * at some frame (ghmm_pair.hpp, RANGE); under GHMM_OPT_KERNELS = 1 a band-only beta^ that left
+     * the numbers, where a wave takes all of its utterances again when one of them asks.  0 on
+     * data the model fits.  The last pass is that of ghmm_estep, ghmm_backward, ghmm_estep_streams,
+     * ghmm_estep_full and its stream form, or the one ghmm_fetch(GHMM_BUF_BETA) starts after an
+     * E-step (it counts the same utterances).  A pass that takes nothing again by construction
+     * reads 0: a model of more than 64 states, ghmm_estep_log and the other log-domain E-steps,
+     * ghmm_estep_embed_streams, a linear E-step on a corpus of no utterances.  Calls that run no
+     * gamma / xi pass (scores, Viterbi, ghmm_forward, ghmm_model_init, the embedded E-step on a
+     * corpus of no utterances) leave the value as it is, whatever corpus they see. */
     GHMM_OPT_REFORDER_COUNT = 7,
     /* matrix-core tier, Gaussians too ill-conditioned for the expanded sums although their
      * variances are not at the floor ("class 2"): 0 (default) their direct-form sums come from

@@ -131,6 +131,7 @@ struct ghmm_ctx {
     // kernel of pass n zeroes the counter of pass n + 1)
     dev_buf<int> fix_mark, fix_list, fix_cnt;
     int fix_stamp = 0;
+    bool fix_counted = false; // the last gamma/xi pass counted in fix_cnt[fix_stamp & 1] (some keep no list)
     bool loglik_pieces = false; // log P of the last E-step is in lpart / logk, loglik[] not assembled
     int lp_nch = 0;             // chunks per utterance of those pieces
     bool own_bwd_done = false; // k_scan_pair ran the backward direction for the current alpha
@@ -550,7 +551,7 @@ extern "C" int ghmm_ctx_get_option(ghmm_ctx *ctx, int option, int64_t *value)
     case GHMM_OPT_REFORDER_COUNT: {
         int n = 0, rc = use(ctx);
         if (rc) return rc;
-        if (ctx->fix_cnt && ctx->fix_stamp > 0) {
+        if (ctx->fix_cnt && ctx->fix_counted) {
             HIP_TRY(hipMemcpyAsync(&n, ctx->fix_cnt + (ctx->fix_stamp & 1), sizeof n, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(stream_sync(ctx));
         }
@@ -1157,8 +1158,10 @@ static int ws_fb(ghmm_ctx *ctx, const ghmm_model *m, const ghmm_corpus *c)
     if ((rc = ctx->part_denc.grow(UN))) return rc;
     if ((size_t)c->U > ctx->fix_mark.cap) {
         if ((rc = ctx->fix_mark.grow((size_t)c->U))) return rc;
+        // fix_stamp stays: stamps are at least 1 and never repeat, so a zeroed mark equals none, and
+        // the counters keep their parity (pass n counts in fix_cnt[n & 1] and zeroes the other slot:
+        // starting the stamps over would hand the next pass the slot the last one counted in)
         HIP_TRY(hipMemsetAsync(ctx->fix_mark, 0, ctx->fix_mark.cap * sizeof(int), ctx->stream));
-        ctx->fix_stamp = 0; // (stamps start at 1: a zeroed mark never equals one)
     }
     if ((rc = ctx->fix_list.grow((size_t)c->U))) return rc;
     if (!ctx->fix_cnt) {
@@ -1426,11 +1429,13 @@ static int run_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool want_
 {
     if (c->U == 0) {
         ctx->slots = 0; // nothing was accumulated: every utterance sum is empty
+        ctx->fix_counted = false;
         return GHMM_OK;
     }
     int L, rc;
     if ((rc = fb_lanes(m, &L))) return rc;
     if (L == 0) {
+        ctx->fix_counted = false; // (k_backward_wide keeps the reference's order itself: no list)
         if ((rc = wide_band_flag(ctx, m->N, m->A, 0.0))) return rc;
         if ((rc = lds_attr(ctx, (const void *)k_backward_wide))) return rc; // (64 KB at 512 states)
         kscope ks(ctx, GHMM_K_BACKWARD);
@@ -1477,6 +1482,7 @@ static int run_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool want_
                 if (want_beta) GHMM_BY_LANES(L, GHMM_COMBINE(LL, true, true));
                 else GHMM_BY_LANES(L, GHMM_COMBINE(LL, false, true));
             }
+            ctx->fix_counted = true;
             if ((rc = run_backward_fix(ctx, m, c, L, blocks, CB_CH, nullptr))) return rc;
             ctx->lp_nch = CB_CH;
             ctx->beta_valid = want_beta;
@@ -1486,6 +1492,7 @@ static int run_backward(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool want_
         } else {
             if (++ctx->fix_stamp == 0x7fffffff) ctx->fix_stamp = 1; // (no marks on this tier: a wave lists each of its utterances once)
             int *cnt = ctx->fix_cnt + (ctx->fix_stamp & 1);
+            ctx->fix_counted = true;
             GHMM_BY_LANES(L, hipLaunchKernelGGL(k_backward<LL>, dim3(blocks), dim3(WAVE), 0, ctx->stream, m->N, c->U,
                                                 (int)ctx->delta, m->A, ctx->b, c->off, ctx->alpha, ctx->scale,
                                                 ctx->sinv, ctx->beta, ctx->gamma, ctx->part_xi, ctx->part_dena,
@@ -1538,6 +1545,7 @@ static int run_scan_combine(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, bool *
                                             c->order, ctx->fix_cnt + (ctx->fix_stamp & 1),
                                             ctx->fix_cnt + ((ctx->fix_stamp + 1) & 1)));
     }
+    ctx->fix_counted = true;
     if ((rc = launch_ok("k_scan_combine"))) return rc;
     ctx->lp_nch = nch;
     ctx->beta_valid = false; // beta^ on demand (ghmm_fetch)
@@ -2588,6 +2596,7 @@ extern "C" int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models
     ctx->N = v.NS;
     ctx->G = v.NS * v.cats[0]->M;
     ctx->embed_ws = true;
+    ctx->fix_counted = false; // (the word lattice runs in the log domain: no utterance is taken again)
     std::vector<embed_dst> dst((size_t)n_models * P);
     for (int p = 0; p < P; p++) {
         int bo = 0;
@@ -2735,6 +2744,7 @@ static int run_log_lattice(ghmm_ctx *ctx, int N, const double *logA, ghmm_corpus
     }
     ctx->slots = c->U; // one partial per utterance
     ctx->loglik_pieces = false;
+    ctx->fix_counted = false; // (no utterance is taken again in the log domain)
     return GHMM_OK;
 }
 
