@@ -99,7 +99,8 @@ enum {
      * ghmm_estep_full and its stream form, or the one ghmm_fetch(GHMM_BUF_BETA) starts after an
      * E-step (it counts the same utterances).  A pass that takes nothing again by construction
      * reads 0: a model of more than 64 states, ghmm_estep_log and the other log-domain E-steps,
-     * ghmm_estep_embed_streams, a linear E-step on a corpus of no utterances.  Calls that run no
+     * ghmm_estep_embed_streams and ghmm_estep_embed_full_streams, a linear E-step on a corpus of no
+     * utterances.  Calls that run no
      * gamma / xi pass (scores, Viterbi, ghmm_forward, ghmm_model_init, the embedded E-step on a
      * corpus of no utterances) leave the value as it is, whatever corpus they see. */
     GHMM_OPT_REFORDER_COUNT = 7,
@@ -693,8 +694,8 @@ int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
  * word of more than 64 states, S_u > 2048 on an utterance with T > 0, an empty transcript with T > 0, a
  * word outside the vocabulary, ...; both transcript arrays are needed when U > 0); GHMM_ERR_ARG for a
  * null stats array or entry, a vector that is not word k's stream-p shape, or a full-covariance one.
- * Full-covariance words are not taken (the lattice, csrc/ghmm_embed.hpp, sees only log b[F][NS] and the
- * words' table, so such an entry point can follow).
+ * Full-covariance words go through ghmm_estep_embed_full_streams (below): the same lattice, which sees
+ * only log b[F][NS] and the words' table (csrc/ghmm_embed.hpp).
  * 2 n_streams - 1 launches under GHMM_K_EMISSION; TWO under GHMM_K_FORWARD (the lattice forwards and
  * backwards, one workgroup per utterance); per stream ghmm_estep's statistics launches on the
  * concatenated vocabulary under GHMM_K_MIXSTATS and GHMM_K_REDUCE, and one more under GHMM_K_REDUCE that
@@ -1042,6 +1043,45 @@ int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_mod
                             ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
                             const int32_t *seq_off, int32_t *word_host, int32_t *path_host,
                             int32_t *begin_host, double *score_host);
+/* ghmm_estep_embed_streams (above) for full-covariance words: the same definition word for word (the la /
+ * lbe / w / wi recursions, LSE2 only at the entries and exits, the tying over instances in ascending
+ * order, den_a built on stay, the log Z_u normaliser, the T = 0 and U = 0 rules), with these differences.
+ * models[k * n_streams + p] are ghmm_fmodels; stats[k * n_streams + p] is a ghmm_stats_create_full vector
+ * of word k's stream-p shape, OVERWRITTEN, so that ghmm_mstep_full and ghmm_mstep_full_dev on it work
+ * unchanged.  log b and the posteriors are ghmm_estep_full_streams(log_domain = 1)'s: one emission launch
+ * per stream over the concatenated vocabulary, every later stream folded in by the launch's own epilogue;
+ * column bo_k + i of log b holds, bit for bit, what ghmm_align_full_streams leaves there.
+ *   num_c / num_mu / num_cov of stream p: calc_mix_param on w = gamma_t(k,j) * post^p_t(k,j,m), gamma tied,
+ *                     by ghmm_estep_full's statistics launches on the concatenated model (frames whose
+ *                     weights are all exactly 0, as in the columns of words an utterance does not hold,
+ *                     add exactly nothing and are skipped)
+ * Consequences:
+ *   (a) with n_models == 1 and one-word transcripts, stats[p], GHMM_BUF_GAMMA, GHMM_BUF_LOGLIK, GHMM_BUF_B
+ *       and (n_streams == 1) GHMM_BUF_POST are ghmm_estep_full_streams(log_domain = 1)'s on the same
+ *       context and options, bit for bit;
+ *   (b) with one-word transcripts and any vocabulary, word k's sums are those of the sub-corpus of its
+ *       utterances, to rounding;
+ *   (c) a transcript (k, k) gives word k the sum of what two separate copies of the word would get.
+ * Asynchronous on the context's stream; a second identical call repeats every byte; GHMM_OPT_DELTA is
+ * honoured; GHMM_OPT_REFORDER_COUNT reads 0.  Afterwards GHMM_BUF_B holds log b[F][NS], GHMM_BUF_GAMMA the
+ * tied gamma[F][NS], GHMM_BUF_LOGLIK log P_u; GHMM_BUF_POST is served for n_streams == 1 and refused
+ * beyond; GHMM_BUF_ALPHA, _BETA and _SCALE give GHMM_ERR_ARG.  A vector's mailbox is not written:
+ * ghmm_stats_loglik copies and waits.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_align_full_streams refuses
+ * (GHMM_OPT_ROBUST set, a word outside the vocabulary, S_u > 2048 on an utterance with T > 0, an empty
+ * transcript with T > 0, ...; both transcript arrays are needed when U > 0); GHMM_ERR_ARG for a null stats
+ * array or entry, a vector that is not word k's stream-p full-covariance shape, or a diagonal one;
+ * GHMM_ERR_UNSUPPORTED for a concatenated vocabulary whose NS * M_p * (1 + D_p + D_p (D_p + 1) / 2) sums
+ * are more batches of 2048 than the statistics launch's grid takes.  U = 0 zeroes every vector and
+ * launches nothing.
+ * Per stream one gather and ONE launch under GHMM_K_EMISSION (the fold is the emission's epilogue); TWO
+ * launches under GHMM_K_FORWARD; per stream one under GHMM_K_MIXSTATS and TWO brackets under GHMM_K_REDUCE:
+ * ghmm_estep_full's reductions (k_fullstats_reduce and k_reduce_all, timed and counted as one, as in
+ * every full-covariance E-step) and the scatter that hands every word its own blocks
+ * (k_embed_scatter_full, csrc/ghmm_embed.hpp). */
+int ghmm_estep_embed_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                  ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
+                                  const int32_t *seq_off, ghmm_stats *const *stats);
 
 /* -------------------------------------- several GPUs: the one collective */
 

@@ -438,4 +438,32 @@ k_embed_scatter(int NS, int M, int D, const double *__restrict__ cat, const embe
     if (tid < 2) d_tail[tid] = s_tail[tid];
 }
 
+// The same for the full-covariance layout (num_cov: the upper triangle, D (D + 1) / 2 per Gaussian), over a
+// grid of (word, chunk): word k's Gaussians are contiguous in the concatenated num_c, num_mu and num_cov, so
+// each of the three is one range, and the chunks of a word share every range between them (a 64-state word's
+// num_cov is tens of thousands of doubles: not one block's loop).  Plain loads and stores, every element
+// written by exactly one thread.
+constexpr int EMBED_SCATTER_PER_BLOCK = 1024; // doubles a chunk moves at the largest word (the host's grid)
+__global__ void __launch_bounds__(256)
+k_embed_scatter_full(int NS, int M, int D, const double *__restrict__ cat, const embed_dst *__restrict__ dst)
+{
+    const embed_dst e = dst[blockIdx.x];
+    const int N = e.N, bo = e.bo;
+    const size_t q0 = (size_t)blockIdx.y * blockDim.x + threadIdx.x, step = (size_t)gridDim.y * blockDim.x;
+    const size_t DT = (size_t)D * (D + 1) / 2, GS = (size_t)NS * M, G = (size_t)N * M, g0 = (size_t)bo * M;
+    const double *s_na = cat, *s_da = s_na + (size_t)NS * NS, *s_dc = s_da + NS, *s_nc = s_dc + NS;
+    const double *s_mu = s_nc + GS, *s_cov = s_mu + GS * D, *s_tail = s_cov + GS * DT;
+    double *d_na = e.v, *d_da = d_na + (size_t)N * N, *d_dc = d_da + N, *d_nc = d_dc + N;
+    double *d_mu = d_nc + G, *d_cov = d_mu + G * D, *d_tail = d_cov + G * DT;
+    for (size_t q = q0; q < (size_t)N * N; q += step) d_na[q] = s_na[(bo + q / N) * NS + bo + q % N];
+    for (size_t q = q0; q < (size_t)N; q += step) {
+        d_da[q] = s_da[bo + q];
+        d_dc[q] = s_dc[bo + q];
+    }
+    for (size_t q = q0; q < G; q += step) d_nc[q] = s_nc[g0 + q];
+    for (size_t q = q0; q < G * D; q += step) d_mu[q] = s_mu[g0 * D + q];
+    for (size_t q = q0; q < G * DT; q += step) d_cov[q] = s_cov[g0 * DT + q];
+    if (q0 < 2) d_tail[q0] = s_tail[q0];
+}
+
 } // namespace ghmm

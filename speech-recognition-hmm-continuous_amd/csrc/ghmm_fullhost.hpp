@@ -251,8 +251,9 @@ extern "C" int ghmm_score_full(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, d
 // cat_slot) with every word's Gaussians of that stream gathered into it by one launch, and the
 // vocabulary's b or log b in the workspace: one emission launch per stream over its concatenated
 // vocabulary, stream 0 plain, every later stream folded into the same b[F][NS].  The FOLD epilogue is per
-// state, so column bo_k + i holds what emission_full_streams leaves in column i for word k alone.  The
-// launch that follows writes bt_ll.
+// state, so column bo_k + i holds what emission_full_streams leaves in column i for word k alone.  Under
+// FC_LOGPOST (the embedded E-step) the same launches also write the mixture posteriors, the table holds
+// log A as under FC_LOG.  The launch that follows writes bt_ll.
 static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models, ghmm_corpus *const *corpora, int P,
                         bool have_dest, int mode, const char *what, vocab_pass *v)
 {
@@ -264,7 +265,9 @@ static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
     const ghmm_corpus *c = corpora[0];
     if ((rc = ctx->bt_ll.grow((size_t)n_models * c->U))) return rc;
     const fgather_src *dsrc;
-    rc = vocab_tables<fgather_src>(ctx, models, n_models, P, mode == FC_LOG, [](const ghmm_fmodel *m, int g0) {
+    const bool want_post = mode == FC_POST || mode == FC_LOGPOST;
+    rc = vocab_tables<fgather_src>(ctx, models, n_models, P, mode == FC_LOG || mode == FC_LOGPOST,
+                                   [](const ghmm_fmodel *m, int g0) {
         return fgather_src{m->c, m->mean, m->inv_cov, m->den, m->lk, g0, m->N * m->M};
     }, v, &dsrc);
     if (rc) return rc;
@@ -279,8 +282,16 @@ static int fvocab_begin(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
         if ((rc = launch_ok("k_gather_fmodels"))) return rc;
     }
     if ((rc = ws_full(ctx, v->NS, models[0]->M, c))) return rc;
+    // the posteriors of a mode that writes them: one stream's into the workspace's own buffer, which
+    // ghmm_fetch serves, several streams' into post_s[p] (as ghmm_estep_full_streams keeps them)
+    for (int p = 0; want_post && p < P; p++) {
+        dev_buf<double> &post = P == 1 ? ctx->post : ctx->post_s[p];
+        if ((rc = post.grow((size_t)c->F * v->NS * models[p]->M))) return rc;
+    }
     for (int p = 0; p < P; p++)
-        if ((rc = run_emission_full(ctx, ctx->fbt_cat[p], corpora[p], mode, p > 0))) return rc;
+        if ((rc = run_emission_full(ctx, ctx->fbt_cat[p], corpora[p], mode, p > 0,
+                                    want_post && P > 1 ? ctx->post_s[p].p : nullptr)))
+            return rc;
     return GHMM_OK;
 }
 
@@ -457,7 +468,10 @@ static int run_fullstats(ghmm_ctx *ctx, ghmm_fmodel *fm, ghmm_corpus *c, ghmm_st
         s->mbox_expect = ra.mbox_seq;
         s->mbox_mark = ctx->launch_mark;
         s->mbox_valid = ra.mbox != nullptr;
-        hipLaunchKernelGGL(k_reduce_all, dim3((unsigned)(N * N + 2 * N + 1)), dim3(RD_THREADS), 0, ctx->stream, ra);
+        // (reduce_grid: at the embedded E-step's concatenated N = 2048 the blocks times RD_THREADS pass
+        // 2^32 work-items along x; a single word's grid, N <= 64, is the one-row grid it always was)
+        hipLaunchKernelGGL(k_reduce_all, reduce_grid((long long)N * N + 2 * N + 1), dim3(RD_THREADS), 0, ctx->stream,
+                           ra);
     }
     return launch_ok("k_reduce_all");
 }
@@ -865,4 +879,76 @@ extern "C" int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models
         (rc = fvocab_begin(ctx, models, n_models, corpora, P, have_dest, FC_LOG, __func__, &v)))
         return rc;
     return vocab_align(ctx, v, corpora[0], pl, seq, seq_off, word_host, path_host, begin_host, score_host);
+}
+
+// ------------------------------------------------ embedded Baum-Welch on word transcripts
+// ghmm_estep_embed_full_streams (definition in include/ghmm.h): ghmm_estep_embed_streams for
+// full-covariance words.  fvocab_begin's gathers and its emission launches under FC_LOGPOST (log b and
+// every stream's posteriors, the folds in the launches' epilogue), the lattice over the transcripts' word
+// instances (embed_lattice: it sees log b[F][NS] and the words' table), run_fullstats once per stream on
+// the CONCATENATED model into a vector of the context's, and one scatter per stream of every word's blocks
+// into its own vector (k_embed_scatter_full).
+
+// k_fullstats puts its batches of FS_THREADS * FS_EPT elements on gridDim.y: whether the concatenated
+// model of NS states has more batches than the device takes there.  Nothing is launched here.
+static int fullstats_extent_check(ghmm_ctx *ctx, int NS, int M, int D, int p, const char *what)
+{
+    int max_y = 0;
+    HIP_TRY(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, ctx->device));
+    const long long E = (long long)NS * M * fs_elems(D);
+    const long long NB = (E + FS_THREADS * FS_EPT - 1) / (FS_THREADS * FS_EPT);
+    if (NB > max_y) {
+        ghmm_set_error("%s: stream %d: %d states of %d Gaussians of %d coefficients are %lld batches of statistics, "
+                       "the launch takes %d", what, p, NS, M, D, NB, max_y);
+        return GHMM_ERR_UNSUPPORTED;
+    }
+    return GHMM_OK;
+}
+
+extern "C" int ghmm_estep_embed_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                             ghmm_corpus *const *corpora, int P, const int32_t *seq,
+                                             const int32_t *seq_off, ghmm_stats *const *stats)
+{
+    vocab_pass v;
+    align_plan pl;
+    // as in ghmm_align_full_streams: the vocabulary checks once ahead of fvocab_begin's own, the other
+    // refusals need the words' states and come before anything is launched
+    int rc = use(ctx);
+    if (rc) return rc;
+    rc = vocab_checks(models, n_models, corpora, P, seq && seq_off, __func__,
+                      [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); }, &v);
+    if (rc) return rc;
+    ARG_CHECK(stats, "null statistics");
+    for (int k = 0; k < n_models * P; k++)
+        if ((rc = check_stats_full(models[k], stats[k]))) return rc;
+    ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return embed_empty(ctx, stats, n_models * P);
+    if ((rc = align_check(models, n_models, P, c, v, seq, seq_off, __func__, &pl))) return rc;
+    for (int p = 0; p < P; p++)
+        if ((rc = fullstats_extent_check(ctx, v.NS, models[p]->M, models[p]->D, p, __func__))) return rc;
+    if ((rc = fvocab_begin(ctx, models, n_models, corpora, P, true, FC_LOGPOST, __func__, &v))) return rc;
+    const embed_dst *ddst;
+    if ((rc = embed_lattice(ctx, models, n_models, P, models[0]->M, c, v, pl, seq, seq_off, stats, &ddst))) return rc;
+    for (int p = 0; p < P; p++) {
+        ghmm_fmodel *cat = ctx->fbt_cat[p];
+        ghmm_stats cs; // the concatenated model's vector: the context's, without a mailbox
+        cs.N = cat->N; cs.M = cat->M; cs.D = cat->D;
+        cs.full = true;
+        cs.n = ghmm_stats_len_full(cat->N, cat->M, cat->D);
+        if ((rc = ctx->em_vec[p].grow(cs.n))) return rc;
+        cs.v = ctx->em_vec[p];
+        if ((rc = run_fullstats(ctx, cat, corpora[p], &cs, P == 1 ? ctx->post : ctx->post_s[p]))) return rc;
+        {
+            // the chunks of the largest word at this stream's shape (every range is shared between them)
+            const size_t most = ghmm_stats_len_full(v.Nmax, cat->M, cat->D);
+            const int ch = (int)std::min<size_t>(1024, (most + EMBED_SCATTER_PER_BLOCK - 1) / EMBED_SCATTER_PER_BLOCK);
+            kscope ks(ctx, GHMM_K_REDUCE);
+            hipLaunchKernelGGL(k_embed_scatter_full, dim3((unsigned)n_models, (unsigned)ch), dim3(256), 0, ctx->stream,
+                               cat->N, cat->M, cat->D, (const double *)cs.v, ddst + (size_t)p * n_models);
+        }
+        if ((rc = launch_ok("k_embed_scatter_full"))) return rc;
+        // (the words' vectors are not k_reduce_all's: its mailbox does not describe them)
+        for (int k = 0; k < n_models; k++) stats[(size_t)k * P + p]->mbox_valid = false;
+    }
+    return GHMM_OK;
 }

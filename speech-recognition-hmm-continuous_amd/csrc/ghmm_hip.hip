@@ -171,10 +171,11 @@ struct ghmm_ctx {
     // word) [F][K]; its back-pointers and words per frame go through cn_psi and cn_word
     dev_buf<double> gr_tab;
     dev_buf<unsigned char> gr_entw;
-    // ghmm_estep_embed_streams (k_embed_fwd / k_embed_bwd): the composite la rows (ragged: S_u doubles per
-    // frame), the blocks' column-head tables [U][NS], and stream p's statistics of the concatenated model,
-    // from which k_embed_scatter fills the words' vectors.  embed_ws: the workspace holds that call's
-    // results, so alpha, beta and c_t are nobody's (ghmm_fetch refuses them); cleared by ws_full
+    // ghmm_estep_embed_streams / _full_streams (k_embed_fwd / k_embed_bwd): the composite la rows (ragged: S_u
+    // doubles per frame), the blocks' column-head tables [U][NS], and stream p's statistics of the concatenated
+    // model in its kind's layout, from which k_embed_scatter / k_embed_scatter_full fills the words' vectors.
+    // embed_ws: the workspace holds that call's results, so alpha, beta and c_t are nobody's (ghmm_fetch
+    // refuses them); cleared by ws_full
     dev_buf<double> em_la;
     dev_buf<int> em_head;
     dev_buf<double> em_vec[GHMM_MAX_STREAMS];
@@ -2565,13 +2566,7 @@ extern "C" int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models
     for (int k = 0; k < n_models * P; k++)
         if ((rc = check_stats(models[k], stats[k]))) return rc;
     ghmm_corpus *c = corpora[0];
-    if (c->U == 0) { // no utterance: every sum is empty, loglik and n_utt are 0
-        for (int k = 0; k < n_models * P; k++) {
-            stats[k]->mbox_valid = false;
-            HIP_TRY(hipMemsetAsync(stats[k]->v, 0, stats[k]->n * 8, ctx->stream));
-        }
-        return GHMM_OK;
-    }
+    if (c->U == 0) return embed_empty(ctx, stats, n_models * P);
     if ((rc = align_check(models, n_models, P, c, v, seq, seq_off, __func__, &pl))) return rc;
     if ((rc = vocab_gather(ctx, models, n_models, P, true, &v))) return rc;
     const size_t F = (size_t)c->F, FN = F * v.NS;
@@ -2587,27 +2582,8 @@ extern "C" int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models
             return rc;
         if (p > 0 && FN && (rc = fold_stream(ctx, FN, true))) return rc;
     }
-    // the workspace belongs to the concatenated vocabulary: the row API does not reuse it, and what an
-    // earlier pass left in alpha, beta and c_t goes with nothing here
-    ws_disown(ctx);
-    ctx->em_c = c;
-    ctx->b_is_log = true;
-    ctx->post_valid = P == 1;
-    ctx->N = v.NS;
-    ctx->G = v.NS * v.cats[0]->M;
-    ctx->embed_ws = true;
-    ctx->fix_counted = false; // (the word lattice runs in the log domain: no utterance is taken again)
-    std::vector<embed_dst> dst((size_t)n_models * P);
-    for (int p = 0; p < P; p++) {
-        int bo = 0;
-        for (int k = 0; k < n_models; k++) {
-            const ghmm_model *m = models[(size_t)k * P + p];
-            dst[(size_t)p * n_models + k] = {stats[(size_t)k * P + p]->v, m->N, bo};
-            bo += m->N;
-        }
-    }
     const embed_dst *ddst;
-    if ((rc = vocab_embed(ctx, v, c, pl, seq, seq_off, dst.data(), dst.size(), &ddst))) return rc;
+    if ((rc = embed_lattice(ctx, models, n_models, P, v.cats[0]->M, c, v, pl, seq, seq_off, stats, &ddst))) return rc;
     for (int p = 0; p < P; p++) {
         ghmm_model *cat = v.cats[p];
         ghmm_stats cs; // the concatenated model's vector: the context's, without a mailbox

@@ -526,7 +526,8 @@ static int vocab_align(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c,
 // ahead of the launches on the same stream, then k_embed_fwd (la rows into em_la, log P_u into loglik,
 // log Z_u into logk) and k_embed_bwd (the tied gamma[F][NS] and one partial per utterance for a model of
 // NS states, as run_log_lattice leaves them for the statistics launches).  Both launches count under
-// GHMM_K_FORWARD.  Nothing waits.  Called by ghmm_estep_embed_streams; it knows no kind of Gaussian.
+// GHMM_K_FORWARD.  Nothing waits.  Called by embed_lattice (below) for ghmm_estep_embed_streams and
+// ghmm_estep_embed_full_streams; it knows no kind of Gaussian.
 static int vocab_embed(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c, const align_plan &pl,
                        const int32_t *seq, const int32_t *seq_off, const embed_dst *dst, size_t n_dst,
                        const embed_dst **ddst)
@@ -585,4 +586,45 @@ static int vocab_embed(ghmm_ctx *ctx, const vocab_pass &v, const ghmm_corpus *c,
     ctx->slots = c->U; // one partial per utterance
     ctx->loglik_pieces = false;
     return GHMM_OK;
+}
+
+// An embedded E-step on a corpus of no utterances: every sum is empty, loglik and n_utt are 0.  Called by
+// the embedded E-steps of both kinds, behind their checks.
+static int embed_empty(ghmm_ctx *ctx, ghmm_stats *const *stats, int n)
+{
+    for (int k = 0; k < n; k++) {
+        stats[k]->mbox_valid = false;
+        HIP_TRY(hipMemsetAsync(stats[k]->v, 0, stats[k]->n * 8, ctx->stream));
+    }
+    return GHMM_OK;
+}
+
+// An embedded E-step between its emission launches and its statistics launches, the same for both kinds
+// of Gaussian (M0 = stream 0's mixtures): the workspace's bookkeeping, the scatter's table (stream p's
+// n_models entries from (*ddst)[p * n_models]: word k's vector, states and first column) and the lattice.
+template <class Model>
+static int embed_lattice(ghmm_ctx *ctx, Model *const *models, int n_models, int P, int M0, const ghmm_corpus *c,
+                         const vocab_pass &v, const align_plan &pl, const int32_t *seq, const int32_t *seq_off,
+                         ghmm_stats *const *stats, const embed_dst **ddst)
+{
+    // the workspace belongs to the concatenated vocabulary: the row API does not reuse it, and what an
+    // earlier pass left in alpha, beta and c_t goes with nothing here
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = true;
+    ctx->post_valid = P == 1;
+    ctx->N = v.NS;
+    ctx->G = v.NS * M0;
+    ctx->embed_ws = true;
+    ctx->fix_counted = false; // (the word lattice runs in the log domain: no utterance is taken again)
+    std::vector<embed_dst> dst((size_t)n_models * P);
+    for (int p = 0; p < P; p++) {
+        int bo = 0;
+        for (int k = 0; k < n_models; k++) {
+            const Model *m = models[(size_t)k * P + p];
+            dst[(size_t)p * n_models + k] = {stats[(size_t)k * P + p]->v, m->N, bo};
+            bo += m->N;
+        }
+    }
+    return vocab_embed(ctx, v, c, pl, seq, seq_off, dst.data(), dst.size(), ddst);
 }

@@ -121,6 +121,8 @@ SYMBOLS = {
                                            C.POINTER(_vp)], True),
     "ghmm_align_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip,
                                           _ip, _dp], True),
+    "ghmm_estep_embed_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
+                                                C.POINTER(_vp)], True),
     "ghmm_logscore": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp], True),
     "ghmm_logscore_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, C.c_int, _dp], True),
     "ghmm_logscore_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _dp], True),
@@ -890,22 +892,28 @@ class Context:
         """align_streams for full-covariance words"""
         return self._align(self.lib.ghmm_align_full_streams, vocab, corpora, transcripts)
 
-    def estep_embed_streams(self, vocab, corpora, transcripts, stats):
-        """the embedded Baum-Welch E-step: forward-backward over every utterance's transcript
-        (transcripts[u] = the sequence of its words' indices into vocab), gamma and xi tied over the
-        instances of a word; stats[k][p] (word k's stream-p shape) is overwritten, so that
-        mstep(vocab[k][p], stats[k][p]) follows.  Asynchronous; every vector carries the summed log P
-        and the utterance count.  fetch(BUF_GAMMA, (frames, NS)) is the tied gamma"""
+    def _estep_embed(self, fn, vocab, corpora, transcripts, stats):
         U = corpora[0].n_utt
         if len(transcripts) != U:
             raise ValueError(f"{len(transcripts)} transcripts for {U} utterances")
         seq_off = np.zeros(U + 1, dtype=np.int32)
         seq_off[1:] = np.cumsum([len(t) for t in transcripts])
         seq = np.array([k for t in transcripts for k in t] + [0], dtype=np.int32)     # (never of size 0)
-        _check(self.lib.ghmm_estep_embed_streams(self.h, self._vocab_handles(vocab), len(vocab),
-                                                 self._stream_handles(corpora), len(corpora),
-                                                 seq.ctypes.data_as(_ip), seq_off.ctypes.data_as(_ip),
-                                                 self._vocab_handles(stats)), self.lib)
+        _check(fn(self.h, self._vocab_handles(vocab), len(vocab), self._stream_handles(corpora), len(corpora),
+                  seq.ctypes.data_as(_ip), seq_off.ctypes.data_as(_ip), self._vocab_handles(stats)), self.lib)
+
+    def estep_embed_streams(self, vocab, corpora, transcripts, stats):
+        """the embedded Baum-Welch E-step: forward-backward over every utterance's transcript
+        (transcripts[u] = the sequence of its words' indices into vocab), gamma and xi tied over the
+        instances of a word; stats[k][p] (word k's stream-p shape) is overwritten, so that
+        mstep(vocab[k][p], stats[k][p]) follows.  Asynchronous; every vector carries the summed log P
+        and the utterance count.  fetch(BUF_GAMMA, (frames, NS)) is the tied gamma"""
+        self._estep_embed(self.lib.ghmm_estep_embed_streams, vocab, corpora, transcripts, stats)
+
+    def estep_embed_full_streams(self, vocab, corpora, transcripts, stats):
+        """estep_embed_streams for full-covariance words: stats[k][p] is a stats_full vector of word k's
+        stream-p shape, so that mstep_full or mstep_full_dev(vocab[k][p], stats[k][p]) follows"""
+        self._estep_embed(self.lib.ghmm_estep_embed_full_streams, vocab, corpora, transcripts, stats)
 
     # ---- the forward score of diagonal models in the log domain
     def logscore(self, model, corpus, final_state=False):
