@@ -703,6 +703,71 @@ int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
 int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
                              ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
                              const int32_t *seq_off, ghmm_stats *const *stats);
+/* Word posteriors under a word-pair grammar: how far to trust each word that ghmm_connect_grammar_streams
+ * decodes, and the utterance's total likelihood under the grammar (n_streams >= 1; diagonal models; the
+ * reference has no such call).  One log-domain forward-backward over the lattice of
+ * ghmm_connect_grammar_streams: its max becomes a log-sum-exp, and a backward pass follows.  The vocabulary,
+ * the corpora, K = n_models, start[K], pair[K*K] and fin[K] are that call's (a null start or fin means all 0;
+ * -inf forbids).  On the vocabulary's log b[F][NS], in that call's notation; LSE as at ghmm_logscore; a term
+ * whose log a or grammar score is -inf is not a term; an LSE over no terms is -inf; LSE2 is
+ * ghmm_estep_embed_streams':
+ *   la_0(k,j)   = (j == 0 ? start[k] : -inf) + log b_{k,j}(0)
+ *   in_t(k,j)   = LSE_{i : a_ij > 0} (la_{t-1}(k,i) + log a^k_ij)            ghmm_estep_log's step inside word k
+ *   x_t(k)      = LSE_{w : pair[w][k] > -inf} (la_{t-1}(w, N_w-1) + pair[w][k])
+ *   la_t(k,0)   = LSE2(in_t(k,0), x_t(k)) + log b_{k,0}(t);   la_t(k,j) = in_t(k,j) + log b_{k,j}(t), j > 0
+ *   log P_u     = LSE_{k : fin[k] > -inf} (la_{T-1}(k, N_k-1) + fin[k])
+ *   lbe_{T-1}(k,j) = (j == N_k-1 ? fin[k] : -inf)
+ *   w_t(k,j)    = log b_{k,j}(t+1) + lbe_{t+1}(k,j)
+ *   wi_t(k,j)   = LSE_{j' : a_jj' > 0} (log a^k_jj' + w_t(k,j'))
+ *   y_t(k)      = LSE_{k' : pair[k][k'] > -inf} (pair[k][k'] + w_t(k',0))
+ *   lbe_t(k,j)  = (j == N_k-1) ? LSE2(wi_t(k,j), y_t(k)) : wi_t(k,j)
+ *   gamma_t(k,j) = exp((la_t(k,j) + lbe_t(k,j)) - log P_u)                    GHMM_BUF_GAMMA [F][NS]
+ *   occ_t(k)    = sum_j gamma_t(k,j), j ascending                             occ_host[F*K]
+ *   ent_0(k)    = gamma_0(k,0)
+ *   ent_t(k)    = exp(((x_t(k) + log b_{k,0}(t)) + lbe_t(k,0)) - log P_u)     ent_host[F*K], may be null
+ * A NaN term makes its LSE NaN.  Inside a word the steps are ghmm_estep_embed_streams' (the banded two-term
+ * form or the dense one, chosen per word).  The order of the terms inside x_t, y_t and log P_u is NOT pinned
+ * to the bit: any reduction tree is allowed (the library keeps a running maximum and a sum scaled by it), and
+ * the results are pinned by tolerance against a long-double restatement (tests/gpost_cases.py).
+ *   occ_host[F*K]  occ_t(k): the posterior that frame t lies in word k.  The mean of occ over the frames of a
+ *                  decoded word instance is that word's confidence
+ *   ent_host[F*K]  ent_t(k): the posterior that an instance of word k BEGINS at frame t; its sum over (t, k)
+ *                  is the expected number of words.  May be null: not copied then
+ *   loglik_host[U] log P_u, the total over every word string that the grammar allows; two grammars on the
+ *                  same audio compare by it
+ * Where log P_u is not finite (no allowed string fits in T frames, a NaN column, a grammar that forbids
+ * everything) the utterance's gamma, occ and ent rows are 0 and loglik_host[u] is that value.  T = 0 gives
+ * log P = 0 and writes no rows.  U = 0 touches nothing.  A second identical call repeats every byte.
+ * Consequences:
+ *   (a) with K = 1, pair = -inf and start = fin = 0, log P_u is ghmm_logscore_streams(final_state = 1)'s, to
+ *       rounding;
+ *   (b) under the chain grammar of a transcript of pairwise distinct words (consequence (b) of
+ *       ghmm_connect_grammar_streams), log P_u is ghmm_estep_embed_streams' GHMM_BUF_LOGLIK for that
+ *       transcript, to rounding, and that call's tied gamma equals this gamma times exp(log P_u - log Z_u);
+ *   (c) log P_u >= ghmm_connect_grammar_streams' score of the same call, to rounding: the sum holds the best
+ *       path;
+ *   (d) at every frame of an utterance with finite log P_u, sum_k occ_t(k) = 1, and sum_k ent_0(k) = 1, to
+ *       rounding;
+ *   (e) a word that no allowed string can hold (start[k] and its whole column of pair -inf: it cannot be
+ *       entered; or its whole row of pair and fin[k] -inf: it cannot be left) has occ == 0 exactly.
+ * Afterwards GHMM_BUF_B holds log b[F][NS], GHMM_BUF_GAMMA gamma[F][NS], GHMM_BUF_LOGLIK log P_u;
+ * GHMM_BUF_ALPHA, _BETA and _SCALE give GHMM_ERR_ARG as after ghmm_estep_embed_streams, and GHMM_BUF_POST
+ * as well (the emission is the decoder's: it writes no posteriors); the row API does not reuse any of these
+ * buffers.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_connect_grammar_streams
+ * refuses (K > GHMM_GRAMMAR_MAX_WORDS, more than 2048 states in the vocabulary, a word of more than 64
+ * states, GHMM_OPT_ROBUST with n_streams > 1, a null pair when U > 0, a NaN or +inf anywhere in start, pair
+ * or fin); GHMM_ERR_ARG for a null occ_host or loglik_host when U > 0.
+ * The vocabulary layout, the gathers, the emission launches and folds are ghmm_connect_grammar_streams':
+ * 2 n_streams - 1 launches under GHMM_K_EMISSION; the grammar and a transposed copy of pair travel to the
+ * device on the context's stream; then TWO launches under GHMM_K_FORWARD (the lattice forwards and
+ * backwards, one workgroup per utterance, csrc/ghmm_gpost.hpp); one wait for the stream per output copied.
+ * Full-covariance words go through ghmm_grammar_post_full_streams (below): the same lattice, which sees
+ * only log b[F][NS] and the words' table. */
+int ghmm_grammar_post_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                              ghmm_corpus *const *corpora, int n_streams, const double *start,
+                              const double *pair, const double *fin, double *occ_host,
+                              double *ent_host, double *loglik_host);
 /* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
  * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
  * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are
@@ -1082,6 +1147,14 @@ int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_mod
 int ghmm_estep_embed_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                   ghmm_corpus *const *corpora, int n_streams, const int32_t *seq,
                                   const int32_t *seq_off, ghmm_stats *const *stats);
+/* ghmm_grammar_post_streams (above) for full-covariance words: the same definition, outputs, grammar arrays,
+ * edge cases, consequences and refusals, on ghmm_recognise_full_streams' log b[F][NS] (n_streams launches
+ * under GHMM_K_EMISSION, the folds being the emission's own epilogue, two under GHMM_K_FORWARD, one wait for
+ * the stream).  GHMM_OPT_ROBUST set is refused as in ghmm_connect_grammar_full_streams. */
+int ghmm_grammar_post_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                   ghmm_corpus *const *corpora, int n_streams, const double *start,
+                                   const double *pair, const double *fin, double *occ_host,
+                                   double *ent_host, double *loglik_host);
 
 /* -------------------------------------- several GPUs: the one collective */
 

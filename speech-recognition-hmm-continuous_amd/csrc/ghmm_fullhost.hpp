@@ -860,6 +860,25 @@ extern "C" int ghmm_connect_grammar_full_streams(ghmm_ctx *ctx, ghmm_fmodel *con
                                  score_host);
 }
 
+extern "C" int ghmm_grammar_post_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
+                                              ghmm_corpus *const *corpora, int P, const double *start,
+                                              const double *pair, const double *fin, double *occ_host,
+                                              double *ent_host, double *loglik_host)
+{
+    vocab_pass v;
+    const bool have_dest = occ_host && loglik_host;
+    // as in ghmm_connect_grammar_full_streams: the vocabulary checks once ahead of fvocab_begin's own, the
+    // lattice's refusals need NS and come before anything is launched
+    int rc = use(ctx);
+    if (rc) return rc;
+    rc = vocab_checks(models, n_models, corpora, P, have_dest, __func__,
+                      [ctx](const ghmm_fmodel *fm, const ghmm_corpus *c) { return check_full(ctx, fm, c); }, &v);
+    if (rc || (rc = grammar_check(v, n_models, corpora[0]->U, start, pair, fin, __func__))) return rc;
+    rc = fvocab_begin(ctx, models, n_models, corpora, P, have_dest, FC_LOG, __func__, &v);
+    if (rc || corpora[0]->U == 0) return rc;
+    return vocab_grammar_post(ctx, v, n_models, corpora[0], start, pair, fin, occ_host, ent_host, loglik_host);
+}
+
 extern "C" int ghmm_align_full_streams(ghmm_ctx *ctx, ghmm_fmodel *const *models, int n_models,
                                        ghmm_corpus *const *corpora, int P, const int32_t *seq,
                                        const int32_t *seq_off, int32_t *word_host, int32_t *path_host,

@@ -27,6 +27,7 @@
 #include "ghmm_grammar.hpp"
 #include "ghmm_align.hpp"
 #include "ghmm_embed.hpp"
+#include "ghmm_gpost.hpp"
 #include "ghmm_fullcov.hpp"
 
 extern "C" void ghmm_set_error(const char *fmt, ...); // ghmm_io.c
@@ -180,6 +181,10 @@ struct ghmm_ctx {
     dev_buf<int> em_head;
     dev_buf<double> em_vec[GHMM_MAX_STREAMS];
     bool embed_ws = false;
+    // ghmm_grammar_post_streams / _full_streams (k_gpost_fwd / k_gpost_bwd): x_t(k), occ and ent, [F][K] each;
+    // the la rows [F][NS] go through em_la, the grammar and its transposed table through gr_tab, and the
+    // workspace is marked as the embedded E-step's (embed_ws)
+    dev_buf<double> gp_x, gp_occ, gp_ent;
 
     // ---- several feature streams: the stream being evaluated (b^p) and every stream's posteriors
     dev_buf<double> b_stream;
@@ -2529,6 +2534,21 @@ extern "C" int ghmm_connect_grammar_streams(ghmm_ctx *ctx, ghmm_model *const *mo
     if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
     return vocab_connect_grammar(ctx, v, n_models, corpora[0], start, pair, fin, word_host, path_host, begin_host,
                                  score_host);
+}
+
+extern "C" int ghmm_grammar_post_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                         ghmm_corpus *const *corpora, int P, const double *start,
+                                         const double *pair, const double *fin, double *occ_host,
+                                         double *ent_host, double *loglik_host)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, occ_host && loglik_host, true, __func__, &v)) ||
+        (rc = grammar_check(v, n_models, corpora[0]->U, start, pair, fin, __func__)))
+        return rc;
+    if (corpora[0]->U == 0) return GHMM_OK;
+    if ((rc = dvocab_begin(ctx, models, n_models, corpora, P, 2, &v))) return rc;
+    return vocab_grammar_post(ctx, v, n_models, corpora[0], start, pair, fin, occ_host, ent_host, loglik_host);
 }
 
 extern "C" int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,

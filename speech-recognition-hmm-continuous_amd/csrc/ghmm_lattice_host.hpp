@@ -408,6 +408,81 @@ static int vocab_connect_grammar(ghmm_ctx *ctx, const vocab_pass &v, int K, cons
     return GHMM_OK;
 }
 
+// The word posteriors under a grammar behind their emission launches (U > 0, grammar_check passed): the
+// grammar as vocab_connect_grammar uploads it and behind it a TRANSPOSED copy of the table (start[K] |
+// pair[K][K] | fin[K] | pairT[K][K], pairT[k' * K + k] = pair[k][k']: the backward launch reduces along the
+// table's rows, ghmm_gpost.hpp says why it reads a copy) into the context's gr_tab ahead of the launches on
+// the same stream; then k_gpost_fwd (la rows [F][NS] into em_la, x rows [F][K] into gp_x, log P_u into loglik)
+// and k_gpost_bwd (gamma[F][NS], occ and ent [F][K] into gp_occ and gp_ent), one workgroup per utterance
+// each, both under GHMM_K_FORWARD; then log P, occ and (if asked for) ent to the host.  The workspace's
+// bookkeeping is embed_lattice's: it belongs to the concatenated vocabulary, holds log b, gamma and log P,
+// and alpha, beta and c_t are nobody's.  Waits for the stream.  Called by ghmm_grammar_post_streams and
+// ghmm_grammar_post_full_streams; it knows no kind of Gaussian.
+static int vocab_grammar_post(ghmm_ctx *ctx, const vocab_pass &v, int K, const ghmm_corpus *c, const double *start,
+                              const double *pair, const double *fin, double *occ_host, double *ent_host,
+                              double *loglik_host)
+{
+    int rc;
+    const size_t KK = (size_t)K * K, F = (size_t)c->F, NS = (size_t)v.NS, FK = F * K;
+    if ((rc = ctx->em_la.grow(F * NS + 1)) || (rc = ctx->gamma.grow(F * NS)) || (rc = ctx->gp_x.grow(FK + 1)) ||
+        (rc = ctx->gp_occ.grow(FK + 1)) || (rc = ctx->gp_ent.grow(FK + 1)) ||
+        (rc = ctx->gr_tab.grow(2 * KK + 2 * (size_t)K)))
+        return rc;
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = true;
+    ctx->N = v.NS;
+    ctx->embed_ws = true;
+    ctx->fix_counted = false;
+    // (pageable sources: the copies complete before the calls return them)
+    double *dstart = ctx->gr_tab, *dpair = dstart + K, *dfin = dpair + KK, *dpairT = dfin + K;
+    std::vector<double> pairT(KK);
+    for (int w = 0; w < K; w++)
+        for (int k = 0; k < K; k++) pairT[(size_t)k * K + w] = pair[(size_t)w * K + k];
+    if (start) HIP_TRY(hipMemcpyAsync(dstart, start, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(hipMemsetAsync(dstart, 0, (size_t)K * 8, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dpair, pair, KK * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (fin) HIP_TRY(hipMemcpyAsync(dfin, fin, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(hipMemsetAsync(dfin, 0, (size_t)K * 8, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dpairT, pairT.data(), KK * 8, hipMemcpyHostToDevice, ctx->stream));
+    const size_t base_f = gpost_fwd_lds_base(v.NS, K), base_b = gpost_bwd_lds_base(v.NS, K);
+    const size_t lds_f = gpost_lds(base_f, K), lds_b = gpost_lds(base_b, K);
+    const int threads = std::min(GPOST_THREADS, ((v.NS + WAVE - 1) / WAVE) * WAVE);
+    const int passes = (v.NS + threads - 1) / threads;
+#define GHMM_GPOST_FWD(PS)                                                                                         \
+    do {                                                                                                           \
+        if (lds_f > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_gpost_fwd<PS>))) return rc;                 \
+        kscope ks(ctx, GHMM_K_FORWARD);                                                                            \
+        hipLaunchKernelGGL(k_gpost_fwd<PS>, dim3((unsigned)c->U), dim3((unsigned)threads), lds_f, ctx->stream, c->U, \
+                           K, v.NS, v.dtab, (const double *)ctx->b, c->off, (const double *)ctx->gr_tab.p,         \
+                           (int)gpost_staged(base_f, K), ctx->em_la, ctx->gp_x, ctx->loglik, c->order);            \
+    } while (0)
+    if (passes <= 1) GHMM_GPOST_FWD(1);
+    else if (passes <= 2) GHMM_GPOST_FWD(2);
+    else if (passes <= 4) GHMM_GPOST_FWD(4);
+    else GHMM_GPOST_FWD(8);
+#undef GHMM_GPOST_FWD
+    if ((rc = launch_ok("k_gpost_fwd"))) return rc;
+#define GHMM_GPOST_BWD(PS)                                                                                         \
+    do {                                                                                                           \
+        if (lds_b > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_gpost_bwd<PS>))) return rc;                 \
+        kscope ks(ctx, GHMM_K_FORWARD);                                                                            \
+        hipLaunchKernelGGL(k_gpost_bwd<PS>, dim3((unsigned)c->U), dim3((unsigned)threads), lds_b, ctx->stream, c->U, \
+                           K, v.NS, v.dtab, (const double *)ctx->b, c->off, (const double *)ctx->gr_tab.p,         \
+                           (int)gpost_staged(base_b, K), (const double *)ctx->em_la, (const double *)ctx->gp_x,    \
+                           (const double *)ctx->loglik, ctx->gamma, ctx->gp_occ, ctx->gp_ent, c->order);           \
+    } while (0)
+    if (passes <= 1) GHMM_GPOST_BWD(1);
+    else if (passes <= 2) GHMM_GPOST_BWD(2);
+    else if (passes <= 4) GHMM_GPOST_BWD(4);
+    else GHMM_GPOST_BWD(8);
+#undef GHMM_GPOST_BWD
+    if ((rc = launch_ok("k_gpost_bwd"))) return rc;
+    HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (ent_host && (rc = d2h_pageable(ctx, ent_host, ctx->gp_ent, FK * 8))) return rc;
+    return d2h_pageable(ctx, occ_host, ctx->gp_occ, FK * 8);
+}
+
 // ------------------------------------------------ forced alignment
 
 // What align_check works out of a call's transcripts for vocab_align: the utterances' back-pointer

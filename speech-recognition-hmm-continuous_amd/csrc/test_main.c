@@ -51,6 +51,13 @@
  * error that names it; the output file's first line says forced alignment, then one line per utterance,
  * also on stdout: feature_file : word first last  word first last ... : score (frames counted inside the
  * utterance).  Together with GHMM_CONNECTED=1 it is refused.  Without the variable nothing changes.
+ * With GHMM_CONFIDENCE=1 beside GHMM_CONNECTED=1 (with or without GHMM_GRAMMAR) every decoded word carries its
+ * confidence, the mean over its frames of the posterior that the frame lies in that word
+ * (ghmm_grammar_post_streams / ghmm_grammar_post_full_streams under the decoder's grammar; without a grammar
+ * file the flat grammar pair == GHMM_WORD_PENALTY, start == fin == 0): name(0.93), and the line ends with the
+ * Viterbi score and then log P, the utterance's total over every string the grammar allows.  The output
+ * file's first line says that confidences are on.  GHMM_CONFIDENCE without GHMM_CONNECTED=1 or with
+ * GHMM_ALIGN=1: a message and exit 1 before any file is read.  Without the variable nothing changes.
  */
 #include "ghmm.h"
 
@@ -128,7 +135,9 @@ static FILE *f_out;
  * utterance decoded as a word string; one line per utterance to stdout and the output file.
  * GHMM_ALIGN=1 (seq_off != NULL): every utterance aligned with its transcript seq[seq_off[u] .. seq_off[u+1])
  * instead, the line holding every word instance's first and last frame.
- * GHMM_GRAMMAR (gram != NULL): start[K] | pair[K][K] | fin[K], the penalty already added to pair */
+ * GHMM_GRAMMAR (gram != NULL): start[K] | pair[K][K] | fin[K], the penalty already added to pair.
+ * GHMM_CONFIDENCE (confidence != 0, decoding only): the word posteriors under the same grammar (none: the
+ * flat one, pair == penalty), every word printed with its mean occ, the line closed by the score and log P */
 #ifdef GHMM_FULL_COV
 typedef ghmm_host_fmodel host_model_t;
 typedef ghmm_fmodel dev_model_t;
@@ -138,7 +147,7 @@ typedef ghmm_model dev_model_t;
 #endif
 static void run_connected(const host_model_t *hm, int word_number, int P, double *const *X, const int32_t *len,
                           int n_utt, const int *D, double penalty, char *const *utt_name, const int32_t *seq,
-                          const int32_t *seq_off, const double *gram)
+                          const int32_t *seq_off, const double *gram, int confidence)
 {
     int rc;
     size_t F = 0;
@@ -181,6 +190,25 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
                  : ghmm_connect_streams(ctx, flat, word_number, corpus, P, penalty, wd, st, bg, sc);
 #endif
     if (rc) die(seq_off ? "alignment" : "decoding", rc);
+    double *occ = NULL, *ll = NULL;
+    if (confidence) {
+        const size_t Kw = (size_t)word_number;
+        double *flat_pair = NULL;
+        occ = (double *)malloc((F ? F : 1) * Kw * sizeof(double));
+        ll = (double *)malloc((size_t)n_utt * sizeof(double));
+        if (!gram && (flat_pair = (double *)malloc(Kw * Kw * sizeof(double))))
+            for (size_t i = 0; i < Kw * Kw; i++) flat_pair[i] = penalty;
+        if (!occ || !ll || (!gram && !flat_pair)) die("memory", GHMM_ERR_ALLOC);
+#ifdef GHMM_FULL_COV
+        rc = ghmm_grammar_post_full_streams(ctx, flat, word_number, corpus, P, gram, gram ? gram + Kw : flat_pair,
+                                            gram ? gram + Kw + Kw * Kw : NULL, occ, NULL, ll);
+#else
+        rc = ghmm_grammar_post_streams(ctx, flat, word_number, corpus, P, gram, gram ? gram + Kw : flat_pair,
+                                       gram ? gram + Kw + Kw * Kw : NULL, occ, NULL, ll);
+#endif
+        if (rc) die("word posteriors", rc);
+        free(flat_pair);
+    }
     size_t f = 0;
     for (int u = 0; u < n_utt; u++) {
         FILE *to[2] = {stdout, f_out};
@@ -189,15 +217,22 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
             for (int t = 0, n = 0; t < len[u]; t++) {
                 if (!bg[f + t]) continue;
                 const char *name = hm[(size_t)wd[f + t] * GHMM_MAX_STREAMS].word;
-                if (!seq_off) {
+                if (!seq_off && !confidence) {
                     fprintf(to[o], " %s", name);
                     continue;
                 }
                 int last = t;
                 while (last + 1 < len[u] && !bg[f + last + 1]) last++;
+                if (confidence) {
+                    double sum = 0.0;
+                    for (int q = t; q <= last; q++) sum += occ[(f + q) * (size_t)word_number + wd[f + t]];
+                    fprintf(to[o], " %s(%.2f)", name, sum / (last - t + 1));
+                    continue;
+                }
                 fprintf(to[o], "%s %s %d %d", n++ ? " " : "", name, t, last);
             }
-            fprintf(to[o], " : %f\n", sc[u]);
+            if (confidence) fprintf(to[o], " : %f %f\n", sc[u], ll[u]);
+            else fprintf(to[o], " : %f\n", sc[u]);
         }
         f += (size_t)len[u];
     }
@@ -209,7 +244,7 @@ static void run_connected(const host_model_t *hm, int word_number, int P, double
 #endif
     for (int p = 0; p < P; p++) ghmm_corpus_destroy(ctx, corpus[p]);
     ghmm_ctx_destroy(ctx);
-    free(flat); free(wd); free(sc);
+    free(flat); free(wd); free(sc); free(occ); free(ll);
 }
 
 /* GHMM_GRAMMAR: the file's K into *K_out and its start[K] | pair[K][K] | fin[K] as one array; a file that
@@ -291,6 +326,12 @@ int main(int argc, char **argv)
     }
     const char *env_al = getenv("GHMM_ALIGN");
     const int align = env_al && strcmp(env_al, "1") == 0;
+    const char *env_conf = getenv("GHMM_CONFIDENCE");
+    const int confidence = env_conf && strcmp(env_conf, "1") == 0;
+    if (confidence && (!connected || align)) {
+        printf("GHMM_CONFIDENCE takes GHMM_CONNECTED=1%s \n", align ? ", not GHMM_ALIGN=1" : "");
+        exit(1);
+    }
     if (align && connected) {
         printf("GHMM_ALIGN=1 and GHMM_CONNECTED=1 exclude each other \n");
         exit(1);
@@ -482,10 +523,10 @@ int main(int argc, char **argv)
         if (!seq && !(seq = (int32_t *)calloc(1, sizeof(int32_t)))) die("memory", GHMM_ERR_ALLOC);
 #ifdef GHMM_FULL_COV
         fprintf(f_out, "Forced alignment using Continuous HMM (full covariance matrix): Viterbi over every utterance's transcript \n");
-        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL);
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL, 0);
 #else
         fprintf(f_out, "Forced alignment using Continuous HMM (diagonal covariance matrix): Viterbi over every utterance's transcript \n");
-        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL);
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], 0.0, utt_name, seq, seq_off, NULL, 0);
 #endif
         if (ferror(f_out) || fclose(f_out) != 0) {
             printf("writing error on file %s \n", output_file);
@@ -496,13 +537,17 @@ int main(int argc, char **argv)
     }
     if (connected) {
 #ifdef GHMM_FULL_COV
-        if (gram) fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g, grammar %s \n", word_penalty, env_gram);
-        else fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram);
+        fprintf(f_out, "Connected word recognition using Continuous HMM (full covariance matrix): Viterbi over the vocabulary, word penalty %g", word_penalty);
+        if (gram) fprintf(f_out, ", grammar %s", env_gram);
+        if (confidence) fprintf(f_out, ", word confidences (mean frame posterior), then the score and log P");
+        fprintf(f_out, " \n");
+        if (n_utt > 0) run_connected(fhm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram, confidence);
 #else
-        if (gram) fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g, grammar %s \n", word_penalty, env_gram);
-        else fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g \n", word_penalty);
-        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram);
+        fprintf(f_out, "Connected word recognition using Continuous HMM (diagonal covariance matrix): Viterbi over the vocabulary, word penalty %g", word_penalty);
+        if (gram) fprintf(f_out, ", grammar %s", env_gram);
+        if (confidence) fprintf(f_out, ", word confidences (mean frame posterior), then the score and log P");
+        fprintf(f_out, " \n");
+        if (n_utt > 0) run_connected(hm[0], word_number, Pj[0], X[0], len[0], n_utt, D[0], word_penalty, utt_name, NULL, NULL, gram, confidence);
 #endif
         if (ferror(f_out) || fclose(f_out) != 0) {
             printf("writing error on file %s \n", output_file);

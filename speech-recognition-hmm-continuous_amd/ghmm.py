@@ -115,6 +115,10 @@ SYMBOLS = {
                                                _ip, _ip, _ip, _dp], True),
     "ghmm_connect_grammar_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp,
                                                     _dp, _ip, _ip, _ip, _dp], True),
+    "ghmm_grammar_post_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp, _dp,
+                                            _dp, _dp, _dp], True),
+    "ghmm_grammar_post_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp,
+                                                 _dp, _dp, _dp, _dp], True),
     "ghmm_align_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip, _ip,
                                      _dp], True),
     "ghmm_estep_embed_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
@@ -549,6 +553,27 @@ def word_segments(word, begin, lens):
     return out
 
 
+def word_confidence(segments, occ, lens):
+    """A confidence per decoded word: segments = word_segments(word, begin, lens) of a connected-word decoding,
+    occ[F, K] = grammar_post_streams' frame posteriors of the same corpus and grammar.  Per utterance the list
+    of (word, first, last, confidence), confidence = the mean of occ[f0 + first .. f0 + last, word] with f0 the
+    utterance's first frame: the average posterior that the instance's frames lie in its word."""
+    occ = np.asarray(occ)
+    if len(segments) != len(lens):
+        raise ValueError(f"{len(segments)} segment lists for {len(lens)} utterances")
+    out, f0 = [], 0
+    for segs, T in zip(segments, lens):
+        T = int(T)
+        row = []
+        for k, a, b in segs:
+            if not 0 <= a <= b < T:
+                raise ValueError(f"segment ({k}, {a}, {b}) outside an utterance of {T} frames")
+            row.append((int(k), int(a), int(b), float(occ[f0 + a:f0 + b + 1, k].mean())))
+        out.append(row)
+        f0 += T
+    return out
+
+
 def bigram_log(transcripts, n_words, alpha=1.0):
     """A word-pair grammar for connect_grammar_streams estimated from transcripts (sequences of word
     indices below n_words; empty ones are skipped): (start[K], pair[K, K], fin[K]) in natural logs, K =
@@ -866,6 +891,37 @@ class Context:
     def connect_grammar_full_streams(self, vocab, corpora, pair, start=None, fin=None):
         """connect_grammar_streams for full-covariance words"""
         return self._connect_grammar(self.lib.ghmm_connect_grammar_full_streams, vocab, corpora, pair, start, fin)
+
+    def _grammar_post(self, fn, vocab, corpora, pair, start, fin, entries):
+        K, F = len(vocab), corpora[0].frames
+        pair = np.ascontiguousarray(pair, dtype=np.float64)
+        if pair.shape != (K, K):
+            raise ValueError(f"pair has shape {pair.shape}, the vocabulary has {K} words")
+        rows = []
+        for name, a in (("start", start), ("fin", fin)):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            if a is not None and a.shape != (K,):
+                raise ValueError(f"{name} has shape {a.shape}, the vocabulary has {K} words")
+            rows.append(a)
+        occ = np.empty((F, K), dtype=np.float64)
+        ent = np.empty((F, K), dtype=np.float64) if entries else None
+        loglik = np.empty(corpora[0].n_utt, dtype=np.float64)
+        _check(fn(self.h, self._vocab_handles(vocab), K, self._stream_handles(corpora), len(corpora), _d(rows[0]),
+                  _d(pair), _d(rows[1]), _d(occ), _d(ent), _d(loglik)), self.lib)
+        return (occ, ent, loglik) if entries else (occ, loglik)
+
+    def grammar_post_streams(self, vocab, corpora, pair, start=None, fin=None, entries=False):
+        """word posteriors under connect_grammar_streams' grammar, by a log-domain forward-backward over its
+        lattice: (occ[F, K], loglik[U]), occ[f, k] = the posterior that frame f lies in word k, loglik[u] =
+        log P of utterance u summed over every word string the grammar allows; with entries (occ, ent,
+        loglik), ent[f, k] = the posterior that an instance of word k begins at frame f.  An utterance whose
+        log P is not finite has zero rows.  word_confidence turns occ into a confidence per decoded word;
+        fetch(BUF_GAMMA, (frames, NS)) is the posterior per composite state"""
+        return self._grammar_post(self.lib.ghmm_grammar_post_streams, vocab, corpora, pair, start, fin, entries)
+
+    def grammar_post_full_streams(self, vocab, corpora, pair, start=None, fin=None, entries=False):
+        """grammar_post_streams for full-covariance words"""
+        return self._grammar_post(self.lib.ghmm_grammar_post_full_streams, vocab, corpora, pair, start, fin, entries)
 
     def _align(self, fn, vocab, corpora, transcripts):
         F, U = corpora[0].frames, corpora[0].n_utt
