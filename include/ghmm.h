@@ -304,6 +304,39 @@ int ghmm_estep(ghmm_ctx *ctx, ghmm_model *m, ghmm_corpus *c, ghmm_stats *stats);
  * is an ordinary value (sqrt(1e-320) = 1e-160).  det == 0: wk = +inf and logwk = +inf; det == inf: wk = 0
  * and logwk = -inf; NaN det: NaN both: the next emission carries them as the reference's calc_gaus would. */
 int ghmm_mstep(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *stats);
+/* The extended Baum-Welch (EBW) update of discriminative (MMI) training, on the device, in place, asynchronous
+ * (diagonal models; the reference has no such call).  `num` holds the numerator statistics (the transcripts':
+ * ghmm_estep_embed_streams, ghmm_estep_log, ...) and `den` the denominator statistics (every word string the
+ * grammar allows: ghmm_estep_grammar_streams), both possibly all-reduced, both of m's shape.  m must be the
+ * model BOTH vectors were accumulated on: num_var is taken around the old mean (see ghmm_stats).
+ * Per Gaussian g = (i, m) and coefficient d, with mu = mean, s2 = 1 / inv_var, cn = num.num_c[g],
+ * cd = den.num_c[g]:
+ *   dc     = cn - cd
+ *   dm_d   = (num.num_mu - den.num_mu)[g,d] - dc * mu_d          the first moment around the old mean
+ *   dv_d   = (num.num_var - den.num_var)[g,d]                    the second moment around the old mean
+ *   r_d    = the larger real root of q_d(x) = s2_d x^2 + (dv_d + s2_d dc) x + (dv_d dc - dm_d^2), 0 if negative
+ *   damp   = max(E * cd, 2 * max_d r_d)
+ *   mu'_d  = mu_d + dm_d / (dc + damp)
+ *   s2'_d  = (dv_d + damp s2_d) / (dc + damp) - (mu'_d - mu_d)^2, then floored at 1e-5 as ghmm_mstep floors
+ * (dc + damp)^2 s2'_d = q_d(damp), and q_d(-dc) = -dm_d^2 <= 0, so -dc does not lie beyond the larger root:
+ * for damp beyond it both dc + damp and q_d(damp) are positive, and s2'_d > 0 before the floor.  (The
+ * discriminant of q_d is (dv_d - s2_d dc)^2 + 4 s2_d dm_d^2 >= 0: the roots are always real, and it is formed so.)
+ * A Gaussian whose dc + damp is not a positive finite number (no statistics at all) keeps its mean, its
+ * variances and its det.  The sums inside a Gaussian run in index order; the divisions are correctly rounded;
+ * the results are pinned by tolerance against a long-double restatement (tests/ebw_cases.py), not to the bit.
+ * Weights and transitions come from the NUMERATOR alone, by ghmm_mstep's expressions, band mask, floors and
+ * quirks, bit for bit what ghmm_mstep(m, num) gives: a = num.num_a / num.den_a inside i <= j <= i +
+ * GHMM_OPT_DELTA and 0 outside, a row with den_a == 0 kept; c = num.num_c / num.den_c through
+ * changing_zero_coef, a state with num.den_c == 0 keeping its weights (floored and renormalised all the same).
+ * Unlike ghmm_mstep a state with num.den_c == 0 does NOT have its variance slot inverted again: its Gaussians
+ * follow the rule above like any other.  det = the product of the new variances in index order; den, wk, logwk
+ * and log a by ghmm_mstep's expressions.  The model's band flag becomes `was banded && delta <= 1`.
+ * Afterwards the model is prepared as after ghmm_model_set (a new epoch, the matrix-core form), so the next
+ * emission on either kernel tier sees it.  There is no acoustic or grammar scale and no I-smoothing: E is the
+ * only constant.  ONE launch under GHMM_K_MSTEP (k_mstep_ebw, block = state), then the preparation's.
+ * GHMM_ERR_ARG, before anything is launched or written: a null argument, a vector of another shape, a
+ * full-covariance vector, E negative, NaN or infinite. */
+int ghmm_mstep_ebw(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *num, ghmm_stats *den, double E);
 /* Forward-algorithm score per utterance (RF:354-366): emission without
  * posteriors + the forward recursion + log P.  Synchronises, writes loglik[U] on the host.
  * (Only log P is kept: alpha^ and c_t stay in registers; ghmm_forward leaves them in the workspace.) */
@@ -768,6 +801,61 @@ int ghmm_grammar_post_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_mo
                               ghmm_corpus *const *corpora, int n_streams, const double *start,
                               const double *pair, const double *fin, double *occ_host,
                               double *ent_host, double *loglik_host);
+/* Baum-Welch statistics on the grammar lattice: the E-step over EVERY word string that the grammar allows
+ * (n_streams >= 1; diagonal models; the reference has no such call).  These are the denominator occupancies of
+ * discriminative training (ghmm_mstep_ebw takes them), and on their own EM on untranscribed or loosely
+ * transcribed audio under a grammar.  The vocabulary, the corpora and start, pair, fin are
+ * ghmm_grammar_post_streams'; stats[k * n_streams + p] is ghmm_estep_embed_streams' layout (a ghmm_stats_create
+ * vector of word k's stream-p shape) and is OVERWRITTEN.  la, lbe, w, wi, x, y, log P_u and gamma are exactly
+ * ghmm_grammar_post_streams' definition, its allowance on the order of the terms inside x_t, y_t and log P_u
+ * included.  Added, for t < T-1, a_jj' > 0 and j <= j' <= j + GHMM_OPT_DELTA:
+ *   xi_t(k;j,j')    = exp(((la_t(k,j) + log a^k_jj') + w_t(k,j')) - log P_u)
+ *   stay_t(k,j)     = exp((la_t(k,j) + wi_t(k,j)) - log P_u)
+ *   num_a[k][j][j'] = sum_u sum_{t<T-1} xi_t(k;j,j')
+ *   den_a[k][j]     = sum_u sum_{t<T-1} stay_t(k,j)
+ *   den_c[k][j]     = sum_u sum_{t<T}   gamma_t(k,j)
+ *   num_c / num_mu / num_var of stream p: calc_mix_param on w = gamma_t(k,j) * post^p_t(k,j,m),
+ *                     ghmm_estep_log's posteriors
+ *   loglik = sum_u log P_u and n_utt = U: the same bits in EVERY stats[k * n_streams + p]
+ * over the utterances in ghmm_estep_log's order (one partial per utterance).  There is one copy of each word
+ * in this lattice: nothing is tied.  The normaliser is log P_u, THIS lattice's total over every allowed word
+ * string; it is NOT ghmm_estep_embed_streams' log Z_u (the LSE over the last instance's states), so the two
+ * calls' vectors differ by exp(log Z_u - log P_u) per utterance even where their lattices coincide ((b) below).
+ * den_a is built on stay for the reason given at ghmm_estep_embed_streams: the exit into another word has no
+ * parameter and receives no xi.
+ * Where log P_u is not finite the utterance adds nothing but its log P_u to loglik and 1 to n_utt, and its
+ * gamma rows are 0; so that "nothing" holds of the mixture sums as well (a column whose log b is NaN has NaN
+ * posteriors, and 0 x NaN is NaN), its rows of the mixture posteriors are set to 0 too, in every stream:
+ * GHMM_BUF_POST shows them so.  T = 0 adds 0 to loglik and counts in n_utt.  T = 1 gives den_c only.  U = 0 gives all-zero
+ * vectors.
+ * Consequences:
+ *   (a) on the same context GHMM_BUF_LOGLIK and GHMM_BUF_GAMMA are ghmm_grammar_post_streams', bit for bit
+ *       under GHMM_OPT_KERNELS = 1 (the emission with posteriors gives the bits of log b that the emission
+ *       without them gives on that tier, and the lattice arithmetic is the same code), to rounding otherwise;
+ *   (b) under the chain grammar of a transcript of pairwise distinct words and a one-utterance corpus, every
+ *       block of every word's vector equals ghmm_estep_embed_streams' for that transcript times
+ *       exp(log Z_u - log P_u), to rounding; that factor is the reciprocal of a frame's sum of that call's tied
+ *       gamma.  loglik is equal to rounding;
+ *   (c) wherever the band holds every a_jj' > 0, sum_j' num_a[k][j][j'] = den_a[k][j] to rounding;
+ *   (d) sum_k sum_j den_c[k][j] is the number of frames of the utterances with finite log P_u, to rounding;
+ *   (e) ghmm_grammar_post_streams' (e): a word that no allowed string can hold gets exactly zero sums;
+ *   (f) ghmm_mstep(models[k * n_streams + p], stats[k * n_streams + p]) works unchanged.  A word with zero
+ *       sums would have its variances re-inverted (see ghmm_mstep), so a trainer skips it.
+ * Asynchronous on the context's stream; a second identical call repeats every byte; GHMM_OPT_DELTA is honoured.
+ * Afterwards GHMM_BUF_B holds log b[F][NS], GHMM_BUF_GAMMA gamma[F][NS], GHMM_BUF_LOGLIK log P_u; GHMM_BUF_POST
+ * is served for n_streams == 1 and refused beyond; GHMM_BUF_ALPHA, _BETA and _SCALE give GHMM_ERR_ARG; the row
+ * API does not reuse any of these buffers.  A vector's mailbox is not written: ghmm_stats_loglik copies and
+ * waits.
+ * Refusals, each before anything is launched, grown or written: whatever ghmm_grammar_post_streams refuses of
+ * the vocabulary, the corpora and the grammar; GHMM_ERR_ARG for a null stats array or entry, a vector that is
+ * not word k's stream-p shape, or a full-covariance one.
+ * Launches: ghmm_estep_embed_streams' emission sequence (2 n_streams - 1 under GHMM_K_EMISSION, with the
+ * posteriors); TWO under GHMM_K_FORWARD (k_gpost_fwd unchanged and k_gpost_bwd in its statistics form, which
+ * keeps the sums of a thread's states in registers over the frames and forms no occ or ent; csrc/ghmm_gpost.hpp);
+ * then per stream ghmm_estep_embed_streams' statistics launches and scatter.  Full-covariance words: not yet. */
+int ghmm_estep_grammar_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                               ghmm_corpus *const *corpora, int n_streams, const double *start,
+                               const double *pair, const double *fin, ghmm_stats *const *stats);
 /* ghmm_logscore (above) on the sum of the streams' log b, log b = ((log b^0 + log b^1) + ...) folded
  * exactly as in ghmm_viterbi_streams, with models[0]'s log A and both final_state conventions; 1 to 512
  * states.  n_streams == 1 is ghmm_logscore itself, the same bits.  The checks and refusals are

@@ -38,6 +38,14 @@
 // it, and after the frame's barrier lane k adds word k's gammas in ascending j into occ and copies the
 // first state's entry share into ent.  Where log P_u is not finite the block writes zero rows and returns.
 //
+// k_gpost_bwd<PASSES, true> is the statistics form of the backward launch (ghmm_estep_grammar_streams): the same
+// step, and besides gamma every thread keeps the running sums of its states over the frames in registers, as
+// k_embed_bwd does (xi[0..delta], stay, gamma; 8 x 11 at PASSES = 8), and writes them at the end straight into
+// one partial per utterance in the layout k_reduce_all reads for a model of NS states.  There is one copy of
+// each word in this lattice: nothing is tied, no list is walked, no LDS is added.  occ and ent are not formed
+// (null is passed; rows_out and the g / ge rows are skipped).  The exits (T <= 0, a log P that is not finite)
+// write zero partials, and the second zeroes the utterance's posterior rows as well (gpost_posts).  The <PASSES, false> instantiations are the code they were before the parameter.
+//
 // The table (forward: pair, backward: pairT) is staged in LDS while the launch's LDS stays within
 // GRAMMAR_STAGE_LDS, otherwise read from L2, as in k_grammar.
 #pragma once
@@ -249,29 +257,67 @@ k_gpost_fwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const doubl
     loglik[u] = m + log(s);
 }
 
-// gamma[F][NS], occ[F][K], ent[F][K]
-template <int PASSES>
+// The statistics form's view of the mixture posteriors that the statistics launches will weigh with gamma:
+// stream p's rows post[p][F][NS * M[p]].  An utterance whose log P is not finite must add nothing to any sum,
+// and 0 x NaN is not nothing (a column whose log b is NaN has NaN posteriors), so the block zeroes the
+// utterance's posterior rows beside its gamma rows: every weight is then exactly 0 and the statistics launches
+// pass over its frames.
+constexpr int GPOST_MAX_STREAMS = 8;
+struct gpost_posts {
+    double *post[GPOST_MAX_STREAMS];
+    int M[GPOST_MAX_STREAMS];
+    int P;
+};
+
+// gamma[F][NS], occ[F][K], ent[F][K].  STATS (ghmm_estep_grammar_streams): occ and ent are null and not formed;
+// part_*: one partial per utterance (slot = u of U) for a model of NS states, as k_embed_bwd leaves them for
+// k_reduce_all.  Without STATS delta and part_* are not read.
+template <int PASSES, bool STATS = false>
 __global__ void __launch_bounds__(GPOST_THREADS)
 k_gpost_bwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const double *__restrict__ logb,
             const long long *__restrict__ off, const double *__restrict__ gram, int staged,
             const double *__restrict__ la, const double *__restrict__ xrow, const double *__restrict__ loglik,
             double *__restrict__ gamma, double *__restrict__ occ, double *__restrict__ ent,
-            const int *__restrict__ order)
+            const int *__restrict__ order, int delta, double *__restrict__ part_xi, double *__restrict__ part_dena,
+            double *__restrict__ part_denc, gpost_posts posts)
 {
     extern __shared__ double lds[];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int u = order[blockIdx.x];
     const long long f0 = off[u];
     const int T = (int)(off[u + 1] - f0);
-    if (T <= 0) return;
-    double *gu = gamma + f0 * NS, *ou = occ + f0 * K, *nu = ent + f0 * K;
+    // an utterance that adds nothing to the sums (no frames, or a log P that is not finite): zero partials
+    auto no_sums = [&]() {
+        for (int c = tid; c < NS; c += nt) {
+            for (int o = 0; o <= delta; o++) part_xi[pxi_at(u, c, o, U)] = 0.0;
+            part_dena[pden_at(u, c, U)] = 0.0;
+            part_denc[pden_at(u, c, U)] = 0.0;
+        }
+    };
+    if (T <= 0) {
+        if constexpr (STATS) no_sums();
+        return;
+    }
+    double *gu = gamma + f0 * NS, *ou = nullptr, *nu = nullptr;
+    if constexpr (!STATS) {
+        ou = occ + f0 * K;
+        nu = ent + f0 * K;
+    }
     const double logP = loglik[u];
     if (!(fabs(logP) < INFINITY)) { // (a NaN included) no allowed string, or a NaN column: zero rows
         for (size_t i = tid; i < (size_t)T * NS; i += nt) gu[i] = 0.0;
-        for (size_t i = tid; i < (size_t)T * K; i += nt) {
-            ou[i] = 0.0;
-            nu[i] = 0.0;
-        }
+        if constexpr (STATS) {
+            no_sums();
+            for (int p = 0; p < posts.P; p++) {
+                const size_t row = (size_t)NS * posts.M[p];
+                double *pu = posts.post[p] + (size_t)f0 * row;
+                for (size_t i = tid; i < (size_t)T * row; i += nt) pu[i] = 0.0;
+            }
+        } else
+            for (size_t i = tid; i < (size_t)T * K; i += nt) {
+                ou[i] = 0.0;
+                nu[i] = 0.0;
+            }
         return;
     }
     const size_t KK = staged ? (size_t)K * K : 0;
@@ -288,6 +334,18 @@ k_gpost_bwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const doubl
     __syncthreads();
     // the NEXT step's la, log b and (first states) x, loaded a frame ahead
     double an[PASSES], bn[PASSES], xn[PASSES];
+    // STATS: a state's running sums over the frames, in registers as in k_embed_bwd (one copy of each word in
+    // this lattice: nothing is tied); without STATS one element each, never touched
+    constexpr int SP = STATS ? PASSES : 1, SO = STATS ? MAX_DELTA + 1 : 1;
+    double xi[SP][SO], st[SP], gs[SP], gl[SP];
+    if constexpr (STATS) {
+#pragma unroll
+        for (int p = 0; p < PASSES; p++) {
+            st[p] = gs[p] = gl[p] = 0.0;
+#pragma unroll
+            for (int o = 0; o <= MAX_DELTA; o++) xi[p][o] = 0.0;
+        }
+    }
     // frame T-1: lbe = fin in the words' last states; gamma_{T-1}; w_{T-2}
     {
         double *wn = w + (size_t)((T - 2) & 1) * NS, *wfn = wf + (size_t)((T - 2) & 1) * K;
@@ -308,8 +366,11 @@ k_gpost_bwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const doubl
                 const double al = lu[(size_t)(T - 1) * NS + s], lbt = lb[(size_t)(T - 1) * NS + s];
                 const double gv = exp_emis((al + be) - logP);
                 gu[(size_t)(T - 1) * NS + s] = gv;
-                gt[s] = gv;
-                if (j == 0) get[k] = T > 1 ? exp_emis(((xu[(size_t)(T - 1) * K + k] + lbt) + be) - logP) : gv;
+                if constexpr (STATS) gl[p] = gv; // gamma_{T-1}: in den_c (t < T) but not in den_a (t < T-1)
+                else {
+                    gt[s] = gv;
+                    if (j == 0) get[k] = T > 1 ? exp_emis(((xu[(size_t)(T - 1) * K + k] + lbt) + be) - logP) : gv;
+                }
                 if (T > 1) {
                     wn[s] = be + lbt;
                     if (j == 0) {
@@ -334,7 +395,7 @@ k_gpost_bwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const doubl
             nu[(size_t)t * K + k] = get[k];
         }
     };
-    rows_out(T - 1);
+    if constexpr (!STATS) rows_out(T - 1);
 
     for (int t = T - 2; t >= 0; t--) {
         const double *wt = w + (size_t)(t & 1) * NS, *wft = wf + (size_t)(t & 1) * K;
@@ -374,15 +435,46 @@ k_gpost_bwd(int U, int K, int NS, const fwd_model *__restrict__ tab, const doubl
             const double be = (mt & CN_END) ? embed_lse2(wi, gpost_combine(pm, ps, K, k, R)) : wi;
             const double gv = exp_emis((al + be) - logP);
             gu[(size_t)t * NS + s] = gv;
-            gt[s] = gv;
-            if (j == 0) get[k] = t > 0 ? exp_emis(((x + lbt) + be) - logP) : gv;
+            if constexpr (STATS) {
+                // the band's xi: a transition with a_{j,j+o} == 0 (or outside the word / the band) is not a term
+                const double ls = la_self[s], ln = la_next[s];
+                if (ls != -INFINITY) xi[p][0] += exp_emis(((al + ls) + wt[s]) - logP);
+                if (delta >= 1 && ln != -INFINITY) xi[p][1] += exp_emis(((al + ln) + wt[s + 1]) - logP);
+                if (delta >= 2) {
+                    const fwd_model mk = tab[k];
+#pragma unroll
+                    for (int o = 2; o <= MAX_DELTA; o++)
+                        if (o <= delta && j + o < mk.N) {
+                            const double a = mk.A[j * mk.N + j + o];
+                            if (a != -INFINITY) xi[p][o] += exp_emis(((al + a) + wt[s + o]) - logP);
+                        }
+                }
+                gs[p] += gv;
+                st[p] += exp_emis((al + wi) - logP);
+            } else {
+                gt[s] = gv;
+                if (j == 0) get[k] = t > 0 ? exp_emis(((x + lbt) + be) - logP) : gv;
+            }
             if (t > 0) {
                 wn[s] = be + lbt;
                 if (j == 0) wfn[k] = be + lbt;
             }
         }
         __syncthreads();
-        rows_out(t);
+        if constexpr (!STATS) rows_out(t);
+    }
+    if constexpr (STATS) {
+        // every composite state is its own: the sums leave from the registers that formed them
+#pragma unroll
+        for (int p = 0; p < PASSES; p++) {
+            const int s = tid + p * nt;
+            if (s >= NS) continue;
+#pragma unroll
+            for (int o = 0; o <= MAX_DELTA; o++)
+                if (o <= delta) part_xi[pxi_at(u, s, o, U)] = xi[p][o];
+            part_dena[pden_at(u, s, U)] = st[p];
+            part_denc[pden_at(u, s, U)] = gs[p] + gl[p];
+        }
     }
 }
 

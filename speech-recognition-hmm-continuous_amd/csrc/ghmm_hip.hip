@@ -1946,6 +1946,32 @@ extern "C" int ghmm_mstep(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *s)
     return model_prepare(ctx, m, false);
 }
 
+// The extended Baum-Welch update (definition in include/ghmm.h): ONE launch of k_mstep_ebw, block = state,
+// which derives wk, logwk and log A itself as k_mstep does; then what ghmm_model_set does behind its own
+// preparation launch, so that the next emission, matrix-core tier included, sees the new model: a new epoch,
+// the statistics classes unknown to the host for a while (vec_until), and the matrix-core preparation.
+extern "C" int ghmm_mstep_ebw(ghmm_ctx *ctx, ghmm_model *m, ghmm_stats *num, ghmm_stats *den, double E)
+{
+    int rc = use(ctx);
+    if (ctx && ctx->last_m == m) ctx->last_m = nullptr; // alpha^ / W on the device belong to the old parameters
+    if (rc) return rc;
+    ARG_CHECK(m && num && den, "null argument");
+    if ((rc = check_stats(m, num)) || (rc = check_stats(m, den))) return rc;
+    ARG_CHECK(E >= 0.0 && E < INFINITY, "the damping constant E is negative, NaN or infinite");
+    m->epoch++;
+    m->vec_until = m->epoch + VEC_WINDOW;
+    m->prep_mark = ++ctx->launch_mark;
+    m->banded = m->banded && ctx->delta <= 1; // (as in ghmm_mstep)
+    {
+        kscope ks(ctx, GHMM_K_MSTEP);
+        hipLaunchKernelGGL(k_mstep_ebw, dim3((unsigned)m->N), dim3(MS2_THREADS), 0, ctx->stream, m->N, m->M, m->D,
+                           (const double *)num->v, (const double *)den->v, E, pow(2.0 * M_PI, m->D / 2.0), m->A, m->c,
+                           m->mean, m->inv_var, m->det, m->wk, m->logwk, m->logA, (int)ctx->delta);
+    }
+    if ((rc = launch_ok("k_mstep_ebw"))) return rc;
+    return model_prepare(ctx, m, false);
+}
+
 // creating_initial_model (TF:732-1317): distance / accumulation passes on the device (hard
 // statistics through the vector-ALU statistics kernel: direct (x - mean)^2, no expanded
 // form), cell bookkeeping on the host exactly as the reference orders it.
@@ -2569,6 +2595,59 @@ extern "C" int ghmm_align_streams(ghmm_ctx *ctx, ghmm_model *const *models, int 
     return vocab_align(ctx, v, corpora[0], pl, seq, seq_off, word_host, path_host, begin_host, score_host);
 }
 
+// An embedded E-step behind its checks (U > 0) up to its lattice: the gathers with the log tables, then one
+// emission launch per stream in mode 3 (log b with the stream's posteriors: the workspace's own buffer for one
+// stream, post_s[p] for several), every later stream folded into b.  Called by ghmm_estep_embed_streams and
+// ghmm_estep_grammar_streams.
+static int embed_emission(ghmm_ctx *ctx, ghmm_model *const *models, int n_models, ghmm_corpus *const *corpora, int P,
+                          dvocab *v)
+{
+    int rc;
+    ghmm_corpus *c = corpora[0];
+    if ((rc = vocab_gather(ctx, models, n_models, P, true, v))) return rc;
+    const size_t F = (size_t)c->F, FN = F * v->NS;
+    if ((rc = ws_frames(ctx, v->cats[0], c, P == 1))) return rc;
+    if (P > 1) {
+        if ((rc = ctx->b_stream.grow(FN))) return rc;
+        for (int p = 0; p < P; p++)
+            if ((rc = ctx->post_s[p].grow(FN * v->cats[p]->M))) return rc;
+    }
+    for (int p = 0; p < P; p++) {
+        if ((rc = run_emission(ctx, v->cats[p], corpora[p], 3, p == 0 ? ctx->b : ctx->b_stream,
+                               P == 1 ? ctx->post : ctx->post_s[p])))
+            return rc;
+        if (p > 0 && FN && (rc = fold_stream(ctx, FN, true))) return rc;
+    }
+    return GHMM_OK;
+}
+
+// ... and behind its lattice, which left gamma[F][NS], log P_u and one partial per utterance: per stream
+// ghmm_estep's statistics launches on the CONCATENATED model into a vector of the context's, and one scatter
+// of every word's diagonal blocks into its own vector (ddst: the lattice's scatter table)
+static int embed_statistics(ghmm_ctx *ctx, const dvocab &v, int n_models, ghmm_corpus *const *corpora, int P,
+                            ghmm_stats *const *stats, const embed_dst *ddst)
+{
+    int rc;
+    for (int p = 0; p < P; p++) {
+        ghmm_model *cat = v.cats[p];
+        ghmm_stats cs; // the concatenated model's vector: the context's, without a mailbox
+        cs.N = cat->N; cs.M = cat->M; cs.D = cat->D;
+        cs.n = ghmm_stats_len(cat->N, cat->M, cat->D);
+        if ((rc = ctx->em_vec[p].grow(cs.n))) return rc;
+        cs.v = ctx->em_vec[p];
+        if ((rc = run_accumulate(ctx, cat, corpora[p], &cs, P == 1 ? ctx->post : ctx->post_s[p]))) return rc;
+        {
+            kscope ks(ctx, GHMM_K_REDUCE);
+            hipLaunchKernelGGL(k_embed_scatter, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, cat->N, cat->M,
+                               cat->D, (const double *)cs.v, ddst + (size_t)p * n_models);
+        }
+        if ((rc = launch_ok("k_embed_scatter"))) return rc;
+        // (the words' vectors are not k_reduce_all's: its mailbox does not describe them)
+        for (int k = 0; k < n_models; k++) stats[(size_t)k * P + p]->mbox_valid = false;
+    }
+    return GHMM_OK;
+}
+
 // ---- embedded Baum-Welch on word transcripts (ghmm_estep_embed_streams; definition in include/ghmm.h):
 // the vocabulary's gathers with the log tables, its emission in mode 3 (log b with every stream's
 // posteriors), the lattice over the transcripts' word instances (vocab_embed), ghmm_estep's statistics
@@ -2588,40 +2667,34 @@ extern "C" int ghmm_estep_embed_streams(ghmm_ctx *ctx, ghmm_model *const *models
     ghmm_corpus *c = corpora[0];
     if (c->U == 0) return embed_empty(ctx, stats, n_models * P);
     if ((rc = align_check(models, n_models, P, c, v, seq, seq_off, __func__, &pl))) return rc;
-    if ((rc = vocab_gather(ctx, models, n_models, P, true, &v))) return rc;
-    const size_t F = (size_t)c->F, FN = F * v.NS;
-    if ((rc = ws_frames(ctx, v.cats[0], c, P == 1))) return rc;
-    if (P > 1) {
-        if ((rc = ctx->b_stream.grow(FN))) return rc;
-        for (int p = 0; p < P; p++)
-            if ((rc = ctx->post_s[p].grow(FN * v.cats[p]->M))) return rc;
-    }
-    for (int p = 0; p < P; p++) {
-        if ((rc = run_emission(ctx, v.cats[p], corpora[p], 3, p == 0 ? ctx->b : ctx->b_stream,
-                               P == 1 ? ctx->post : ctx->post_s[p])))
-            return rc;
-        if (p > 0 && FN && (rc = fold_stream(ctx, FN, true))) return rc;
-    }
+    if ((rc = embed_emission(ctx, models, n_models, corpora, P, &v))) return rc;
     const embed_dst *ddst;
     if ((rc = embed_lattice(ctx, models, n_models, P, v.cats[0]->M, c, v, pl, seq, seq_off, stats, &ddst))) return rc;
-    for (int p = 0; p < P; p++) {
-        ghmm_model *cat = v.cats[p];
-        ghmm_stats cs; // the concatenated model's vector: the context's, without a mailbox
-        cs.N = cat->N; cs.M = cat->M; cs.D = cat->D;
-        cs.n = ghmm_stats_len(cat->N, cat->M, cat->D);
-        if ((rc = ctx->em_vec[p].grow(cs.n))) return rc;
-        cs.v = ctx->em_vec[p];
-        if ((rc = run_accumulate(ctx, cat, corpora[p], &cs, P == 1 ? ctx->post : ctx->post_s[p]))) return rc;
-        {
-            kscope ks(ctx, GHMM_K_REDUCE);
-            hipLaunchKernelGGL(k_embed_scatter, dim3((unsigned)n_models), dim3(256), 0, ctx->stream, cat->N, cat->M,
-                               cat->D, (const double *)cs.v, ddst + (size_t)p * n_models);
-        }
-        if ((rc = launch_ok("k_embed_scatter"))) return rc;
-        // (the words' vectors are not k_reduce_all's: its mailbox does not describe them)
-        for (int k = 0; k < n_models; k++) stats[(size_t)k * P + p]->mbox_valid = false;
-    }
-    return GHMM_OK;
+    return embed_statistics(ctx, v, n_models, corpora, P, stats, ddst);
+}
+
+// ---- Baum-Welch statistics on the grammar lattice (ghmm_estep_grammar_streams; definition in include/ghmm.h):
+// the embedded E-step's emission sequence, ghmm_grammar_post_streams' lattice with its backward launch in the
+// statistics form (vocab_grammar_stats), and the embedded E-step's statistics launches and scatters
+extern "C" int ghmm_estep_grammar_streams(ghmm_ctx *ctx, ghmm_model *const *models, int n_models,
+                                          ghmm_corpus *const *corpora, int P, const double *start,
+                                          const double *pair, const double *fin, ghmm_stats *const *stats)
+{
+    dvocab v;
+    int rc = use(ctx);
+    if (rc || (rc = vocab_check(ctx, models, n_models, corpora, P, true, true, __func__, &v)) ||
+        (rc = grammar_check(v, n_models, corpora[0]->U, start, pair, fin, __func__)))
+        return rc;
+    ARG_CHECK_AS(__func__, stats, "null statistics");
+    for (int k = 0; k < n_models * P; k++)
+        if ((rc = check_stats(models[k], stats[k]))) return rc;
+    ghmm_corpus *c = corpora[0];
+    if (c->U == 0) return embed_empty(ctx, stats, n_models * P);
+    if ((rc = embed_emission(ctx, models, n_models, corpora, P, &v))) return rc;
+    const embed_dst *ddst;
+    if ((rc = vocab_grammar_stats(ctx, models, n_models, P, v.cats[0]->M, c, v, start, pair, fin, stats, &ddst)))
+        return rc;
+    return embed_statistics(ctx, v, n_models, corpora, P, stats, ddst);
 }
 
 // ---- the forward score in the log domain (ghmm_logscore and its three companions; definitions in

@@ -1404,6 +1404,85 @@ k_mstep(int N, int M, int D, const double *__restrict__ stats, double norm2pi,
     mstep_state(N, M, D, stats, norm2pi, A, c, mean, inv_var, det, wk, logwk, logA, lds_doubles, vs, delta);
 }
 
+// The extended Baum-Welch update of ghmm_mstep_ebw (definition in include/ghmm.h), block = state.
+// Transitions and weights come from the numerator vector alone by mstep_state's expressions (its global
+// path: the band mask, the kept row, the kept weights, changing_zero_coef with its sum in index order).  Then a
+// thread per Gaussian walks its D coefficients in index order three times: the larger roots and their maximum,
+// the new mean and variance of every coefficient, the determinant's product; nothing is shared between the
+// Gaussians, so there is no LDS and one path for every shape.  The discriminant is formed as
+// (dv - s2 dc)^2 + 4 s2 dm^2, which is the same polynomial and cannot cancel below zero, and the larger root in
+// the form that does not subtract two close numbers.
+__device__ __forceinline__ double ebw_root(double s2, double dc, double dm, double dv)
+{
+    const double b = dv + s2 * dc, q = dv * dc - dm * dm, h = dv - s2 * dc;
+    const double sq = sqrt(h * h + 4.0 * s2 * (dm * dm));
+    const double r = b <= 0.0 ? (sq - b) / (2.0 * s2) : -2.0 * q / (b + sq);
+    return r > 0.0 ? r : 0.0; // (a NaN gives 0)
+}
+
+__global__ void __launch_bounds__(MS2_THREADS)
+k_mstep_ebw(int N, int M, int D, const double *__restrict__ num, const double *__restrict__ den, double E,
+            double norm2pi, double *__restrict__ A, double *__restrict__ c, double *__restrict__ mean,
+            double *__restrict__ inv_var, double *__restrict__ det, double *__restrict__ wk,
+            double *__restrict__ logwk, double *__restrict__ logA, int delta)
+{
+    const int G = N * M, i = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const double *num_a = num, *den_a = num_a + (size_t)N * N, *den_c = den_a + N;
+    const double *n_c = den_c + N, *n_mu = n_c + G, *n_var = n_mu + (size_t)G * D;
+    const double *d_c = den + (size_t)N * N + 2 * (size_t)N, *d_mu = d_c + G, *d_var = d_mu + (size_t)G * D;
+    for (int j = tid; j < N; j += nt) {
+        double v = A[i * N + j];
+        if (den_a[i] != 0.0) {
+            v = (j >= i && j <= i + delta) ? num_a[i * N + j] / den_a[i] : 0.0;
+            A[i * N + j] = v;
+        }
+        logA[i * N + j] = v > 0.0 ? log(v) : -INFINITY;
+    }
+    if (den_c[i] != 0.0)
+        for (int m = tid; m < M; m += nt) c[i * M + m] = n_c[i * M + m] / den_c[i];
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int k = 0; k < M; k++) {
+            double v = c[i * M + k];
+            if (v < FLOOR) v = FLOOR;
+            c[i * M + k] = v;
+            sum += v;
+        }
+        for (int k = 0; k < M; k++) c[i * M + k] /= sum;
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += nt) {
+        const int g = i * M + m;
+        const size_t q0 = (size_t)g * D;
+        const double cn = n_c[g], cd = d_c[g], dc = cn - cd;
+        double rmax = 0.0;
+        for (int d = 0; d < D; d++) {
+            const double mu = mean[q0 + d], s2 = 1.0 / inv_var[q0 + d];
+            const double dm = (n_mu[q0 + d] - d_mu[q0 + d]) - dc * mu, dv = n_var[q0 + d] - d_var[q0 + d];
+            rmax = fmax(rmax, ebw_root(s2, dc, dm, dv));
+        }
+        const double damp = fmax(E * cd, 2.0 * rmax), t = dc + damp;
+        if (t > 0.0 && t < INFINITY) { // otherwise (no statistics at all) the Gaussian keeps what it has
+            double dt = 1.0;
+            for (int d = 0; d < D; d++) {
+                const double mu = mean[q0 + d], s2 = 1.0 / inv_var[q0 + d];
+                const double dm = (n_mu[q0 + d] - d_mu[q0 + d]) - dc * mu, dv = n_var[q0 + d] - d_var[q0 + d];
+                const double step = dm / t;
+                double v = (dv + damp * s2) / t - step * step;
+                if (v < FLOOR) v = FLOOR;
+                mean[q0 + d] = mu + step;
+                inv_var[q0 + d] = 1.0 / v;
+                dt *= v;
+            }
+            det[g] = dt;
+        }
+        const double dn = norm2pi * sqrt(fabs(det[g]));
+        wk[g] = c[g] / dn;
+        logwk[g] = log(c[g]) - log(dn);
+    }
+}
+
 // The cell bookkeeping between two k-means passes of the initial model (TF:1043-1270), on the device:
 // new means = cell sums / counts, empty cells re-seeded from the cells of largest distortion, and
 // (do_split) the split that opens the next round — the same operations in the same order as the

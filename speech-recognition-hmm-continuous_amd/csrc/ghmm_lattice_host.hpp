@@ -408,32 +408,22 @@ static int vocab_connect_grammar(ghmm_ctx *ctx, const vocab_pass &v, int K, cons
     return GHMM_OK;
 }
 
-// The word posteriors under a grammar behind their emission launches (U > 0, grammar_check passed): the
-// grammar as vocab_connect_grammar uploads it and behind it a TRANSPOSED copy of the table (start[K] |
-// pair[K][K] | fin[K] | pairT[K][K], pairT[k' * K + k] = pair[k][k']: the backward launch reduces along the
-// table's rows, ghmm_gpost.hpp says why it reads a copy) into the context's gr_tab ahead of the launches on
-// the same stream; then k_gpost_fwd (la rows [F][NS] into em_la, x rows [F][K] into gp_x, log P_u into loglik)
-// and k_gpost_bwd (gamma[F][NS], occ and ent [F][K] into gp_occ and gp_ent), one workgroup per utterance
-// each, both under GHMM_K_FORWARD; then log P, occ and (if asked for) ent to the host.  The workspace's
-// bookkeeping is embed_lattice's: it belongs to the concatenated vocabulary, holds log b, gamma and log P,
-// and alpha, beta and c_t are nobody's.  Waits for the stream.  Called by ghmm_grammar_post_streams and
-// ghmm_grammar_post_full_streams; it knows no kind of Gaussian.
-static int vocab_grammar_post(ghmm_ctx *ctx, const vocab_pass &v, int K, const ghmm_corpus *c, const double *start,
-                              const double *pair, const double *fin, double *occ_host, double *ent_host,
-                              double *loglik_host)
+// The grammar lattice's two launches on the log b[F][NS] in the workspace (U > 0, grammar_check passed,
+// em_la, gp_x, gr_tab and what the backward form writes grown by the caller): the grammar as
+// vocab_connect_grammar uploads it and behind it a TRANSPOSED copy of the table (start[K] | pair[K][K] |
+// fin[K] | pairT[K][K], pairT[k' * K + k] = pair[k][k']: the backward launch reduces along the table's rows,
+// ghmm_gpost.hpp says why it reads a copy) into the context's gr_tab ahead of the launches on the same
+// stream; then k_gpost_fwd (la rows [F][NS] into em_la, x rows [F][K] into gp_x, log P_u into loglik) and
+// k_gpost_bwd, one workgroup per utterance each, both under GHMM_K_FORWARD: the posteriors form (gamma[F][NS],
+// occ and ent [F][K] into gp_occ and gp_ent) or with `stats` the statistics form (gamma and one partial per
+// utterance for a model of NS states in part_xi, part_dena and part_denc; occ and ent are not formed; the
+// posterior rows in `posts` of an utterance without a finite log P are zeroed).
+// Nothing waits.  Called by vocab_grammar_post and vocab_grammar_stats.
+static int gpost_launches(ghmm_ctx *ctx, const vocab_pass &v, int K, const ghmm_corpus *c, const double *start,
+                          const double *pair, const double *fin, bool stats, const gpost_posts &posts)
 {
     int rc;
-    const size_t KK = (size_t)K * K, F = (size_t)c->F, NS = (size_t)v.NS, FK = F * K;
-    if ((rc = ctx->em_la.grow(F * NS + 1)) || (rc = ctx->gamma.grow(F * NS)) || (rc = ctx->gp_x.grow(FK + 1)) ||
-        (rc = ctx->gp_occ.grow(FK + 1)) || (rc = ctx->gp_ent.grow(FK + 1)) ||
-        (rc = ctx->gr_tab.grow(2 * KK + 2 * (size_t)K)))
-        return rc;
-    ws_disown(ctx);
-    ctx->em_c = c;
-    ctx->b_is_log = true;
-    ctx->N = v.NS;
-    ctx->embed_ws = true;
-    ctx->fix_counted = false;
+    const size_t KK = (size_t)K * K;
     // (pageable sources: the copies complete before the calls return them)
     double *dstart = ctx->gr_tab, *dpair = dstart + K, *dfin = dpair + KK, *dpairT = dfin + K;
     std::vector<double> pairT(KK);
@@ -463,21 +453,60 @@ static int vocab_grammar_post(ghmm_ctx *ctx, const vocab_pass &v, int K, const g
     else GHMM_GPOST_FWD(8);
 #undef GHMM_GPOST_FWD
     if ((rc = launch_ok("k_gpost_fwd"))) return rc;
-#define GHMM_GPOST_BWD(PS)                                                                                         \
+#define GHMM_GPOST_BWD(PS, ST, OCC, ENT, DELTA, PXI, PDA, PDC)                                                     \
     do {                                                                                                           \
-        if (lds_b > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_gpost_bwd<PS>))) return rc;                 \
+        if (lds_b > (48u << 10) && (rc = lds_attr(ctx, (const void *)k_gpost_bwd<PS, ST>))) return rc;             \
         kscope ks(ctx, GHMM_K_FORWARD);                                                                            \
-        hipLaunchKernelGGL(k_gpost_bwd<PS>, dim3((unsigned)c->U), dim3((unsigned)threads), lds_b, ctx->stream, c->U, \
-                           K, v.NS, v.dtab, (const double *)ctx->b, c->off, (const double *)ctx->gr_tab.p,         \
+        hipLaunchKernelGGL((k_gpost_bwd<PS, ST>), dim3((unsigned)c->U), dim3((unsigned)threads), lds_b, ctx->stream, \
+                           c->U, K, v.NS, v.dtab, (const double *)ctx->b, c->off, (const double *)ctx->gr_tab.p,   \
                            (int)gpost_staged(base_b, K), (const double *)ctx->em_la, (const double *)ctx->gp_x,    \
-                           (const double *)ctx->loglik, ctx->gamma, ctx->gp_occ, ctx->gp_ent, c->order);           \
+                           (const double *)ctx->loglik, ctx->gamma, OCC, ENT, c->order, DELTA, PXI, PDA, PDC,      \
+                           posts);                                                                                 \
     } while (0)
-    if (passes <= 1) GHMM_GPOST_BWD(1);
-    else if (passes <= 2) GHMM_GPOST_BWD(2);
-    else if (passes <= 4) GHMM_GPOST_BWD(4);
-    else GHMM_GPOST_BWD(8);
+#define GHMM_GPOST_BWD_POST(PS)                                                                                    \
+    GHMM_GPOST_BWD(PS, false, ctx->gp_occ, ctx->gp_ent, 0, (double *)nullptr, (double *)nullptr, (double *)nullptr)
+#define GHMM_GPOST_BWD_STATS(PS)                                                                                   \
+    GHMM_GPOST_BWD(PS, true, (double *)nullptr, (double *)nullptr, (int)ctx->delta, ctx->part_xi, ctx->part_dena,  \
+                   ctx->part_denc)
+    if (!stats) {
+        if (passes <= 1) GHMM_GPOST_BWD_POST(1);
+        else if (passes <= 2) GHMM_GPOST_BWD_POST(2);
+        else if (passes <= 4) GHMM_GPOST_BWD_POST(4);
+        else GHMM_GPOST_BWD_POST(8);
+    } else {
+        if (passes <= 1) GHMM_GPOST_BWD_STATS(1);
+        else if (passes <= 2) GHMM_GPOST_BWD_STATS(2);
+        else if (passes <= 4) GHMM_GPOST_BWD_STATS(4);
+        else GHMM_GPOST_BWD_STATS(8);
+    }
+#undef GHMM_GPOST_BWD_STATS
+#undef GHMM_GPOST_BWD_POST
 #undef GHMM_GPOST_BWD
-    if ((rc = launch_ok("k_gpost_bwd"))) return rc;
+    return launch_ok("k_gpost_bwd");
+}
+
+// The word posteriors under a grammar behind their emission launches (U > 0, grammar_check passed): the
+// lattice's two launches (gpost_launches, the posteriors form), then log P, occ and (if asked for) ent to
+// the host.  The workspace's bookkeeping is embed_lattice's: it belongs to the concatenated vocabulary,
+// holds log b, gamma and log P, and alpha, beta and c_t are nobody's.  Waits for the stream.  Called by
+// ghmm_grammar_post_streams and ghmm_grammar_post_full_streams; it knows no kind of Gaussian.
+static int vocab_grammar_post(ghmm_ctx *ctx, const vocab_pass &v, int K, const ghmm_corpus *c, const double *start,
+                              const double *pair, const double *fin, double *occ_host, double *ent_host,
+                              double *loglik_host)
+{
+    int rc;
+    const size_t KK = (size_t)K * K, F = (size_t)c->F, NS = (size_t)v.NS, FK = F * K;
+    if ((rc = ctx->em_la.grow(F * NS + 1)) || (rc = ctx->gamma.grow(F * NS)) || (rc = ctx->gp_x.grow(FK + 1)) ||
+        (rc = ctx->gp_occ.grow(FK + 1)) || (rc = ctx->gp_ent.grow(FK + 1)) ||
+        (rc = ctx->gr_tab.grow(2 * KK + 2 * (size_t)K)))
+        return rc;
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = true;
+    ctx->N = v.NS;
+    ctx->embed_ws = true;
+    ctx->fix_counted = false;
+    if ((rc = gpost_launches(ctx, v, K, c, start, pair, fin, false, gpost_posts{}))) return rc;
     HIP_TRY(hipMemcpyAsync(loglik_host, ctx->loglik, (size_t)c->U * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (ent_host && (rc = d2h_pageable(ctx, ent_host, ctx->gp_ent, FK * 8))) return rc;
     return d2h_pageable(ctx, occ_host, ctx->gp_occ, FK * 8);
@@ -702,4 +731,61 @@ static int embed_lattice(ghmm_ctx *ctx, Model *const *models, int n_models, int 
         }
     }
     return vocab_embed(ctx, v, c, pl, seq, seq_off, dst.data(), dst.size(), ddst);
+}
+
+// ------------------------------------------------ Baum-Welch statistics on the grammar lattice
+
+// The grammar E-step between its emission launches and its statistics launches (U > 0, grammar_check and the
+// stats checks passed; M0 = stream 0's mixtures): the workspace's bookkeeping, which is embed_lattice's; the
+// scatter's table (stream p's n_models entries from (*ddst)[p * n_models]: word k's vector, states and first
+// column) into the context's al_tab ahead of the launches on the same stream; then the lattice's two launches
+// in the statistics form (gpost_launches), which leave gamma[F][NS], log P_u and one partial per utterance for
+// a model of NS states, as vocab_embed leaves them for the statistics launches.  Nothing waits.  Called by
+// ghmm_estep_grammar_streams; it knows no kind of Gaussian.
+template <class Model>
+static int vocab_grammar_stats(ghmm_ctx *ctx, Model *const *models, int n_models, int P, int M0, const ghmm_corpus *c,
+                               const vocab_pass &v, const double *start, const double *pair, const double *fin,
+                               ghmm_stats *const *stats, const embed_dst **ddst)
+{
+    int rc;
+    const int K = n_models;
+    const size_t KK = (size_t)K * K, F = (size_t)c->F, NS = (size_t)v.NS, U = (size_t)c->U;
+    std::vector<embed_dst> dst((size_t)n_models * P);
+    for (int p = 0; p < P; p++) {
+        int bo = 0;
+        for (int k = 0; k < n_models; k++) {
+            const Model *m = models[(size_t)k * P + p];
+            dst[(size_t)p * n_models + k] = {stats[(size_t)k * P + p]->v, m->N, bo};
+            bo += m->N;
+        }
+    }
+    if ((rc = ctx->em_la.grow(F * NS + 1)) || (rc = ctx->gamma.grow(F * NS)) || (rc = ctx->gp_x.grow(F * K + 1)) ||
+        (rc = ctx->gr_tab.grow(2 * KK + 2 * (size_t)K)) || (rc = ctx->part_xi.grow(U * NS * (MAX_DELTA + 1))) ||
+        (rc = ctx->part_dena.grow(U * NS)) || (rc = ctx->part_denc.grow(U * NS)) ||
+        (rc = ctx->al_tab.grow(dst.size() * sizeof(embed_dst))))
+        return rc;
+    ws_disown(ctx);
+    ctx->em_c = c;
+    ctx->b_is_log = true;
+    ctx->post_valid = P == 1;
+    ctx->N = v.NS;
+    ctx->G = v.NS * M0;
+    ctx->embed_ws = true;
+    ctx->fix_counted = false; // (the lattice runs in the log domain: no utterance is taken again)
+    // (a pageable source: the copy completes before the call returns it)
+    HIP_TRY(hipMemcpyAsync(ctx->al_tab, dst.data(), dst.size() * sizeof(embed_dst), hipMemcpyHostToDevice,
+                           ctx->stream));
+    *ddst = (const embed_dst *)ctx->al_tab.p;
+    // the posteriors the statistics launches will read: an utterance without a finite log P has its rows zeroed
+    static_assert(GPOST_MAX_STREAMS == GHMM_MAX_STREAMS, "the kernel's view holds every stream");
+    gpost_posts posts{};
+    posts.P = P;
+    for (int p = 0; p < P; p++) {
+        posts.post[p] = P == 1 ? ctx->post.p : ctx->post_s[p].p;
+        posts.M[p] = models[p]->M;
+    }
+    if ((rc = gpost_launches(ctx, v, K, c, start, pair, fin, true, posts))) return rc;
+    ctx->slots = c->U; // one partial per utterance
+    ctx->loglik_pieces = false;
+    return GHMM_OK;
 }

@@ -97,6 +97,7 @@ SYMBOLS = {
     "ghmm_fetch_range": (C.c_int, [_vp, C.c_int, C.c_size_t, _dp, C.c_size_t], True),
     "ghmm_estep": (C.c_int, [_vp, _vp, _vp, _vp], True),
     "ghmm_mstep": (C.c_int, [_vp, _vp, _vp], True),
+    "ghmm_mstep_ebw": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double], True),
     "ghmm_score": (C.c_int, [_vp, _vp, _vp, _dp], True),
     "ghmm_score_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _vp, _dp], True),
     "ghmm_estep_streams": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp)], True),
@@ -123,6 +124,8 @@ SYMBOLS = {
                                      _dp], True),
     "ghmm_estep_embed_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
                                            C.POINTER(_vp)], True),
+    "ghmm_estep_grammar_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _dp, _dp, _dp,
+                                             C.POINTER(_vp)], True),
     "ghmm_align_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip, _ip, _ip,
                                           _ip, _dp], True),
     "ghmm_estep_embed_full_streams": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _ip, _ip,
@@ -773,6 +776,14 @@ class Context:
     def mstep(self, model, stats):
         _check(self.lib.ghmm_mstep(self.h, model.h, stats.h), self.lib)
 
+    def mstep_ebw(self, model, num, den, E=2.0):
+        """the extended Baum-Welch update in place: means and variances from the numerator vector `num`
+        (the transcripts' statistics) against the denominator vector `den` (estep_grammar_streams'), damped per
+        Gaussian by max(E * den.num_c, twice the value that keeps every variance positive); weights and
+        transitions from `num` alone as mstep would set them.  Both vectors must have been accumulated on this
+        model.  Asynchronous"""
+        _check(self.lib.ghmm_mstep_ebw(self.h, model.h, num.h, den.h, float(E)), self.lib)
+
     def score(self, model, corpus):
         out = np.empty(corpus.n_utt, dtype=np.float64)
         _check(self.lib.ghmm_score(self.h, model.h, corpus.h, _d(out)), self.lib)
@@ -970,6 +981,27 @@ class Context:
         """estep_embed_streams for full-covariance words: stats[k][p] is a stats_full vector of word k's
         stream-p shape, so that mstep_full or mstep_full_dev(vocab[k][p], stats[k][p]) follows"""
         self._estep_embed(self.lib.ghmm_estep_embed_full_streams, vocab, corpora, transcripts, stats)
+
+    def estep_grammar_streams(self, vocab, corpora, pair, stats, start=None, fin=None):
+        """the Baum-Welch E-step over grammar_post_streams' lattice, that is over EVERY word string the grammar
+        (pair, start, fin: connect_grammar_streams') allows: stats[k][p] (word k's stream-p shape) is
+        overwritten in estep_embed_streams' layout, so that mstep(vocab[k][p], stats[k][p]) follows.  The sums
+        are normalised by the lattice's own log P_u (not estep_embed_streams' log Z_u); an utterance whose log P
+        is not finite adds only that to the summed log P.  Asynchronous; fetch(BUF_GAMMA, (frames, NS)) and
+        fetch(BUF_LOGLIK, (n_utt,)) are grammar_post_streams'"""
+        K = len(vocab)
+        pair = np.ascontiguousarray(pair, dtype=np.float64)
+        if pair.shape != (K, K):
+            raise ValueError(f"pair has shape {pair.shape}, the vocabulary has {K} words")
+        rows = []
+        for name, a in (("start", start), ("fin", fin)):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            if a is not None and a.shape != (K,):
+                raise ValueError(f"{name} has shape {a.shape}, the vocabulary has {K} words")
+            rows.append(a)
+        _check(self.lib.ghmm_estep_grammar_streams(self.h, self._vocab_handles(vocab), K,
+                                                   self._stream_handles(corpora), len(corpora), _d(rows[0]),
+                                                   _d(pair), _d(rows[1]), self._vocab_handles(stats)), self.lib)
 
     # ---- the forward score of diagonal models in the log domain
     def logscore(self, model, corpus, final_state=False):
